@@ -8,14 +8,18 @@ the hand-written HIP kernels of libbts_hip.so -- at B=16 per GPU, 3x352x1216 fp3
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W       # or under torchrun: RANK / LOCAL_RANK / WORLD_SIZE from the env
     python bench.py --gpus 8 --global-batch 64      # BASELINE.json configs[3]: B=64 sharded 8 x 8 (strong scaling)
+    python bench.py --gpus 1 --full                 # + roofline leg, emulated-fp32 leg, CPU baseline and parity gate
+    python bench.py --gpus 1 --dump-outputs DIR     # + the last timed step's outputs as DIR/<name>.npy
 
 Weak scaling by default (--batch frames per GPU); --global-batch G fixes the total and shards it.  `n_gpus` in the
 JSON line is the number of ranks RCCL actually formed; a mismatch with --gpus is an error, never a silent 1-GPU run.
-Rank 0 prints ONE JSON line (contract in the task statement) with `roofline` (dominant hand-written
+Rank 0 prints ONE JSON line (contract in the task statement).  A plain run only sets up, warms up, times --steps steps
+and prints it (`roofline` is null).  With --full the line also carries `roofline` (dominant hand-written
 kernel, HIP-event timed on its launch stream; `roofline.survey_8d` = SURVEY.md section 8(d)'s own definitions for the
-ASPP branches and the fused reduction + LPG launches; `roofline.groups` / `.kernels` = every call site / kernel family)
-and `cpu_baseline` (the CPU oracle on the host cores).  `config.fill_frames` is the frames-per-launch declaration the
-library's tile / split-K choices were sized for (the per-GPU batch, at most 16).
+ASPP branches and the fused reduction + LPG launches; `roofline.groups` / `.kernels` = every call site / kernel family),
+`emulated_fp32_bf16x3` (N=1) and `cpu_baseline` with the same-run `parity` gate (N=1; the CPU oracle on the host cores).
+`config.fill_frames` is the frames-per-launch declaration the library's tile / split-K choices were sized for (the
+per-GPU batch, at most 16).
 """
 import argparse
 import json
@@ -61,6 +65,25 @@ def build_model(params, device, seed=0):
     model.decoder.load_state_dict(sd, strict=True)
     # keep random-init encoder activations O(1): eval-BN with unit stats does not renormalise 160 layers
     return model.eval().to(device)
+
+
+OUTPUT_NAMES = ("depth_8x8_scaled", "depth_4x4_scaled", "depth_2x2_scaled", "reduc1x1", "final_depth", "iconv1")
+DUMP_BUDGET_BYTES = 60_000_000          # all files together stay under 64 MB, .npy headers included
+
+
+def dump_outputs(arrays, out_dir, budget=DUMP_BUDGET_BYTES):
+    """Write {name: tensor} as out_dir/<name>.npy in float32.  A tensor with more elements than its equal share of
+    `budget` is stored as a fixed sample instead: its flattened elements at the sorted unique indices of
+    PCG64(0).integers(0, numel, share) -- the same positions in every run with the same shapes, so two builds can be
+    compared element for element.  (B=16 at 352x1216: ~137 MB of depth maps + 876 MB of iconv1 in the full outputs.)"""
+    os.makedirs(out_dir, exist_ok=True)
+    share = budget // (4 * len(arrays))
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > share:
+            idx = np.unique(np.random.default_rng(0).integers(0, t.numel(), share))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
 
 
 def pmc_traffic(kernel):
@@ -236,9 +259,16 @@ def build_parser():
     ap.add_argument("--dataset", choices=["kitti", "nyu"], default="kitti",
                     help="decoder head: kitti (max_depth 80, focal scaling) or nyu (max_depth 10), bts.py:289-291")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of hipGraph replay")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the roofline leg (HIP-event timed isolated launches), the "
+                         "bf16x3-emulated-fp32 leg and the CPU baseline with its parity gate (the last two N=1 only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32, rank 0; the gathered maps "
+                         "when N > 1).  An output above its share of 60 MB is stored as a fixed sample: the flattened "
+                         "elements at the sorted unique indices of PCG64(0).integers(0, size, share)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline and parity gate")
     ap.add_argument("--no-emulated-leg", action="store_true",
-                    help="skip the secondary bf16x3-emulated-fp32 measurement (N=1 only; never the headline value)")
+                    help="--full without the secondary bf16x3-emulated-fp32 measurement (N=1 only; never the headline value)")
     ap.add_argument("--no-gather", action="store_true", help="skip the per-step all-gather of the 5 depth maps (N>1)")
     ap.add_argument("--streams", type=int, default=4,
                     help="run the per-GPU batch as this many concurrent sub-batches on separate HIP streams (one graph): "
@@ -528,15 +558,22 @@ def main():
         log("timed %d steps: %.3f ms/step" % (args.steps, 1e3 * elapsed / args.steps))
         # frame 0 of what the LAST TIMED step produced (the replayed graph's static outputs): this is what the parity gate
         # below compares with the CPU oracle -- the timed outputs themselves, not a fresh forward
-        timed_frame0 = [o[0:1].clone() for o in outs] if (rank == 0 and not args.decoder_only) else None
+        timed_frame0 = [o[0:1].clone() for o in outs] if (rank == 0 and args.full and not args.decoder_only) else None
         if use_dist:
             tt = torch.tensor([elapsed], dtype=torch.float64, device=device)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             elapsed = float(tt.item())
+        if rank == 0 and args.dump_outputs:
+            # before any other leg: a later eager forward writes into the same output buffers
+            arrays = dict(zip(OUTPUT_NAMES, outs))
+            if gather:                             # what the caller of the N-rank path receives: the whole batch's maps
+                arrays.update(zip(OUTPUT_NAMES, dg.maps((step_no[0] - 1) % n_slots, G)))
+            dump_outputs(arrays, args.dump_outputs)
+            log("outputs of the last timed step written to %s" % args.dump_outputs)
 
         # ---- roofline leg: HIP events around every hand-written launch, eager, on the launch stream
         roof = None
-        if rank == 0:
+        if rank == 0 and args.full:
             tr = ops.KernelTrace()
             ops.set_trace(tr)
             nrep = max(3, min(args.steps, 10))
@@ -651,7 +688,7 @@ def main():
         }
         emu = None
         emu_frame0 = None
-        if world == 1 and not args.no_emulated_leg:
+        if world == 1 and args.full and not args.no_emulated_leg:
             # Secondary measurement, NOT the headline: the same forward with every convolution in the
             # "fp32 emulated on the bf16 matrix cores" mode (bts_conv_desc.precision = 1: three-way bf16 split of both
             # operands, six products, fp32 accumulation -- results at fp32 rounding level, see its own parity gate).
@@ -694,7 +731,7 @@ def main():
                 torch.cuda.synchronize()
             finally:
                 model.conv_precision = model.decoder.conv_precision = "fp32"
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             log("cpu baseline (oracle on host cores)")
             frame0 = timed_frame0             # outs[i][0:1] of the last timed step (graph replay or eager, as timed)
             line["cpu_baseline"], par, xpar = cpu_baseline(params, H, W, gpu_frame0=frame0,

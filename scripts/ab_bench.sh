@@ -8,7 +8,7 @@ mkdir -p "$OUT"
 for spec in "$@"; do
     name=${spec%%:*}; rest=${spec#*:}; envs=${rest%%:*}; extra=${rest#*:}
     [ "$extra" == "$rest" ] && extra=""
-    ( export $envs; timeout -k 10 200 python3 "$ROOT/bench.py" --no-cpu-baseline --no-emulated-leg $extra > "$OUT/$name.json" 2> "$OUT/$name.err" ) || { echo "$name FAILED rc=$?" | tee -a "$OUT/ab.txt"; tail -3 "$OUT/$name.err"; continue; }
+    ( export $envs; timeout -k 10 200 python3 "$ROOT/bench.py" --full --no-cpu-baseline --no-emulated-leg $extra > "$OUT/$name.json" 2> "$OUT/$name.err" ) || { echo "$name FAILED rc=$?" | tee -a "$OUT/ab.txt"; tail -3 "$OUT/$name.err"; continue; }
     python3 - "$name" "$OUT/$name.json" <<'PY' | tee -a "$OUT/ab.txt"
 import json, sys
 d = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])

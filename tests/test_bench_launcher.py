@@ -116,3 +116,28 @@ def test_kernel_labels_map_to_rocprof_names():
         assert pat is not None, label
         assert [s for s in seen if re.fullmatch(pat, s)] == want, (label, pat)
     assert bench.trace_to_rocprof_name("get_depth_kernel<32>") is None
+
+
+def test_plain_run_is_lean_and_dump_outputs_is_a_fixed_bounded_sample(tmp_path):
+    """A plain run leaves the extra legs to --full.  --dump-outputs writes float32 .npy files within the byte budget:
+    small outputs whole, large ones as the same seeded sample of positions on every run."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.build_parser().parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert not a.full and a.dump_outputs is None and a.steps == 3
+    assert bench.build_parser().parse_args(["--full", "--dump-outputs", "d"]).full
+    big = torch.arange(2 * 1000 * 1500, dtype=torch.float32).reshape(2, 1, 1000, 1500)
+    small = torch.linspace(-1, 1, 40).reshape(2, 1, 4, 5)
+    budget = 2_000_000
+    for d in ("a", "b"):
+        bench.dump_outputs({"final_depth": big, "reduc1x1": small}, str(tmp_path / d), budget=budget)
+    assert sorted(os.listdir(tmp_path / "a")) == ["final_depth.npy", "reduc1x1.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= budget + 2 * 128
+    s = np.load(tmp_path / "a" / "reduc1x1.npy")
+    assert s.dtype == np.float32 and np.array_equal(s, small.numpy())
+    g1, g2 = np.load(tmp_path / "a" / "final_depth.npy"), np.load(tmp_path / "b" / "final_depth.npy")
+    assert g1.dtype == np.float32 and np.array_equal(g1, g2)
+    assert 0.9 * budget // 8 <= g1.size <= budget // 8            # one share of two, 4 bytes per element
+    assert np.all(np.diff(g1) > 0) and g1[-1] < big.numel()       # arange: the values are the (sorted, unique) positions
