@@ -203,7 +203,8 @@ inline bool conv1x1_eligible(const ConvArgs& a, bool nchw, int bn) {
     if (a.ksize != 1 || a.stride != 1 || a.pad != 0 || a.ups != 0 || a.bundled || a.subpix || nchw || a.n_tail > 0) return false;
     if (a.c_out % bn != 0) return false;
     const long tiles8 = ((long)a.fill_frames * a.H * a.W + 127) / 128 * ((a.c_out + bn - 1) / bn);      // nominal launch
-    return tiles8 >= knobs().k1x1_min_tiles;
+    constexpr long kMinTiles = 150;
+    return tiles8 >= kMinTiles;
 }
 
 template <int BN, int WM = 4, bool SB = false>

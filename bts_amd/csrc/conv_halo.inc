@@ -494,7 +494,7 @@ int launch_halo(const ConvArgs& a0, bool nchw, hipStream_t s) {
                           : (a.halo_single_a ? (size_t)(NPIX + 2 * BN) * LdsLd<MF>::value * 4 : (size_t)halo_lds_bytes<BN, MF, KS, DIL>());
     static_assert(!SB || (size_t)(2 * NPIX + BN) * LdsLd<MF>::value * 4 <= 160 * 1024, "single-weight-buffer tile must fit the LDS");
     if (SB) a.halo_single_a = 0;
-    a.stagger = (BN == 48 && WM * WN == 8 && knobs().stagger) ? 1 : 0;
+    a.stagger = (BN == 48 && WM * WN == 8) ? 1 : 0;
     hipError_t e;
     if constexpr (DIL == 1) {
         if (nchw) {

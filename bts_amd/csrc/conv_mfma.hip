@@ -31,41 +31,22 @@ namespace {
 
 constexpr int BK = 32;
 
-// Tuning / A-B knobs from the environment, read ONCE (thread-safe function-local static) into an immutable struct:
-// nothing in this file mutates state after that, whichever thread, device or stream calls in.
+// Knobs from the environment, read ONCE (thread-safe function-local static) into an immutable struct: nothing in this
+// file mutates state after that, whichever thread, device or stream calls in.
 struct ConvKnobs {
-    int split_max; long split_below; long split_target;   // BTS_CONV_SPLITK / _BELOW / _TARGET
-    long lds_bytes;                                        // BTS_CONV_LDS_KB: inflate LDS to cap workgroups per CU (0 = off)
-    int no48, force_bm;                                    // BTS_CONV_NO48, BTS_CONV_BM
-    int precision, emu_sb;                                 // BTS_CONV_PRECISION, BTS_CONV_EMU_SB (-1 = unset)
-    int w8, w8s;                                           // BTS_CONV_W8, BTS_CONV_W8S
-    int k1x1; long k1x1_min_tiles;                         // BTS_CONV_1X1 (0 off, 1 = wide-tile 1x1 kernel for c_out % 192 == 0, 2 = also 256/128 wide), BTS_CONV_1X1_MIN_TILES
-    int k1x1_sb;                                           // BTS_CONV_1X1_SB: 1 (default) = the 64-row wide tile keeps one weight buffer (three workgroups per CU), 0 = two
-    int k1x1_rows;                                         // BTS_CONV_1X1_ROWS: 0 = by K (default), 64 / 128 force the wide kernel's row tile
-    int stem;                                              // BTS_CONV_STEM: 0 = the stem on the generic row-tiled kernel (A/B), default 1
-    int tapskip;                                           // BTS_CONV_TAPSKIP: 0 = run every tap of every tile (A/B), default 1
-    int halo_sb;                                           // BTS_CONV_HALO_SB: 1 (default) = the 128- and 32-wide halo tiles (no planar tail) keep one weight buffer: two / three workgroups per CU instead of one / two
-    int halo48_w8; long halo48_w8_below;                   // BTS_CONV_HALO48_W8 (0 = never) / _BELOW: 8-wave 48-wide halo tile for declared launches below this many workgroups (default: all)
-    long halo_fill;                                        // BTS_CONV_HALO_FILL: declared-launch workgroups from which the halo kernel replaces split-K (200)
+    int precision;                                         // BTS_CONV_PRECISION: overrides bts_conv_desc.precision (-1 = unset)
     int fill_frames;                                       // BTS_CONV_FILL_FRAMES: default of bts_conv_desc.fill_frames (8)
     int wino;                                              // BTS_CONV_WINO: 1 (default) = eligible stride-1 3x3 convolutions whose caller supplies Winograd-form weights take the fused F(2x2,3x3) kernel (conv_wino.inc); 0 = direct kernels (A/B)
-    int halo_emu;                                          // BTS_CONV_HALO_EMU: 1 (default) = precision-1 launches with pre-split weights take the bf16x3 halo-tile kernel where eligible, 0 = row-tiled emulation (A/B)
+    int tapskip;                                           // BTS_CONV_TAPSKIP: 0 = run every tap of every tile (A/B), default 1
+    int k1x1;                                              // BTS_CONV_1X1: 1 (default) = wide-tile 1x1 kernel for c_out % 192 == 0 (conv_1x1.inc), 0 = row-tiled kernel
     int halo_dil;                                          // BTS_CONV_HALO_DIL: 1 (default) = the dilation-3 3x3 convolution (ASPP daspp_3) on the dilated halo tile, 2 = also dilation 6 / 12, 0 = none (row-tiled kernel with tap skipping)
-    int stagger;                                           // BTS_CONV_STAGGER: 1 (default) = the eight-wave 48-wide halo tile staggers the staging block of waves 4..7 against their SIMD partners 0..3 (A/B)
-    int halo;                                              // BTS_CONV_HALO: 0 off, 1 = halo-tile kernel where eligible unless split-K applies, 2 = also instead of split-K.  Default 1: on the deep 22x76 maps a frame has only 15 spatial tiles, so at batch 1 split-K fills the chip 7x better (53 vs 16 us per layer), and the choice may not depend on the batch (a frame's bits must not)
 };
 inline long env_long(const char* name, long dflt) { const char* v = getenv(name); return v ? atol(v) : dflt; }
 const ConvKnobs& knobs() {
-    static const ConvKnobs k = {(int)env_long("BTS_CONV_SPLITK", 8), env_long("BTS_CONV_SPLITK_BELOW", 700),
-                                env_long("BTS_CONV_SPLITK_TARGET", 1024), env_long("BTS_CONV_LDS_KB", 0) * 1024,
-                                (int)env_long("BTS_CONV_NO48", 0), (int)env_long("BTS_CONV_BM", 0),
-                                (int)env_long("BTS_CONV_PRECISION", -1), (int)env_long("BTS_CONV_EMU_SB", -1),
-                                (int)env_long("BTS_CONV_W8", 1), (int)env_long("BTS_CONV_W8S", 1),
-                                (int)env_long("BTS_CONV_1X1", 1), env_long("BTS_CONV_1X1_MIN_TILES", 150),
-                                (int)env_long("BTS_CONV_1X1_SB", 1), (int)env_long("BTS_CONV_1X1_ROWS", 0), (int)env_long("BTS_CONV_STEM", 1), (int)env_long("BTS_CONV_TAPSKIP", 1), (int)env_long("BTS_CONV_HALO_SB", 1), (int)env_long("BTS_CONV_HALO48_W8", 1), env_long("BTS_CONV_HALO48_W8_BELOW", 1L << 40), env_long("BTS_CONV_HALO_FILL", 200),
+    static const ConvKnobs k = {(int)env_long("BTS_CONV_PRECISION", -1),
                                 (int)(env_long("BTS_CONV_FILL_FRAMES", 8) > 0 ? env_long("BTS_CONV_FILL_FRAMES", 8) : 8),
-                                (int)env_long("BTS_CONV_WINO", 1), (int)env_long("BTS_CONV_HALO_EMU", 1), (int)env_long("BTS_CONV_HALO_DIL", 1), (int)env_long("BTS_CONV_STAGGER", 1),
-                                (int)env_long("BTS_CONV_HALO", 1)};
+                                (int)env_long("BTS_CONV_WINO", 1), (int)env_long("BTS_CONV_TAPSKIP", 1),
+                                (int)env_long("BTS_CONV_1X1", 1), (int)env_long("BTS_CONV_HALO_DIL", 1)};
     return k;
 }
 // floats per LDS row (32 + pad), chosen per MFMA shape so that the 16 rows a ds_read_b128 lane group touches
@@ -415,7 +396,7 @@ __device__ __forceinline__ void stage_to_lds_emu(const ConvArgs& a, char* __rest
 template <int BM, int BN, int WM, int WN, int MF, bool NCHW_OUT, int PREC = 0>
 __global__ __launch_bounds__(WM * WN * 64) void conv_fwd_kernel(const ConvArgs a0) {
     static_assert(PREC == 0 || MF == 32, "the bf16x3 emulation uses the 32x32x16 bf16 MFMA");
-    static_assert(PREC >= 0 && PREC <= 2, "PREC: 0 fp32 MFMA, 1 bf16x3, 2 bf16x3 with a single LDS buffer");
+    static_assert(PREC == 0 || PREC == 2, "PREC: 0 fp32 MFMA, 2 bf16x3 with a single LDS buffer");
     constexpr int NT = WM * WN * 64;          // threads per workgroup (4 or 8 waves)
     constexpr int RPP = NT / 8;               // tile rows staged per pass (8 lanes x 16 B per row)
     constexpr int TM = BM / WM / MF, TN = BN / WN / MF;
@@ -428,8 +409,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_fwd_kernel(const ConvArgs a
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     float* smem = reinterpret_cast<float*>(smem_raw);
     // layout: [buf][A rows BM | B rows BN][LDS_LD]
-    constexpr int BUF_FLOATS = PREC == 0 ? (BM + BN) * LDS_LD : 3 * (BM + BN) * EMU_ROW_BYTES / 4;
-    constexpr bool EMU_SB = PREC == 2;        // bf16x3 with ONE LDS buffer (half the footprint -> two workgroups per CU)
+    constexpr int BUF_FLOATS = (BM + BN) * LDS_LD;   // fp32 path: one of its two LDS buffers
 
     // XCD-aware block remap (bijective): blocks sharing an XCD (bid % 8) get a contiguous range of
     // tiles, so neighbouring pixel tiles (shared halo rows) and the N tiles of one M tile share an L2.
@@ -612,14 +592,14 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_fwd_kernel(const ConvArgs a
             if (it + 1 < nit) read_frags(smem + (buf ^ 1) * BUF_FLOATS, 0, 0);
         }
     } else {
-        // bf16x3: per k16 step every 32x32 block takes six bf16 MFMAs on the (h, m, l) planes
+        // bf16x3: per k16 step every 32x32 block takes six bf16 MFMAs on the (h, m, l) planes.  ONE LDS buffer (half the
+        // footprint -> two workgroups per CU): the next tile is staged after everyone has read the current one.
         constexpr int PLANE = (BM + BN) * EMU_ROW_BYTES;
         // fragment of k16 step ks: 8 bf16 at k = 16*ks + 8*lh -> chunk (2*ks + lh), swizzled with the row's bits 2-3
         const int a_row = (wm * TM * 32 + li) * EMU_ROW_BYTES, b_row = (BM + wn * TN * 32 + li) * EMU_ROW_BYTES;
         const int sw = (li >> 2) & 3;
         for (int it = 0; it < nit; ++it) {
-            const int buf = EMU_SB ? 0 : (it & 1);
-            const char* cur = reinterpret_cast<const char*>(smem + buf * BUF_FLOATS);
+            const char* cur = reinterpret_cast<const char*>(smem);
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
                 u32x4 fa[3][TM], fb[3][TN];
@@ -646,17 +626,11 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_fwd_kernel(const ConvArgs a
                             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, xa),
                                                                                 __builtin_bit_cast(bf16x8, xb), acc[i][j], 0, 0, 0);
                         }
-                if (!EMU_SB && ks == 0) {
-                    if (it + 1 < nit) stage(smem + (buf ^ 1) * BUF_FLOATS);
-                    if (it + 2 < nit) issue(it + 2);
-                }
             }
             __syncthreads();
-            if (EMU_SB) {                      // everyone has read the tile: overwrite it with the next one
-                if (it + 1 < nit) stage(smem);
-                if (it + 2 < nit) issue(it + 2);
-                __syncthreads();
-            }
+            if (it + 1 < nit) stage(smem);     // everyone has read the tile: overwrite it with the next one
+            if (it + 2 < nit) issue(it + 2);
+            __syncthreads();
         }
     }
 
@@ -784,10 +758,13 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const ConvArgs a, in
 // and the caller lent a workspace.  The decision is a function of the PER-FRAME geometry only (H*W, c_out) -- sized
 // for the nominal 8-frame sub-batch -- never of the batch size: an output element's summation order, hence its bits,
 // must not depend on how many frames share the launch (frames are independent, bts.py:223-293).
+// A nominal launch splits below kSplitBelow 64-row tiles, into enough splits to reach kSplitTarget of them, at most kSplitMax.
+constexpr int kSplitMax = 8;
+constexpr long kSplitBelow = 700, kSplitTarget = 1024;
 inline bool wants_split(const ConvArgs& a) {
-    if (a.n_classes != 1 || a.ws == nullptr || knobs().split_max <= 1) return false;
+    if (a.n_classes != 1 || a.ws == nullptr) return false;
     const long tiles64 = (((long)a.fill_frames * a.H * a.W + 63) / 64) * a.n_ntiles;
-    return tiles64 < knobs().split_below;
+    return tiles64 < kSplitBelow;
 }
 
 // The split factor launch_conv will use (1 = no split): the one place that decides it, so the dispatch can ask "will this
@@ -796,12 +773,32 @@ inline int split_factor(const ConvArgs& a, long ws_floats) {
     if (!wants_split(a)) return 1;
     const int nit_all = a.k_pad / BK;
     const long tiles64 = (((long)a.fill_frames * a.H * a.W + 63) / 64) * a.n_ntiles;     // 64-row tiles of a nominal launch
-    long sp = knobs().split_target / tiles64;
-    if (sp > knobs().split_max) sp = knobs().split_max;
+    long sp = kSplitTarget / tiles64;
+    if (sp > kSplitMax) sp = kSplitMax;
     if (sp > nit_all / 4) sp = nit_all / 4;
     const long ws_ld = (a.c_out + 3) & ~3;
     if (sp <= 1 || sp * a.M * ws_ld > ws_floats) return 1;
     return (int)sp;
+}
+
+// Would the layer really split K at column tile `bn`?  (split_factor, not the mere tile-count threshold: DenseNet block 3's
+// bottlenecks sit under the threshold but end up with a split factor of 1.)
+inline bool splits_k(const ConvArgs& a, int bn, long ws_floats) {
+    ConvArgs probe = a;
+    probe.n_ntiles = (a.c_out + bn - 1) / bn;
+    return split_factor(probe, ws_floats) > 1;
+}
+
+// Gate of the kernels chosen by map geometry (bf16x3 halo tile, Winograd, halo tile): they take a layer unless it would
+// really split K and its declared launch of `wgs` workgroups stays below kFillWgs.  Like the split-K decision, this depends
+// on per-frame geometry and the DECLARED frames per launch only, never on B.  Where a layer would split K, the halo kernel still wins once the declared launch brings enough spatial tiles (DenseNet
+// block 3 at fill_frames 16: 240 workgroups, 83 -> 55 us per layer at B=16).  The threshold (200) sits ABOVE the library's
+// default fill_frames of 8 (120 workgroups) on purpose: a caller that never declares anything and runs one frame per call
+// (bts_test.py) would get 15 workgroups per launch from it -- on the deep 22x76 maps split-K fills the chip 7x better there
+// (53 vs 16 us per layer; whole forward at batch 1: 8.9 ms with split-K, 12.0 ms with the halo / wide-tile choices).
+constexpr long kFillWgs = 200;
+inline bool geometry_kernel_ok(const ConvArgs& a, int bn, long ws_floats, long wgs) {
+    return !splits_k(a, bn, ws_floats) || wgs >= kFillWgs;
 }
 
 template <int BM, int BN, int WM, int WN, int MF = 32, int PREC = 0>
@@ -841,9 +838,7 @@ int launch_conv(const ConvArgs& a0, bool nchw, hipStream_t s, long ws_floats) {
         }
         return 0;
     }
-    size_t lds = PREC == 0 ? (size_t)2 * (BM + BN) * LdsLd<MF>::value * sizeof(float)
-                           : (size_t)(PREC == 2 ? 1 : 2) * 3 * (BM + BN) * EMU_ROW_BYTES;
-    if ((size_t)knobs().lds_bytes > lds && knobs().lds_bytes <= 160 * 1024) lds = (size_t)knobs().lds_bytes;
+    const size_t lds = PREC == 0 ? (size_t)2 * (BM + BN) * LdsLd<MF>::value * sizeof(float) : (size_t)3 * (BM + BN) * EMU_ROW_BYTES;
     hipError_t e;
     if (nchw) {
         auto k = conv_fwd_kernel<BM, BN, WM, WN, MF, true, PREC>;
@@ -878,7 +873,6 @@ void choose_tile(long M, int c_out, int* bm, int* bn) {
         const double cost = (double)((c_out + cand[i] - 1) / cand[i] * cand[i]) * eff[i];
         if (cost < best) { best = cost; *bn = cand[i]; }
     }
-    if (knobs().no48 && *bn == 48) *bn = 64;
     *bm = 128;
     if (*bn != 32) {
         const long nt = (c_out + *bn - 1) / *bn;
@@ -886,10 +880,6 @@ void choose_tile(long M, int c_out, int* bm, int* bn) {
         const double t128 = (double)((wg128 + 255) / 256) * 128.0;
         const double t64 = (double)((wg64 + 255) / 256) * 64.0 * 1.05;
         if (t64 < t128) *bm = 64;
-    }
-    {                                                  // tuning aid: force the row tile (64 / 128)
-        const int v = knobs().force_bm;
-        if ((v == 64 && *bn != 32) || v == 128) *bm = v;
     }
 }
 
@@ -999,117 +989,73 @@ int conv_dispatch(const bts_conv_desc* d, bts_stream_t stream) {
     if (prec == 1) {
         if (bn == 48) bn = 64;                       // the 16x16x4 48-wide tile has no bf16x3 twin: pad to 64
         // stride-1 3x3 / sub-pixel 2x2 convolutions on maps that tile well, whole 32-channel chunks, pre-split weights:
-        // the bf16x3 halo-tile kernel (conv_halo_emu.inc); same geometry-only gating as the fp32 halo kernel below
-        if (knobs().halo && knobs().halo_emu && (bn == 128 || bn == 64) && halo_emu_eligible(a, nchw)) {
-            ConvArgs probe = a;
-            probe.n_ntiles = (a.c_out + bn - 1) / bn;
-            const long halo_wgs = (long)a.fill_frames * ((a.H + 3) / 4) * ((a.W + 31) / 32) * probe.n_ntiles * a.n_classes;
-            if (knobs().halo >= 2 || split_factor(probe, wsf) <= 1 || halo_wgs >= knobs().halo_fill) {
+        // the bf16x3 halo-tile kernel (conv_halo_emu.inc)
+        if ((bn == 128 || bn == 64) && halo_emu_eligible(a, nchw)) {
+            const long halo_wgs = (long)a.fill_frames * ((a.H + 3) / 4) * ((a.W + 31) / 32) * ((a.c_out + bn - 1) / bn) * a.n_classes;
+            if (geometry_kernel_ok(a, bn, wsf, halo_wgs)) {
                 if (a.subpix) return bn == 128 ? launch_halo_emu<128, 2>(a, s) : launch_halo_emu<64, 2>(a, s);
                 return bn == 128 ? launch_halo_emu<128, 3>(a, s) : launch_halo_emu<64, 3>(a, s);
             }
         }
-        // LDS buffering: the planes take 6 B per element, and with ONE buffer per workgroup (two barriers per K-step,
-        // the other resident workgroup fills the gaps) every tile runs faster than double-buffered with fewer
-        // workgroups per CU (total over the decoder layers 134.7 vs 126.6 TFLOP/s-equivalent).  BTS_CONV_EMU_SB=0 = double.
-        // (Forcing a third workgroup per CU with an 80-VGPR cap on the narrow tiles: same layer rates, whole model
-        // 39.7 vs 38.3 ms -- dropped.)
-        const int emu_sb_env = knobs().emu_sb;
-        const int emu_sb = emu_sb_env >= 0 ? emu_sb_env : 1;
-        if (emu_sb) {                                  // one LDS buffer: half the footprint, two workgroups per CU
-            if (bn == 128) return bm == 128 ? launch_conv<128, 128, 2, 4, 32, 2>(a, nchw, s, wsf) : launch_conv<64, 128, 2, 4, 32, 2>(a, nchw, s, wsf);
-            if (bn == 64) return bm == 128 ? launch_conv<128, 64, 4, 2, 32, 2>(a, nchw, s, wsf) : launch_conv<64, 64, 2, 2, 32, 2>(a, nchw, s, wsf);
-            return launch_conv<128, 32, 4, 1, 32, 2>(a, nchw, s, wsf);
-        }
-        if (bn == 128) return bm == 128 ? launch_conv<128, 128, 2, 4, 32, 1>(a, nchw, s, wsf) : launch_conv<64, 128, 2, 4, 32, 1>(a, nchw, s, wsf);
-        if (bn == 64) return bm == 128 ? launch_conv<128, 64, 4, 2, 32, 1>(a, nchw, s, wsf) : launch_conv<64, 64, 2, 2, 32, 1>(a, nchw, s, wsf);
-        return launch_conv<128, 32, 4, 1, 32, 1>(a, nchw, s, wsf);
+        // ONE LDS buffer per workgroup: the planes take 6 B per element, and with one buffer (two barriers per K-step, the
+        // other resident workgroup fills the gaps) every tile runs faster than double-buffered with fewer workgroups per CU
+        // (total over the decoder layers 134.7 vs 126.6 TFLOP/s-equivalent).  (Forcing a third workgroup per CU with an
+        // 80-VGPR cap on the narrow tiles: same layer rates, whole model 39.7 vs 38.3 ms -- dropped.)
+        if (bn == 128) return bm == 128 ? launch_conv<128, 128, 2, 4, 32, 2>(a, nchw, s, wsf) : launch_conv<64, 128, 2, 4, 32, 2>(a, nchw, s, wsf);
+        if (bn == 64) return bm == 128 ? launch_conv<128, 64, 4, 2, 32, 2>(a, nchw, s, wsf) : launch_conv<64, 64, 2, 2, 32, 2>(a, nchw, s, wsf);
+        return launch_conv<128, 32, 4, 1, 32, 2>(a, nchw, s, wsf);
     }
     // the encoder stem (7x7 / stride 2 on the 3-channel image): its own kernel (conv_stem.inc)
-    if (knobs().stem && stem_eligible(a, nchw, prec)) return a.c_out == 96 ? launch_stem<96>(a, s) : launch_stem<64>(a, s);
-    // plain 1x1 convolutions with a wide output: one workgroup per 128 (or 64) pixels x 192 channels (conv_1x1.inc).
-    // Layers that will really split K stay on the row-tiled kernel (split_factor, not the mere tile-count threshold:
-    // DenseNet block 3's bottlenecks sit under the threshold but end up with a split factor of 1).
-    if (knobs().k1x1 && a.ksize == 1) {
-        const int wide = a.c_out % 192 == 0 ? 192 : (knobs().k1x1 == 2 ? (a.c_out % 256 == 0 ? 256 : (a.c_out % 128 == 0 ? 128 : 0)) : 0);
-        ConvArgs probe = a;
-        probe.n_ntiles = (a.c_out + bn - 1) / bn;
-        if (wide && split_factor(probe, wsf) <= 1 && conv1x1_eligible(a, nchw, wide)) {
-            if (wide == 192) {
-                // row tile by K (per-layer geometry, never the batch): a short K loop cannot amortise a 128x192 tile's
-                // prologue and 96 KB of output stores with nothing else resident on the CU -- the 64-row four-wave tile
-                // (74 KB of LDS: two workgroups per CU) overlaps them; from ~24 K-steps on the fatter tile's lower
-                // staging-per-MFMA wins (measured at B=16: block 2, K 192..720: 2.62 -> 2.33 ms with 64 rows;
-                // block 3, K 384..2064: 4.86 ms with 128 rows, 5.06 with 64)
-                const int rows = knobs().k1x1_rows ? knobs().k1x1_rows : (a.c_in_ld <= 768 ? 64 : 128);
-                if (rows == 64) return knobs().k1x1_sb ? launch_conv1x1<192, 2, true>(a, s) : launch_conv1x1<192, 2>(a, s);
-                return launch_conv1x1<192>(a, s);
-            }
-            if (wide == 256) return launch_conv1x1<256>(a, s);
-            return launch_conv1x1<128>(a, s);
-        }
+    if (stem_eligible(a, nchw, prec)) return a.c_out == 96 ? launch_stem<96>(a, s) : launch_stem<64>(a, s);
+    // plain 1x1 convolutions with a 192-multiple output: one workgroup per 128 (or 64) pixels x 192 channels (conv_1x1.inc).
+    // Layers that will really split K stay on the row-tiled kernel whatever the declared launch (conv1x1_eligible already
+    // asks for a chip-filling one).
+    if (knobs().k1x1 && a.ksize == 1 && a.c_out % 192 == 0 && !splits_k(a, bn, wsf) && conv1x1_eligible(a, nchw, 192)) {
+        // row tile by K (per-layer geometry, never the batch): a short K loop cannot amortise a 128x192 tile's prologue and
+        // 96 KB of output stores with nothing else resident on the CU -- the 64-row four-wave tile (one weight buffer, 74 KB
+        // of LDS: two workgroups per CU) overlaps them; from ~24 K-steps on the fatter tile's lower staging-per-MFMA wins
+        // (measured at B=16: block 2, K 192..720: 2.62 -> 2.33 ms with 64 rows; block 3, K 384..2064: 4.86 ms with 128 rows,
+        // 5.06 with 64)
+        return a.c_in_ld <= 768 ? launch_conv1x1<192, 2, true>(a, s) : launch_conv1x1<192>(a, s);
     }
-    // fused Winograd F(2x2,3x3) (conv_wino.inc): same geometry-only gating as the halo kernel (never instead of split-K
-    // unless the declared launch fills the chip)
+    // fused Winograd F(2x2,3x3) (conv_wino.inc); its workgroup count is taken over 128-wide channel tiles whatever bn is
     if (knobs().wino && ((bn == 128 && a.c_out_pad % 128 == 0) || (bn == 64 && a.c_out_pad % 64 == 0) || (bn == 48 && a.c_out % 48 == 0)) &&
         wino_eligible(a, nchw)) {
-        ConvArgs probe = a;
-        probe.n_ntiles = (a.c_out + bn - 1) / bn;
         const long wgs = (long)a.fill_frames * ((a.H + 7) / 8) * ((a.W + 15) / 16) * ((a.c_out + 127) / 128);
-        if (split_factor(probe, wsf) <= 1 || wgs >= knobs().halo_fill)
+        if (geometry_kernel_ok(a, bn, wsf, wgs))
             return bn == 128 ? launch_wino<128>(a, s) : (bn == 64 ? launch_wino<64>(a, s) : launch_wino<48>(a, s));
     }
     // stride-1 3x3 (and sub-pixel 2x2) convolutions on maps that tile well: the halo-tile kernel (conv_halo.inc).  The
-    // choice depends on per-frame geometry and the DECLARED frames per launch only (never on B), like the split-K
-    // decision.  Where a layer would split K, the halo kernel still wins once the declared launch brings enough spatial
-    // tiles (DenseNet block 3 at fill_frames 16: 240 workgroups, 83 -> 55 us per layer at B=16).  The threshold (200) sits
-    // ABOVE the library's default fill_frames of 8 (120 workgroups) on purpose: a caller that never declares anything and
-    // runs one frame per call (bts_test.py) would get 15 workgroups per launch from it -- split-K fills the chip 7x
-    // better there (whole forward at batch 1: 8.9 ms with split-K, 12.0 ms with the halo / wide-tile choices).
-    if (knobs().halo) {
-        ConvArgs probe = a;
-        probe.n_ntiles = (a.c_out + bn - 1) / bn;
-        const int mf = bn == 48 ? 16 : 32;
-        const long halo_wgs = (long)a.fill_frames * ((a.H + 128 / mf - 1) / (128 / mf)) * ((a.W + mf - 1) / mf) * probe.n_ntiles * a.n_classes;
-        if ((knobs().halo >= 2 || split_factor(probe, wsf) <= 1 || halo_wgs >= knobs().halo_fill) && halo_eligible(a, true, mf, nullptr)) {
-            if (a.subpix) {
-                if (bn == 128) return knobs().halo_sb ? launch_halo<128, 4, 2, 32, 2, false, true>(a, nchw, s) : launch_halo<128, 4, 2, 32, 2>(a, nchw, s);
-                if (bn == 64) return launch_halo<64, 4, 2, 32, 2>(a, nchw, s);
-                if (bn == 32) return knobs().halo_sb ? launch_halo<32, 4, 1, 32, 2, false, true>(a, nchw, s) : launch_halo<32, 4, 1, 32, 2>(a, nchw, s);
-            } else if (a.dil != 1) {
-                // dilated halo tiles (ASPP branches, c_out 128): one eight-wave workgroup per CU, single weight buffer
-                if (bn == 128 && !nchw) {
-                    if (a.dil == 3) return launch_halo<128, 4, 2, 32, 3, false, true, 3>(a, nchw, s);
-                    if (a.dil == 6) return launch_halo<128, 4, 2, 32, 3, false, true, 6>(a, nchw, s);
-                    if (a.dil == 12) return launch_halo<128, 4, 2, 32, 3, false, true, 12>(a, nchw, s);
-                }
-            } else {
-                if (bn == 128) return knobs().halo_sb ? launch_halo<128, 4, 2, 32, 3, false, true>(a, nchw, s) : launch_halo<128, 4, 2, 32, 3>(a, nchw, s);
-                if (bn == 64) return launch_halo<64, 4, 2, 32, 3>(a, nchw, s);
-                if (bn == 32) return knobs().halo_sb ? launch_halo<32, 4, 1, 32, 3, false, true>(a, nchw, s) : launch_halo<32, 4, 1, 32, 3>(a, nchw, s);
-                if (bn == 48) {
-                    // eight waves per workgroup (one 16-pixel row each) instead of four: 16 instead of 8 waves per CU at two
-                    // workgroups per CU.  Worth -10 % where the launch is under-filled (DenseNet block 3: 240 workgroups at
-                    // fill_frames 16) and -2 % on the chip-filling block 1 / 2 launches; BTS_CONV_HALO48_W8_BELOW restricts it
-                    // to declared launches below that many workgroups (A/B)
-                    if (knobs().halo48_w8 && halo_wgs < knobs().halo48_w8_below) return launch_halo<48, 8, 1, 16, 3>(a, nchw, s);
-                    return launch_halo<48, 4, 1, 16, 3>(a, nchw, s);
-                }
+    // 128- and 32-wide tiles keep one weight buffer: two / three workgroups per CU instead of one / two.
+    const int mf = bn == 48 ? 16 : 32;
+    const long halo_wgs = (long)a.fill_frames * ((a.H + 128 / mf - 1) / (128 / mf)) * ((a.W + mf - 1) / mf) * ((a.c_out + bn - 1) / bn) * a.n_classes;
+    if (geometry_kernel_ok(a, bn, wsf, halo_wgs) && halo_eligible(a, true, mf, nullptr)) {
+        if (a.subpix) {
+            if (bn == 128) return launch_halo<128, 4, 2, 32, 2, false, true>(a, nchw, s);
+            if (bn == 64) return launch_halo<64, 4, 2, 32, 2>(a, nchw, s);
+            if (bn == 32) return launch_halo<32, 4, 1, 32, 2, false, true>(a, nchw, s);
+        } else if (a.dil != 1) {
+            // dilated halo tiles (ASPP branches, c_out 128): one eight-wave workgroup per CU, single weight buffer
+            if (bn == 128 && !nchw) {
+                if (a.dil == 3) return launch_halo<128, 4, 2, 32, 3, false, true, 3>(a, nchw, s);
+                if (a.dil == 6) return launch_halo<128, 4, 2, 32, 3, false, true, 6>(a, nchw, s);
+                if (a.dil == 12) return launch_halo<128, 4, 2, 32, 3, false, true, 12>(a, nchw, s);
             }
+        } else {
+            if (bn == 128) return launch_halo<128, 4, 2, 32, 3, false, true>(a, nchw, s);
+            if (bn == 64) return launch_halo<64, 4, 2, 32, 3>(a, nchw, s);
+            if (bn == 32) return launch_halo<32, 4, 1, 32, 3, false, true>(a, nchw, s);
+            // eight waves per workgroup (one 16-pixel row each): 16 instead of 8 waves per CU at two workgroups per CU.  Worth
+            // -10 % over four where the launch is under-filled (DenseNet block 3: 240 workgroups at fill_frames 16) and -2 %
+            // on the chip-filling block 1 / 2 launches
+            if (bn == 48) return launch_halo<48, 8, 1, 16, 3>(a, nchw, s);
         }
     }
     if (bn == 48) return bm == 128 ? launch_conv<128, 48, 4, 1, 16>(a, nchw, s, wsf) : launch_conv<64, 48, 4, 1, 16>(a, nchw, s, wsf);
-    // 8-wave workgroups (two waves per SIMD from the same tile) for the 128-row tiles: +2 % end to end over the
-    // 4-wave layout on MI355X (more waves to cover each other's staging); BTS_CONV_W8=0 selects the 4-wave kernels
-    const int w8 = knobs().w8, w8s = knobs().w8s;
-    if (bn == 128) {
-        if (bm == 128) return w8 ? launch_conv<128, 128, 2, 4>(a, nchw, s, wsf) : launch_conv<128, 128, 2, 2>(a, nchw, s, wsf);
-        return w8s ? launch_conv<64, 128, 2, 4>(a, nchw, s, wsf) : launch_conv<64, 128, 2, 2>(a, nchw, s, wsf);
-    }
-    if (bn == 64) {
-        if (bm == 128) return w8 ? launch_conv<128, 64, 4, 2>(a, nchw, s, wsf) : launch_conv<128, 64, 2, 2>(a, nchw, s, wsf);
-        return launch_conv<64, 64, 2, 2>(a, nchw, s, wsf);
-    }
+    // 8-wave workgroups (two waves per SIMD from the same tile) for the 128-row tiles and the 64x128 tile: +2 % end to end
+    // over the 4-wave layout on MI355X (more waves to cover each other's staging)
+    if (bn == 128) return bm == 128 ? launch_conv<128, 128, 2, 4>(a, nchw, s, wsf) : launch_conv<64, 128, 2, 4>(a, nchw, s, wsf);
+    if (bn == 64) return bm == 128 ? launch_conv<128, 64, 4, 2>(a, nchw, s, wsf) : launch_conv<64, 64, 2, 2>(a, nchw, s, wsf);
     return launch_conv<128, 32, 4, 1>(a, nchw, s, wsf);
 }
 

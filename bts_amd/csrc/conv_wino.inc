@@ -433,7 +433,7 @@ inline bool wino_eligible(const ConvArgs& a, bool nchw) {
     const long ntx = (a.W + 15) / 16, nty = (a.H + 7) / 8;
     // break-even against the direct kernels is a tile-grid fill of ~0.65 (Winograd runs 1.5-1.7x their rate on the pixels it
     // computes); 0.70 keeps a margin.  The NYU decoder's 52x68 maps (0.79) are in, 26x34 (0.58) and 11x38 (0.54) stay out.
-    static const double min_fill = getenv("BTS_CONV_WINO_FILL") ? atof(getenv("BTS_CONV_WINO_FILL")) : 0.70;      // read once (A/B)
+    constexpr double min_fill = 0.70;
     return (double)a.H * a.W / (double)(ntx * 16 * nty * 8) >= min_fill;
 }
 

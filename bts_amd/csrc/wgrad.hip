@@ -12,7 +12,6 @@
 // (128x128 / 64x128 / 32x128 / 64x64) and the split together.
 #include "common.h"
 #include <stdint.h>
-#include <stdlib.h>
 
 namespace {
 
@@ -251,8 +250,7 @@ struct WgradPlan { int variant; long split; };
 inline WgradPlan plan_wgrad(int c_out, int N, long M, long ws_floats, bool have_ws, int n_bundles) {
     static const int bm[4] = {128, 64, 32, 64}, bn[4] = {128, 128, 128, 64};
     static const double eff[4] = {1.0, 0.9, 0.75, 0.8};
-    static const long target = getenv("BTS_WGRAD_TARGET") ? atol(getenv("BTS_WGRAD_TARGET")) : 768;   // immutable once read
-    static const int force_variant = getenv("BTS_WGRAD_VARIANT") ? (atoi(getenv("BTS_WGRAD_VARIANT")) & 3) : -1;
+    constexpr long target = 768;                                       // workgroups a split aims for (see above)
     const long per = (long)c_out * N * n_bundles;
     long max_split = M / (4 * WBK);
     if (max_split > 1024) max_split = 1024;
@@ -274,7 +272,6 @@ inline WgradPlan plan_wgrad(int c_out, int N, long M, long ws_floats, bool have_
         const double score = useful * eff[v] * fill * in_bytes / (in_bytes + partial_bytes);
         if (score > best_score * 1.0001) { best_score = score; best = {v, split}; }
     }
-    if (force_variant >= 0) best.variant = force_variant;
     return best;
 }
 

@@ -16,8 +16,8 @@
  *  - re-entrant per (device, stream): every entry point works on the calling thread's current device and the given
  *    stream.  The library keeps no mutable state between calls except one idempotent, lock-free cache: "the
  *    dynamic-LDS limit of kernel K has been raised on device D" (a bit per device ordinal; the attribute is per
- *    device, so a process driving several GPUs -- nn.DataParallel, bts_test.py:91 -- gets it set on each).  Tuning
- *    knobs (BTS_CONV_*, BTS_WGRAD_* environment variables) are read once into immutable values.
+ *    device, so a process driving several GPUs -- nn.DataParallel, bts_test.py:91 -- gets it set on each).  The
+ *    BTS_CONV_* environment knobs (conv_mfma.hip, ConvKnobs) are read once into immutable values.
  */
 #ifndef BTS_HIP_H_
 #define BTS_HIP_H_

@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """Per-layer microbenchmark of the fp32-MFMA conv kernel on the decoder's (and encoder's) GEMM shapes.
-    python scripts/conv_bench.py [--batch 16] [--reps 5]
-Env BTS_CONV_BM=64|128 forces the row tile (A/B of the tile heuristic)."""
+    python scripts/conv_bench.py [--batch 16] [--reps 5]"""
 import argparse
 import os
 import sys
