@@ -441,6 +441,8 @@ class bts(nn.Module):
         if focal is not None and self.params.dataset == 'kitti' and focal.numel() != B:
             raise BtsHipError("bts.forward: focal must have one entry per frame (%d), got %d" % (B, focal.numel()))
         if self.training:
+            if torch.is_grad_enabled():
+                train.refuse_bf16("bts.forward (train mode)")
             return train.decoder_forward(self, features, focal.to(dense.device) if isinstance(focal, torch.Tensor) else focal)
         ws = self._workspace(B, H, W, dense.device)
         # boundary: NCHW encoder taps -> NHWC channel slices (dense_features = ReLU(features[5]), bts.py:225)
@@ -602,7 +604,8 @@ class BtsModel(nn.Module):
                                             # None = by the batch of each call, in three classes (ops.auto_fill_frames:
                                             # B <= 2 -> 2, the latency setting of bts_test.py's B=1 loop; B <= 11 -> 8;
                                             # else 16); an int pins it, and a frame's bits then never depend on the batch
-        self.conv_precision = "fp32"        # "fp32": fp32-input MFMA; "bf16x3": fp32 emulated on the bf16 matrix cores
+        self.conv_precision = "fp32"        # "fp32": fp32-input MFMA; "bf16x3": fp32 emulated on the bf16 matrix cores;
+                                            # "bf16": bf16 operands, fp32 accumulation (inference only)
         self.output_buffers = None          # optional: up to six preallocated contiguous result tensors ([B,1,H,W] x 5,
                                             # [B,32,H,W]); entries given (not None) receive the results of the native eval
                                             # forward IN PLACE instead of fresh tensors -- e.g. views of a persistent
@@ -688,6 +691,8 @@ class BtsModel(nn.Module):
         return self._forward(x, focal)
 
     def _forward(self, x, focal):
+        if self.training and torch.is_grad_enabled():
+            train.refuse_bf16("BtsModel.forward (train mode)")
         if self.training and self.native_encoder and isinstance(x, torch.Tensor) and x.is_cuda:
             # training step: encoder + decoder as one autograd graph on the HIP kernels (bts_amd/train.py)
             enc_fwd = train.resnet_encoder_forward if isinstance(self.encoder.base_model, encoders.ResNet) \

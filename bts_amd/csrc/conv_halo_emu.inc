@@ -32,11 +32,15 @@
 // 16 whatever uniform shift the tap adds (base + {0-3, 12-15, 20-27}), so (pixel & 3, chunk ^ (pixel >> 2 & 3)) -- the
 // 16-byte bank slot -- is distinct too: conflict-free for every tap.  The swizzle makes a tap's address non-additive, so
 // the KS*KS x 2 fragment addresses of a lane are computed once, before the loop (they do not depend on the chunk).
+//
+// NP = 1 is the bf16 mode (bts_conv_desc.precision = 2): the same tile with ONE plane -- the patch rounded to nearest even
+// on its way to LDS (rne_store), the weights pre-rounded offline (ops.round_bf16, [class][1][c_out_pad][k_pad]) -- and one
+// v_mfma_f32_32x32x16_bf16 per 16 k of a 32x32 block instead of six.  A third of the LDS and of the weight DMA.
 __device__ __forceinline__ int emu_a_off(int pix, int chunk16) { return pix * EMU_ROW_BYTES + (((chunk16 ^ (pix >> 2)) & 3) << 4); }
 
-template <int BN, int KS>
+template <int BN, int KS, int NP>
 constexpr int halo_emu_lds_bytes() {
-    return 2 * 3 * ((4 + KS - 1) * (32 + KS - 1)) * EMU_ROW_BYTES + 3 * 3 * BN * EMU_ROW_BYTES;
+    return 2 * NP * ((4 + KS - 1) * (32 + KS - 1)) * EMU_ROW_BYTES + 3 * NP * BN * EMU_ROW_BYTES;
 }
 
 // global_load_dwordx4 whose result the compiler does not track: beside LDS-DMA traffic hipcc waits vmcnt(0) at the first
@@ -49,23 +53,24 @@ template <int N> __device__ __forceinline__ void wait_vm(f32x4& v0, f32x4& v1, f
     asm volatile("s_waitcnt vmcnt(%3)" : "+v"(v0), "+v"(v1), "+v"(v2) : "n"(N) : "memory");
 }
 
-template <int BN, int KS>
+template <int BN, int KS, int NP>
 __global__ __launch_bounds__(512, 2) void conv_halo_emu_kernel(const ConvArgs a) {
+    static_assert(NP == 3 || NP == 1, "NP: 3 bf16x3 planes (precision 1) or one bf16 plane (precision 2)");
     constexpr int MF = 32, TM = 2, TN = BN / 2 / MF;      // consumer wave tile: 2 patch rows (64 pixels) x BN/2 channels
     constexpr int TW = 32, TH = 4, PH = TH + KS - 1, PW = TW + KS - 1, NPIX = PH * PW, T = KS * KS;
     constexpr int RPP = 256 / 8;                         // patch pixels staged per pass by the 256 producer threads
     constexpr int PA = (NPIX + RPP - 1) / RPP;           // passes over the patch: 7 (3x3), 6 (2x2)
     constexpr int PPS = (PA + T - 2) / (T - 1);          // passes per tap-step: 1 (3x3), 2 (2x2)
-    constexpr int A_PLANE = NPIX * EMU_ROW_BYTES, A_BUF = 3 * A_PLANE;
-    constexpr int B_PLANE = BN * EMU_ROW_BYTES, B_STAGE = 3 * B_PLANE;
-    constexpr int NI = 3 * BN / 16;                      // DMA wave-instructions per weight stage (16 rows x 64 B each)
-    constexpr int NIW = NI / 4;                          // ... per producer wave: 6 (BN 128), 3 (BN 64)
+    constexpr int A_PLANE = NPIX * EMU_ROW_BYTES, A_BUF = NP * A_PLANE;
+    constexpr int B_PLANE = BN * EMU_ROW_BYTES, B_STAGE = NP * B_PLANE;
+    constexpr int NI = NP * BN / 16;                     // DMA wave-instructions per weight stage (16 rows x 64 B each)
+    constexpr int NIW = NI / 4;                          // ... per producer wave: 6 / 3 (BN 128 / 64, NP 3), 2 / 1 (NP 1)
     static_assert(NI % 4 == 0 && PPS * (T - 1) >= PA, "producer work divides evenly");
     static_assert(A_PLANE % 16 == 0 && TN >= 1, "layout");
     typedef float acc_t __attribute__((ext_vector_type(16)));
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    char* const As = smem_raw;                            // [2][3 planes][NPIX][64 B]
-    char* const Bs = smem_raw + 2 * A_BUF;                // [3 stages][3 planes][BN][64 B]
+    char* const As = smem_raw;                            // [2][NP planes][NPIX][64 B]
+    char* const Bs = smem_raw + 2 * A_BUF;                // [3 stages][NP planes][BN][64 B]
 
     // ---- tile decode (as conv_halo_kernel)
     const int nwg = gridDim.x, bid = blockIdx.x;
@@ -124,11 +129,11 @@ __global__ __launch_bounds__(512, 2) void conv_halo_emu_kernel(const ConvArgs a)
             if (a.pre_relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
             const bool ok = (inimg >> p) & 1u;                               // zero padding AFTER the prologue
             v.x = ok ? v.x : 0.f; v.y = ok ? v.y : 0.f; v.z = ok ? v.z : 0.f; v.w = ok ? v.w : 0.f;
-            split_store(dstbuf, A_PLANE, awr[p], v);
+            plane_store<NP>(dstbuf, A_PLANE, awr[p], v);
         };
         // weight DMA: producer wave pw sends wave-instructions q = pw + 4u: rows [16 rb, 16 rb + 16) of plane q / (BN/16)
         const int pw = wv - 4;
-        const unsigned short* const wq = reinterpret_cast<const unsigned short*>(a.w_split) + (size_t)cls * 3 * a.c_out_pad * a.k_pad;
+        const unsigned short* const wq = reinterpret_cast<const unsigned short*>(a.w_split) + (size_t)cls * NP * a.c_out_pad * a.k_pad;
         unsigned wsrc[NIW];                               // per-lane source element offset (without the step's k offset)
         int wdst[NIW];                                    // wave-uniform LDS byte offset inside a stage
 #pragma unroll
@@ -250,20 +255,21 @@ __global__ __launch_bounds__(512, 2) void conv_halo_emu_kernel(const ConvArgs a)
     __builtin_amdgcn_s_barrier();                                    // the producers' prologue
     asm volatile("" ::: "memory");
 
-    constexpr int PA_[6] = {0, 0, 1, 0, 2, 1}, PB_[6] = {0, 1, 0, 2, 0, 1};      // hh, hm, mh, hl, lh, mm
-    u32x4 fa0[3][TM], fb0[3][TN], fa1[3][TM], fb1[3][TN];
-    auto read_frags = [&](const char* A, const char* B, const int (&aoff)[TM][2], int ks, int boff, u32x4 (&fa)[3][TM], u32x4 (&fb)[3][TN]) {
+    constexpr int PA_[6] = {0, 0, 1, 0, 2, 1}, PB_[6] = {0, 1, 0, 2, 0, 1};      // hh, hm, mh, hl, lh, mm (NP 1: the first)
+    constexpr int NQ = NP == 3 ? 6 : 1;                                            // products per k16 block
+    u32x4 fa0[NP][TM], fb0[NP][TN], fa1[NP][TM], fb1[NP][TN];
+    auto read_frags = [&](const char* A, const char* B, const int (&aoff)[TM][2], int ks, int boff, u32x4 (&fa)[NP][TM], u32x4 (&fb)[NP][TN]) {
 #pragma unroll
-        for (int pl = 0; pl < 3; ++pl) {
+        for (int pl = 0; pl < NP; ++pl) {
 #pragma unroll
             for (int i = 0; i < TM; ++i) fa[pl][i] = *reinterpret_cast<const u32x4*>(A + pl * A_PLANE + aoff[i][ks]);
 #pragma unroll
             for (int j = 0; j < TN; ++j) fb[pl][j] = *reinterpret_cast<const u32x4*>(B + pl * B_PLANE + j * 32 * EMU_ROW_BYTES + boff);
         }
     };
-    auto mfmas = [&](const u32x4 (&fa)[3][TM], const u32x4 (&fb)[3][TN]) {
+    auto mfmas = [&](const u32x4 (&fa)[NP][TM], const u32x4 (&fb)[NP][TN]) {
 #pragma unroll
-        for (int q = 0; q < 6; ++q)
+        for (int q = 0; q < NQ; ++q)
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -340,14 +346,14 @@ __global__ __launch_bounds__(512, 2) void conv_halo_emu_kernel(const ConvArgs a)
 }
 
 // Eligibility on top of halo_eligible(): whole 32-channel chunks (the weight DMA moves whole 64-byte rows), pre-split
-// weights supplied, plain NHWC output, no planar tail, dilation 1.
+// (precision 1) or pre-rounded (precision 2) weights supplied, plain NHWC output, no planar tail, dilation 1.
 inline bool halo_emu_eligible(const ConvArgs& a, bool nchw) {
     if (a.w_split == nullptr || nchw || a.n_tail > 0 || a.dil != 1 || (a.c_in_ld % BK) != 0) return false;
     if (((uintptr_t)a.w_split & 15) || (a.k_pad & 7)) return false;
     return halo_eligible(a, true, 32, nullptr);
 }
 
-template <int BN, int KS>
+template <int BN, int KS, int NP = 3>
 int launch_halo_emu(const ConvArgs& a0, hipStream_t s) {
     ConvArgs a = a0;
     constexpr int TW = 32, TH = 4;
@@ -357,10 +363,10 @@ int launch_halo_emu(const ConvArgs& a0, hipStream_t s) {
     a.ksplit = 1;
     const long nwg = n_mtiles * a.n_ntiles * a.n_classes;
     if (nwg > 0x7fffffffL) return BTS_ERR_INVALID;
-    if (g_dry) { *g_dry = ConvChoice{5, 128, BN, 1}; return 0; }
-    constexpr size_t lds = (size_t)halo_emu_lds_bytes<BN, KS>();
+    if (g_dry) { *g_dry = ConvChoice{NP == 3 ? 5 : 8, 128, BN, 1}; return 0; }
+    constexpr size_t lds = (size_t)halo_emu_lds_bytes<BN, KS, NP>();
     static_assert(lds <= 160 * 1024, "LDS");
-    auto k = conv_halo_emu_kernel<BN, KS>;
+    auto k = conv_halo_emu_kernel<BN, KS, NP>;
     static std::atomic<unsigned long long> lds_set{0};
     if (hipError_t e = bts_ensure_dynamic_lds((const void*)k, lds, lds_set); e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(k, dim3((unsigned)nwg), dim3(512), lds, s, a);

@@ -87,7 +87,9 @@ struct ConvArgs {
     int halo_single_a;                       // halo-tile kernel: one channel chunk, one A buffer (set by launch_halo)
     int tapskip;                             // 1: a tile skips the taps that fall outside the map for ALL of its pixels (tile_tapmask)
     const float* w_wino;                     // Winograd-form weights (bts_conv_desc.w_wino) or null
-    const void* w_split;                     // precision 1: weights pre-split into bf16 planes [classes][3][c_out_pad][k_pad] (bts_conv_desc.w_split) or null
+    const void* w_split;                     // bts_conv_desc.w_split when the descriptor's own precision runs, else null: precision 1 =
+                                             // weights pre-split into bf16 planes [classes][3][c_out_pad][k_pad], precision 2 = one
+                                             // RNE plane [classes][1][c_out_pad][k_pad]
     int stagger;                             // halo-tile kernel, eight-wave 48-wide tile: waves 4..7 stage half a step after their SIMD partners 0..3 (set by launch_halo)
 };
 
@@ -366,9 +368,29 @@ __device__ __forceinline__ void split_store(char* plane0, int plane_bytes, int b
     *reinterpret_cast<u32x2*>(plane0 + 2 * plane_bytes + byte_off) = pl;
 }
 
-// same role as stage_to_lds: prologue + zero padding, then the split into the three bf16 planes of one LDS buffer
+// ---- bf16 operands (bts_conv_desc.precision = 2) ------------------------------------------------------------------------
+// One plane: each fp32 operand is rounded to the nearest bf16 (ties to even) on its way to LDS -- a plain conversion, which
+// hipcc emits as v_cvt_pk_bf16_f32 (two values per instruction) -- and a 32x32 block takes ONE v_mfma_f32_32x32x16_bf16 per
+// 16 k.  Products of bf16 pairs are exact in fp32 and accumulate in fp32; the only departure from the fp32 path is the
+// rounding of the operands themselves (2^-9 relative).  Same 64-byte swizzled rows as the emulated planes (emu_off).
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ unsigned pack_bf16_rne(float lo, float hi) {      // low half = lo
+    return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{lo, hi}, bf16x2));
+}
+__device__ __forceinline__ void rne_store(char* plane, int byte_off, const f32x4 v) {
+    *reinterpret_cast<u32x2*>(plane + byte_off) = u32x2{pack_bf16_rne(v.x, v.y), pack_bf16_rne(v.z, v.w)};
+}
+// NP = 3: split_store into the three planes of the emulated mode; NP = 1: rne_store into the one plane of the bf16 mode
+template <int NP>
+__device__ __forceinline__ void plane_store(char* plane0, int plane_bytes, int byte_off, const f32x4 v) {
+    if constexpr (NP == 3) split_store(plane0, plane_bytes, byte_off, v);
+    else rne_store(plane0, byte_off, v);
+}
+
+// same role as stage_to_lds: prologue + zero padding, then the conversion into the NP bf16 planes of one LDS buffer
 // (layout [plane][A rows BM | B rows BN][EMU_ROW_BYTES])
-template <int BM, int BN, int RPP, int PA, int PB>
+template <int BM, int BN, int RPP, int PA, int PB, int NP>
 __device__ __forceinline__ void stage_to_lds_emu(const ConvArgs& a, char* __restrict__ buf, int lrow, int lk,
                                                  const f32x4 (&ra)[PA], const f32x4 (&rb)[PB], const f32x4& ps,
                                                  const f32x4& pb, unsigned okmask) {
@@ -383,20 +405,22 @@ __device__ __forceinline__ void stage_to_lds_emu(const ConvArgs& a, char* __rest
         }
         const bool ok = (okmask >> p) & 1u;
         v.x = ok ? v.x : 0.f; v.y = ok ? v.y : 0.f; v.z = ok ? v.z : 0.f; v.w = ok ? v.w : 0.f;
-        split_store(buf, PLANE, emu_off(p * RPP + lrow, lk), v);
+        plane_store<NP>(buf, PLANE, emu_off(p * RPP + lrow, lk), v);
     }
 #pragma unroll
     for (int p = 0; p < PB; ++p)
         if ((p + 1) * RPP <= BN || p * RPP + lrow < BN)
-            split_store(buf, PLANE, emu_off(BM + p * RPP + lrow, lk), rb[p]);
+            plane_store<NP>(buf, PLANE, emu_off(BM + p * RPP + lrow, lk), rb[p]);
 }
 
 // MF = 32: v_mfma_f32_32x32x2_f32 tiles (default).  MF = 16: v_mfma_f32_16x16x4_f32 tiles, same FLOP rate
 // but 16-column granularity -- used for c_out = 48 (DenseNet growth) where a 64-wide tile wastes 25 %.
+// PREC (the kernel's arithmetic, not the descriptor's code): 0 fp32 MFMA; 2 bf16x3 (descriptor precision 1) with a single
+// LDS buffer; 3 bf16 operands rounded to nearest even (descriptor precision 2), one plane, two LDS buffers.
 template <int BM, int BN, int WM, int WN, int MF, bool NCHW_OUT, int PREC = 0>
 __global__ __launch_bounds__(WM * WN * 64) void conv_fwd_kernel(const ConvArgs a0) {
-    static_assert(PREC == 0 || MF == 32, "the bf16x3 emulation uses the 32x32x16 bf16 MFMA");
-    static_assert(PREC == 0 || PREC == 2, "PREC: 0 fp32 MFMA, 2 bf16x3 with a single LDS buffer");
+    static_assert(PREC == 0 || MF == 32, "the bf16 modes use the 32x32x16 bf16 MFMA");
+    static_assert(PREC == 0 || PREC == 2 || PREC == 3, "PREC: 0 fp32 MFMA, 2 bf16x3 with a single LDS buffer, 3 bf16 RNE");
     constexpr int NT = WM * WN * 64;          // threads per workgroup (4 or 8 waves)
     constexpr int RPP = NT / 8;               // tile rows staged per pass (8 lanes x 16 B per row)
     constexpr int TM = BM / WM / MF, TN = BN / WN / MF;
@@ -540,7 +564,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_fwd_kernel(const ConvArgs a
     };
     auto stage = [&](float* dst) __attribute__((always_inline)) {
         if constexpr (PREC == 0) stage_to_lds<BM, BN, RPP, PA, PB, LDS_LD>(a, dst, lrow, lk, ra, rb, ps, pb, okmask);
-        else stage_to_lds_emu<BM, BN, RPP, PA, PB>(a, reinterpret_cast<char*>(dst), lrow, lk, ra, rb, ps, pb, okmask);
+        else stage_to_lds_emu<BM, BN, RPP, PA, PB, PREC == 3 ? 1 : 3>(a, reinterpret_cast<char*>(dst), lrow, lk, ra, rb, ps, pb, okmask);
     };
     issue(0);
     stage(smem);
@@ -590,6 +614,41 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_fwd_kernel(const ConvArgs a
             }
             __syncthreads();
             if (it + 1 < nit) read_frags(smem + (buf ^ 1) * BUF_FLOATS, 0, 0);
+        }
+    } else if constexpr (PREC == 3) {
+        // bf16: one plane, 2 B per element, so the tile is double-buffered like the fp32 path: the next tile is staged into
+        // the other buffer between the two k16 blocks of the current one, and one barrier ends the step
+        constexpr int BUF = (BM + BN) * EMU_ROW_BYTES;
+        const int a_row = (wm * TM * 32 + li) * EMU_ROW_BYTES, b_row = (BM + wn * TN * 32 + li) * EMU_ROW_BYTES;
+        const int sw = (li >> 2) & 3;
+        auto read_frags = [&](const char* cur, int ks, u32x4 (&fa)[TM], u32x4 (&fb)[TN]) {
+#pragma unroll
+            for (int i = 0; i < TM; ++i) fa[i] = *reinterpret_cast<const u32x4*>(cur + a_row + i * 32 * EMU_ROW_BYTES + (((2 * ks + lh) ^ sw) << 4));
+#pragma unroll
+            for (int j = 0; j < TN; ++j) fb[j] = *reinterpret_cast<const u32x4*>(cur + b_row + j * 32 * EMU_ROW_BYTES + (((2 * ks + lh) ^ sw) << 4));
+        };
+        auto mfmas = [&](const u32x4 (&fa)[TM], const u32x4 (&fb)[TN]) {
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int j = 0; j < TN; ++j) {
+                    const u32x4 xa = NCHW_OUT ? fb[j] : fa[i];
+                    const u32x4 xb = NCHW_OUT ? fa[i] : fb[j];
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, xa), __builtin_bit_cast(bf16x8, xb),
+                                                                        acc[i][j], 0, 0, 0);
+                }
+        };
+        for (int it = 0; it < nit; ++it) {
+            const int buf = it & 1;
+            const char* cur = smem_raw + buf * BUF;
+            u32x4 fa0[TM], fb0[TN], fa1[TM], fb1[TN];
+            read_frags(cur, 0, fa0, fb0);
+            read_frags(cur, 1, fa1, fb1);
+            mfmas(fa0, fb0);
+            if (it + 1 < nit) stage(reinterpret_cast<float*>(smem_raw + (buf ^ 1) * BUF));   // read last in step it-1
+            if (it + 2 < nit) issue(it + 2);
+            mfmas(fa1, fb1);
+            __syncthreads();
         }
     } else {
         // bf16x3: per k16 step every 32x32 block takes six bf16 MFMAs on the (h, m, l) planes.  ONE LDS buffer (half the
@@ -823,7 +882,7 @@ int launch_conv(const ConvArgs& a0, bool nchw, hipStream_t s, long ws_floats) {
     const bool lean = (a.c_in_ld % BK) == 0 && a.ups == 0;
     a.tapskip = (knobs().tapskip && lean && a.ksplit == 1 && a.stride == 1 && a.ksize > 1 && a.ksize * a.ksize <= 49) ? 1 : 0;
     if (g_dry) {
-        *g_dry = ConvChoice{0, BM, BN, a.ksplit};
+        *g_dry = ConvChoice{PREC == 3 ? 7 : 0, BM, BN, a.ksplit};
         const long taps = (long)a.ksize * a.ksize;
         g_dry->ksteps_dense = n_mtiles * a.n_classes * taps;
         g_dry->ksteps_issued = g_dry->ksteps_dense;
@@ -838,7 +897,8 @@ int launch_conv(const ConvArgs& a0, bool nchw, hipStream_t s, long ws_floats) {
         }
         return 0;
     }
-    const size_t lds = PREC == 0 ? (size_t)2 * (BM + BN) * LdsLd<MF>::value * sizeof(float) : (size_t)3 * (BM + BN) * EMU_ROW_BYTES;
+    const size_t lds = PREC == 0 ? (size_t)2 * (BM + BN) * LdsLd<MF>::value * sizeof(float)
+                                 : (size_t)(PREC == 3 ? 2 : 3) * (BM + BN) * EMU_ROW_BYTES;     // bf16: two buffers of one plane
     hipError_t e;
     if (nchw) {
         auto k = conv_fwd_kernel<BM, BN, WM, WN, MF, true, PREC>;
@@ -974,10 +1034,15 @@ int conv_dispatch(const bts_conv_desc* d, bts_stream_t stream) {
     int bm, bn;
     choose_tile(a.M * a.n_classes, d->c_out, &bm, &bn);
     // precision: 0 = v_mfma_f32_32x32x2_f32 (exact fp32 products), 1 = fp32 emulated on the bf16 matrix cores
-    // (three-way split, six products; see split_store).  BTS_CONV_PRECISION overrides the descriptor (A/B runs).
+    // (three-way split, six products; see split_store), 2 = bf16 operands rounded to nearest even, one product (rne_store).
+    // BTS_CONV_PRECISION (0 / 1) overrides the descriptor (A/B runs).
     const int prec_env = knobs().precision;
     const int prec = prec_env >= 0 ? prec_env : d->precision;
-    if (prec != 0 && prec != 1) return BTS_ERR_INVALID;
+    if (prec != 0 && prec != 1 && prec != 2) return BTS_ERR_INVALID;
+    if (prec_env >= 0 && prec_env != 0 && prec_env != 1) return BTS_ERR_INVALID;
+    // w_split's layout is the DESCRIPTOR's precision (three planes for 1, one for 2): when BTS_CONV_PRECISION overrides it,
+    // the buffer does not describe the arithmetic that runs -- the kernels then work from the fp32 `w` alone
+    if (prec != d->precision) a.w_split = nullptr;
     // fused Winograd F(2x2,3x3) (conv_wino.inc), planar-tail layers included (conv3 / conv2: NHWC output)
     if (a.n_tail > 0 && prec == 0 && knobs().wino && (bn == 128 || bn == 64) && a.c_out_pad % (bn == 128 ? 128 : 64) == 0 && wino_eligible(a, nchw))
         return bn == 128 ? launch_wino<128, true>(a, s) : launch_wino<64, true>(a, s);
@@ -1005,8 +1070,25 @@ int conv_dispatch(const bts_conv_desc* d, bts_stream_t stream) {
         if (bn == 64) return bm == 128 ? launch_conv<128, 64, 4, 2, 32, 2>(a, nchw, s, wsf) : launch_conv<64, 64, 2, 2, 32, 2>(a, nchw, s, wsf);
         return launch_conv<128, 32, 4, 1, 32, 2>(a, nchw, s, wsf);
     }
-    // the encoder stem (7x7 / stride 2 on the 3-channel image): its own kernel (conv_stem.inc)
+    // the encoder stem (7x7 / stride 2 on the 3-channel image): its own kernel (conv_stem.inc), in fp32 under precision 2 too
     if (stem_eligible(a, nchw, prec)) return a.c_out == 96 ? launch_stem<96>(a, s) : launch_stem<64>(a, s);
+    if (prec == 2) {
+        // bf16 operands: never Winograd (its transformed operands would not be the rounded ones), never the fp32 wide 1x1
+        if (bn == 48) bn = 64;                       // no 48-wide bf16 tile: pad DenseNet's growth convs to 64, as precision 1
+        // stride-1 3x3 / sub-pixel 2x2 on maps that tile well, pre-rounded weights: the one-plane halo tile (conv_halo_emu.inc)
+        if ((bn == 128 || bn == 64) && halo_emu_eligible(a, nchw)) {
+            const long halo_wgs = (long)a.fill_frames * ((a.H + 3) / 4) * ((a.W + 31) / 32) * ((a.c_out + bn - 1) / bn) * a.n_classes;
+            if (geometry_kernel_ok(a, bn, wsf, halo_wgs)) {
+                if (a.subpix) return bn == 128 ? launch_halo_emu<128, 2, 1>(a, s) : launch_halo_emu<64, 2, 1>(a, s);
+                return bn == 128 ? launch_halo_emu<128, 3, 1>(a, s) : launch_halo_emu<64, 3, 1>(a, s);
+            }
+        }
+        // everything else (1x1, strided, dilated, bundles, split-K, NCHW output, residual): the row-tiled kernel, which
+        // rounds the fp32 weights itself on the way to LDS (the same rounding as the pre-rounded plane)
+        if (bn == 128) return bm == 128 ? launch_conv<128, 128, 2, 4, 32, 3>(a, nchw, s, wsf) : launch_conv<64, 128, 2, 4, 32, 3>(a, nchw, s, wsf);
+        if (bn == 64) return bm == 128 ? launch_conv<128, 64, 4, 2, 32, 3>(a, nchw, s, wsf) : launch_conv<64, 64, 2, 2, 32, 3>(a, nchw, s, wsf);
+        return launch_conv<128, 32, 4, 1, 32, 3>(a, nchw, s, wsf);
+    }
     // plain 1x1 convolutions with a 192-multiple output: one workgroup per 128 (or 64) pixels x 192 channels (conv_1x1.inc).
     // Layers that will really split K stay on the row-tiled kernel whatever the declared launch (conv1x1_eligible already
     // asks for a chip-filling one).

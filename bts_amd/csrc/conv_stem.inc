@@ -134,7 +134,7 @@ __global__ __launch_bounds__(512, 1) void conv_stem_kernel(const ConvArgs a, int
 
 // 7x7 / stride 2 / pad 3 over a 4-channel-padded NHWC image, 64 or 96 output channels, BN(+ReLU) epilogue, NHWC out
 inline bool stem_eligible(const ConvArgs& a, bool nchw, int prec) {
-    return prec == 0 && !nchw && a.ksize == 7 && a.stride == 2 && a.pad == 3 && a.dil == 1 && a.ups == 0 && !a.subpix && !a.bundled &&
+    return prec != 1 && !nchw && a.ksize == 7 && a.stride == 2 && a.pad == 3 && a.dil == 1 && a.ups == 0 && !a.subpix && !a.bundled &&
            a.c_in_ld == 4 && a.k_pad == 224 && (a.c_out == 96 || a.c_out == 64) && a.c_out_pad == a.c_out &&
            a.pre_scale == nullptr && a.res == nullptr && a.act != 3 && a.n_tail == 0 &&
            (double)32 * (double)(a.y_pix_stride > a.y2_pix_stride ? a.y_pix_stride : a.y2_pix_stride) < 2147483648.0;

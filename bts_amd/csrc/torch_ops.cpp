@@ -218,8 +218,11 @@ void conv_fwd(const Tensor& x, const Tensor& w, OptTensor pre_scale, OptTensor p
         d.tail_planes[j] = tail_planes[j].data_ptr<float>();
     }
     if (w_split.has_value() && w_split->defined()) {
-        TORCH_CHECK(w_split->is_cuda() && w_split->scalar_type() == at::kShort && w_split->is_contiguous() && w_split->numel() == 3 * w.numel(), op,
-                    ": w_split must be the contiguous int16 [classes][3][c_out_pad][k_pad] split of w (ops.split_bf16x3)");
+        // precision 1: three truncation planes (ops.split_bf16x3); precision 2: one round-to-nearest-even plane (ops.round_bf16)
+        const int64_t planes = d.precision == 2 ? 1 : 3;
+        TORCH_CHECK(w_split->is_cuda() && w_split->scalar_type() == at::kShort && w_split->is_contiguous() && w_split->numel() == planes * w.numel(), op,
+                    planes == 1 ? ": w_split must be the contiguous int16 [classes][1][c_out_pad][k_pad] bf16 rounding of w (ops.round_bf16)"
+                                : ": w_split must be the contiguous int16 [classes][3][c_out_pad][k_pad] split of w (ops.split_bf16x3)");
         same_device(x, *w_split, op, "w_split");
         d.w_split = w_split->data_ptr();
     }

@@ -487,14 +487,15 @@ def bn_affine(weight, bias, mean, var, eps: float):
 
 # ---- per-call launch configuration -----------------------------------------------------------------------------------
 # Two facts about a convolution launch belong to the CALLER, not to the process: the arithmetic of the contraction
-# (bts_conv_desc.precision: 0 = fp32-input MFMA, 1 = fp32 emulated on the bf16 matrix cores) and the number of frames
+# (bts_conv_desc.precision: 0 = fp32-input MFMA, 1 = fp32 emulated on the bf16 matrix cores, 2 = bf16 operands with fp32
+# accumulation -- an inference mode) and the number of frames
 # the caller expects to share the chip (bts_conv_desc.fill_frames, which sizes split-K and the tile family; 0 = the
 # library default of 8).  Both change output BITS (fp32 summation order / product rounding), so two models in one
 # process must be able to hold different values: they live in a thread-local scope that a model opens around its own
 # forward (``BtsModel.fill_frames`` / ``BtsModel.conv_precision``, bts_amd/bts.py) -- there is no process-wide setter.
 # Code that calls conv_forward directly (tests, micro-benchmarks) wraps the calls in ``launch_config(...)``.
 _cfg_tls = threading.local()
-_PRECISIONS = {"fp32": 0, "bf16x3": 1, 0: 0, 1: 1}
+_PRECISIONS = {"fp32": 0, "bf16x3": 1, "bf16": 2, 0: 0, 1: 1, 2: 2}
 
 
 class launch_config:
@@ -508,7 +509,7 @@ class launch_config:
                 raise BtsHipError("launch_config: fill_frames must be in 0..4096")
         if precision is not None:
             if precision not in _PRECISIONS:
-                raise BtsHipError("launch_config: precision must be 'fp32' / 0 or 'bf16x3' / 1")
+                raise BtsHipError("launch_config: precision must be 'fp32' / 0, 'bf16x3' / 1 or 'bf16' / 2")
             precision = _PRECISIONS[precision]
         self._new = (fill_frames, precision)
 
@@ -576,6 +577,29 @@ def split_bf16x3(w: torch.Tensor) -> torch.Tensor:
     lo = (r1 - mid.view(torch.float32)).view(torch.int32) & -65536
     planes = torch.stack([hi, mid, lo], dim=-3)
     return (planes >> 16).to(torch.int16).contiguous()
+
+
+def round_bf16(w: torch.Tensor) -> torch.Tensor:
+    """The bf16 mode's weight plane, made offline: int16 [.., 1, R, K] holding the bits of w rounded to the nearest bf16
+    (ties to even) for a [.., R, K] float32 input -- ``Tensor.to(torch.bfloat16)``, bit for bit what the kernels' own
+    rne_store does to an operand on its way to LDS (csrc/conv_mfma.hip)."""
+    _need(w, "round_bf16")
+    return w.to(torch.bfloat16).view(torch.int16).unsqueeze(-3).contiguous()
+
+
+def _derived_weight(w_packed: torch.Tensor, attr: str, make):
+    """A form of a packed weight made once and cached on it as ``attr``; re-made in place when train.WeightPacker has
+    refilled the packed buffer since (``_bts_pack_seq``)."""
+    cached = getattr(w_packed, attr, None)
+    seq = getattr(w_packed, "_bts_pack_seq", 0)
+    if cached is None or getattr(w_packed, attr + "_seq", 0) != seq:
+        if cached is None:
+            cached = make(w_packed)
+        else:
+            cached.copy_(make(w_packed))
+        setattr(w_packed, attr, cached)
+        setattr(w_packed, attr + "_seq", seq)
+    return cached
 
 
 _WINO = os.environ.get("BTS_CONV_WINO", "1").strip() not in ("", "0")      # fused Winograd F(2x2,3x3) for eligible 3x3 layers (0: direct kernels, A/B)
@@ -702,19 +726,16 @@ def conv_forward(x2d: torch.Tensor, B: int, h_in: int, w_in: int, w_packed: torc
     keep = []
     d.n_bundles = n_bundles if n_bundles > 1 else 0
     d.fill_frames, d.precision = current_launch_config()
-    if d.precision == 1 and n_bundles <= 1 and not n_tail:
-        # weights pre-split into bf16 planes for the emulated mode's halo-tile kernel (LDS-DMA of plain bytes); made once
-        # per packed weight tensor and kept on it
-        ws3 = getattr(w_packed, "_bts_split3", None)
-        seq3 = getattr(w_packed, "_bts_pack_seq", 0)       # train.WeightPacker refills packed buffers in place: re-split then
-        if ws3 is None or getattr(w_packed, "_bts_split3_seq", 0) != seq3:
-            if ws3 is None:
-                ws3 = split_bf16x3(w_packed)
-            else:
-                ws3.copy_(split_bf16x3(w_packed))
-            w_packed._bts_split3, w_packed._bts_split3_seq = ws3, seq3
-        keep.append(ws3)
-        d.w_split = ws3.data_ptr()
+    wsplit_t = None
+    if d.precision in (1, 2) and n_bundles <= 1 and not n_tail:
+        # weights pre-split into bf16 planes (precision 1) or pre-rounded to one bf16 plane (precision 2) for the halo-tile
+        # kernels of those modes (LDS-DMA of plain bytes); made once per packed weight tensor and kept on it
+        if d.precision == 1:
+            wsplit_t = _derived_weight(w_packed, "_bts_split3", split_bf16x3)
+        else:
+            wsplit_t = _derived_weight(w_packed, "_bts_round1", round_bf16)
+        keep.append(wsplit_t)
+        d.w_split = wsplit_t.data_ptr()
     d.n_tail = n_tail
     for j in range(n_tail):
         d.tail_planes[j] = tail_planes[j].data_ptr()
@@ -793,7 +814,11 @@ def conv_forward(x2d: torch.Tensor, B: int, h_in: int, w_in: int, w_packed: torc
         bm, bn, kind = C.c_int(0), C.c_int(0), C.c_int(0)
         _lib.load().bts_conv_plan_f32(C.byref(d), C.byref(bm), C.byref(bn), C.byref(kind))
         lay = "nchw" if y_nchw is not None else "nhwc"
-        if (kind.value & 15) == 6:
+        if (kind.value & 15) == 8:
+            variant = "conv_halo_emu_kernel<%d,k%d,bf16>" % (bn.value, 2 if subpixel else 3)
+        elif (kind.value & 15) == 7:
+            variant = "conv_fwd_kernel<%d,%d,%s%s,bf16>" % (bm.value, bn.value, lay, ",splitk" if kind.value & 16 else "")
+        elif (kind.value & 15) == 6:
             variant = "conv_wino_kernel<%d>" % bn.value
         elif (kind.value & 15) == 5:
             variant = "conv_halo_emu_kernel<%d,k%d>" % (bn.value, 2 if subpixel else 3)
@@ -826,10 +851,9 @@ def conv_forward(x2d: torch.Tensor, B: int, h_in: int, w_in: int, w_packed: torc
         pre_s, pre_b = pre if pre is not None else (None, None)
         e1_s, e1_b = e1 if e1 is not None else (None, None)
         e2_s, e2_b = e2 if e2 is not None else (None, None)
-        ws3_t = w_packed._bts_split3 if d.w_split else None
         uw_t = w_packed._bts_wino if d.w_wino else None
         run = lambda: _op(lambda: tops.conv_fwd(x2d, w_packed, pre_s, pre_b, e1_s, e1_b, e2_s, e2_b, out, y2_2d, res2d, splitk_ws,
-                                                list(tail_planes) if tail_planes else [], ws3_t, uw_t, geom))
+                                                list(tail_planes) if tail_planes else [], wsplit_t, uw_t, geom))
     else:
         run = lambda: _lib.load().bts_conv_fwd_f32(C.byref(d), _stream(x2d))
     with torch.cuda.device(x2d.device):

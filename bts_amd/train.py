@@ -216,11 +216,19 @@ class model_step:
         return False
 
 
+def refuse_bf16(where: str) -> None:
+    """The training path computes in fp32 (or its bf16x3 emulation) only: bf16 operands (precision 2) are an inference
+    mode, and a gradient taken through them would be a different function's."""
+    if ops.current_launch_config()[1] == 2:
+        raise BtsHipError("%s: conv_precision 'bf16' is an inference mode; training runs in 'fp32' or 'bf16x3'" % where)
+
+
 class _ConvFn(torch.autograd.Function):
     """y = conv2d(nearest_up(x, up), w, stride, padding, dilation, groups), bias-free, on libbts_hip.so."""
 
     @staticmethod
     def forward(ctx, x, weight, stride, padding, dilation, up, tag, groups, act=ops.ACT_NONE):
+        refuse_bf16("train.conv2d")
         ops._need(x, "train.conv2d")
         ops._need(weight, "train.conv2d")
         B, C, h, w = x.shape
@@ -514,6 +522,7 @@ class _DenseBlockFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, block, *params):
+        refuse_bf16("train.densenet_block")
         B, C0, H, W = x.shape
         layers = list(block.values())
         g = layers[0].conv2.out_channels

@@ -172,7 +172,13 @@ typedef struct bts_conv_desc {
                                 1: fp32 EMULATED on the bf16 matrix cores -- every operand split into three bf16
                                 pieces on the way to LDS, six bf16 MFMAs per product block, fp32 accumulation; the
                                 result differs from mode 0 only by fp32 rounding (measured 1.2e-6 vs 1.1e-6 of
-                                max|result| against fp64), at up to 2.6x the MFMA rate.  Same inputs, outputs, tiles. */
+                                max|result| against fp64), at up to 2.6x the MFMA rate.  Same inputs, outputs, tiles.
+                                2: bf16 OPERANDS (an inference mode): the conv input after the prologue and zero padding,
+                                and the packed weights `w`, are rounded to bf16 (round to nearest, ties to even); each
+                                product of two bf16 values is exact and accumulates in fp32 (one v_mfma_f32_32x32x16_bf16 per
+                                16 k).  The epilogue and the HBM tensors stay fp32; bf16 keeps fp32's exponent range.  The
+                                planar-tail layers and the 7x7 encoder stem stay on their fp32 kernels; no Winograd.
+                                $BTS_CONV_PRECISION (0 / 1) overrides this field in every mode.                          */
     const float* tail_planes[4];  /* planar tail operand: n_tail (1..4) extra input channels that live in dense one-channel
                                 planes [B,h_in,w_in] instead of the NHWC buffer -- the LPG depth maps / reduc1x1 that the
                                 reference concatenates behind the features (pytorch/bts.py:260, 274, 287: cat[upconv3, skip,
@@ -192,12 +198,16 @@ typedef struct bts_conv_desc {
                                 from the split-K kernels to the wide 1x1 tile and the halo kernel -- choices that would cost a
                                 single-frame caller 45 % if they were tied to the default.  Results of different fill_frames
                                 differ in summation order (fp32 rounding)                                                  */
-    const void* w_split;       /* optional, precision = 1 only: the packed weights `w` pre-split into three bf16 planes --
+    const void* w_split;       /* optional, precision = 1 or 2 only.  Precision 1: the packed weights `w` pre-split into three bf16 planes --
                                 [classes][3][c_out_pad][k_pad] bf16 (classes = 4 for sub-pixel, else 1), plane 0 = the top 16
                                 bits of w, plane 1 = the top 16 bits of (w - plane 0), plane 2 = the top 16 bits of the rest
                                 (the kernels' own truncation split; bts_amd/ops.py:split_bf16x3).  With it the halo-tile
                                 kernel of the emulated mode streams weight tiles global -> LDS by LDS-DMA; NULL = the
-                                row-tiled kernel splits `w` on the fly.  16-byte aligned.                                  */
+                                row-tiled kernel splits `w` on the fly.  Precision 2: ONE plane [classes][1][c_out_pad][k_pad]
+                                bf16 (int16 bits), `w` rounded to nearest even (bts_amd/ops.py:round_bf16); the bf16 halo-tile
+                                kernel streams it by LDS-DMA; NULL = the row-tiled kernel rounds `w` on the fly, the same
+                                rounding.  The layout follows THIS descriptor's precision: when $BTS_CONV_PRECISION
+                                overrides it, w_split is ignored.  16-byte aligned.                                        */
     const float* w_wino;       /* optional, precision = 0, stride-1 3x3 / padding 1 / dilation 1 only: the weights in Winograd
                                 F(2x2,3x3) form U = G g G^T, in MFMA B-fragment order [16 xi][c_in_ld/32][c_out_pad/32][4][64][4]
                                 (bts_amd/ops.py:pack_wino_weight).  With it (and $BTS_CONV_WINO) eligible layers run the fused
@@ -223,7 +233,10 @@ int bts_upconv_combine_f32(const float* taps, long taps_pix_stride, int B, int h
  * dispatch path): lets a profiler attribute a launch to its kernel instantiation.
  *   kind & 15: 0 = conv_fwd_kernel (row-tiled, BM x BN), 1 = conv_halo_kernel (spatial 128-pixel tile x BN),
  *              2 = conv_halo_kernel with the planar tail operand, 3 = conv1x1_kernel (bm = 128 or 64 pixels x BN),
- *              4 = conv_stem_kernel (7x7 / stride-2 encoder stem, 8x32-pixel tiles x BN);
+ *              4 = conv_stem_kernel (7x7 / stride-2 encoder stem, 8x32-pixel tiles x BN),
+ *              5 = conv_halo_emu_kernel (precision 1: bf16x3 halo tile), 6 = conv_wino_kernel (Winograd F(2x2,3x3)),
+ *              7 = conv_fwd_kernel with bf16 operands (precision 2, row-tiled), 8 = conv_halo_emu_kernel with one bf16
+ *              plane (precision 2, halo tile);
  *   kind & 16: split-K (+ splitk_reduce_kernel);  kind & 32: the eight-wave variant of the 48-wide halo tile (under-filled launches). */
 int bts_conv_plan_f32(const bts_conv_desc* desc, int* bm, int* bn, int* kind);
 
