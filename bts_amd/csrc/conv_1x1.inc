@@ -217,7 +217,7 @@ int launch_conv1x1(const ConvArgs& a0, hipStream_t s) {
     a.ksplit = 1;
     const long nwg = n_mtiles * a.n_ntiles;
     if (nwg > 0x7fffffffL) return BTS_ERR_INVALID;
-    if (g_dry) { *g_dry = ConvChoice{3, BM, BN, 1}; return 0; }
+    if (g_dry) { *g_dry = ConvChoice{BTS_CONV_KIND_WIDE_1X1, BM, BN, 1}; return 0; }
     const size_t lds = (size_t)(2 * BM + (SB ? 1 : 2) * BN) * LdsLd<32>::value * sizeof(float);
     auto k = conv1x1_kernel<BN, WM, SB>;
     static std::atomic<unsigned long long> lds_set{0};

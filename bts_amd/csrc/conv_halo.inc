@@ -486,7 +486,7 @@ int launch_halo(const ConvArgs& a0, bool nchw, hipStream_t s) {
     const long nwg = n_mtiles * a.n_ntiles * a.n_classes;
     if (nwg > 0x7fffffffL) return BTS_ERR_INVALID;
     if (DIL > 1 && (nchw || a.dil != DIL || a.pad != DIL)) return BTS_ERR_INVALID;
-    if (g_dry) { *g_dry = ConvChoice{(TAIL ? 2 : 1) + (BN == 48 && WM == 8 ? 32 : 0) + (DIL > 1 ? 64 : 0), 128, BN, 1}; return 0; }      // +32: eight-wave 48-wide variant, +64: dilated tile
+    if (g_dry) { *g_dry = ConvChoice{(TAIL ? BTS_CONV_KIND_HALO_TAIL : BTS_CONV_KIND_HALO) | (BN == 48 && WM == 8 ? BTS_CONV_FLAG_W8 : 0) | (DIL > 1 ? BTS_CONV_FLAG_DIL : 0), 128, BN, 1}; return 0; }
     static_assert(halo_lds_bytes<BN, MF, KS, DIL>() == 2 * (NPIX + BN) * LdsLd<MF>::value * 4, "LDS size");
     const int c_main = TAIL ? a.c_in_ld - 4 : a.c_in_ld;
     a.halo_single_a = c_main <= BK ? 1 : 0;

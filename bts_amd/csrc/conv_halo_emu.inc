@@ -363,7 +363,7 @@ int launch_halo_emu(const ConvArgs& a0, hipStream_t s) {
     a.ksplit = 1;
     const long nwg = n_mtiles * a.n_ntiles * a.n_classes;
     if (nwg > 0x7fffffffL) return BTS_ERR_INVALID;
-    if (g_dry) { *g_dry = ConvChoice{NP == 3 ? 5 : 8, 128, BN, 1}; return 0; }
+    if (g_dry) { *g_dry = ConvChoice{NP == 3 ? BTS_CONV_KIND_HALO_EMU : BTS_CONV_KIND_HALO_BF16, 128, BN, 1}; return 0; }
     constexpr size_t lds = (size_t)halo_emu_lds_bytes<BN, KS, NP>();
     static_assert(lds <= 160 * 1024, "LDS");
     auto k = conv_halo_emu_kernel<BN, KS, NP>;

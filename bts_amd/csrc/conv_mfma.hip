@@ -882,7 +882,7 @@ int launch_conv(const ConvArgs& a0, bool nchw, hipStream_t s, long ws_floats) {
     const bool lean = (a.c_in_ld % BK) == 0 && a.ups == 0;
     a.tapskip = (knobs().tapskip && lean && a.ksplit == 1 && a.stride == 1 && a.ksize > 1 && a.ksize * a.ksize <= 49) ? 1 : 0;
     if (g_dry) {
-        *g_dry = ConvChoice{PREC == 3 ? 7 : 0, BM, BN, a.ksplit};
+        *g_dry = ConvChoice{PREC == 3 ? BTS_CONV_KIND_ROW_BF16 : BTS_CONV_KIND_ROW, BM, BN, a.ksplit};
         const long taps = (long)a.ksize * a.ksize;
         g_dry->ksteps_dense = n_mtiles * a.n_classes * taps;
         g_dry->ksteps_issued = g_dry->ksteps_dense;
@@ -1143,22 +1143,27 @@ int conv_dispatch(const bts_conv_desc* d, bts_stream_t stream) {
 
 }  // namespace
 
+// The real decision path with g_dry set: launch_* fill `c` instead of launching.
+static int conv_dry_run(const bts_conv_desc* d, ConvChoice& c) {
+    c = ConvChoice{BTS_CONV_KIND_ROW, 0, 0, 1};
+    g_dry = &c;
+    const int rc = conv_dispatch(d, nullptr);
+    g_dry = nullptr;
+    return rc;
+}
+
 extern "C" int bts_conv_plan_f32(const bts_conv_desc* d, int* bm, int* bn, int* kind) {
     if (!d || !bm || !bn || !kind) return BTS_ERR_INVALID;
-    ConvChoice c{0, 0, 0, 1};
-    g_dry = &c;
-    const int rc = conv_dispatch(d, nullptr);          // the real decision path; launch_* fill `c` instead of launching
-    g_dry = nullptr;
-    *bm = c.bm; *bn = c.bn; *kind = c.kind + (c.ksplit > 1 ? 16 : 0);
+    ConvChoice c;
+    const int rc = conv_dry_run(d, c);
+    *bm = c.bm; *bn = c.bn; *kind = c.kind | (c.ksplit > 1 ? BTS_CONV_FLAG_SPLITK : 0);
     return rc;
 }
 
 extern "C" int bts_conv_plan_ksteps_f32(const bts_conv_desc* d, long* issued, long* dense) {
     if (!d || !issued || !dense) return BTS_ERR_INVALID;
-    ConvChoice c{0, 0, 0, 1};
-    g_dry = &c;
-    const int rc = conv_dispatch(d, nullptr);
-    g_dry = nullptr;
+    ConvChoice c;
+    const int rc = conv_dry_run(d, c);
     *issued = c.ksteps_issued; *dense = c.ksteps_dense;      // both 0 for the kernel families that never skip
     return rc;
 }

@@ -147,7 +147,7 @@ int launch_stem(const ConvArgs& a0, hipStream_t s) {
     const long n_tiles = (long)a.B * n_ty * n_tx;
     if (n_tiles > 0x7fffffffL) return BTS_ERR_INVALID;
     a.n_ntiles = 1; a.tiles_per_class = (int)n_tiles; a.ksplit = 1;
-    if (g_dry) { *g_dry = ConvChoice{4, 256, BN, 1}; return 0; }
+    if (g_dry) { *g_dry = ConvChoice{BTS_CONV_KIND_STEM, 256, BN, 1}; return 0; }
     const size_t lds = (size_t)(BN * 228 + 2 * 21 * 320) * sizeof(float);
     auto k = conv_stem_kernel<BN>;
     static std::atomic<unsigned long long> lds_set{0};

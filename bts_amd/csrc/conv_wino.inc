@@ -446,7 +446,7 @@ int launch_wino(const ConvArgs& a0, hipStream_t s) {
     a.ksplit = 1;
     const long nwg = n_mtiles * a.n_ntiles;
     if (nwg > 0x7fffffffL) return BTS_ERR_INVALID;
-    if (g_dry) { *g_dry = ConvChoice{6, 128, BN, 1}; return 0; }
+    if (g_dry) { *g_dry = ConvChoice{BTS_CONV_KIND_WINO, 128, BN, 1}; return 0; }
     constexpr size_t lds = (size_t)wino_lds_bytes<BN, TAIL>();
     static_assert(lds <= 160 * 1024, "LDS");
     auto k = conv_wino_kernel<BN, TAIL>;

@@ -12,8 +12,9 @@ from typing import List, Optional, Sequence, Tuple
 
 import torch
 
-from . import _lib
+from . import _lib, conv_plan
 from ._lib import BtsHipError, ConvDesc, ConvWgradDesc
+from .conv_plan import conv_out_hw, round_up
 
 ACT_NONE, ACT_RELU, ACT_ELU, ACT_SIGMOID = 0, 1, 2, 3
 
@@ -352,10 +353,6 @@ def nhwc_to_nchw(src2d: torch.Tensor, B: int, H: int, W: int) -> torch.Tensor:
 
 
 # ------------------------------------------------------------------------------ conv
-def round_up(v: int, m: int) -> int:
-    return (v + m - 1) // m * m
-
-
 def pack_conv_weight(w: torch.Tensor, perm: Optional[torch.Tensor] = None,
                      c_in_ld: Optional[int] = None) -> Tuple[torch.Tensor, int, int]:
     """[cout,cin,k,k] -> packed [cout_pad][k_pad], K flattened tap-major: k = tap*c_in_ld + c, zero padded
@@ -587,14 +584,17 @@ def round_bf16(w: torch.Tensor) -> torch.Tensor:
     return w.to(torch.bfloat16).view(torch.int16).unsqueeze(-3).contiguous()
 
 
-def _derived_weight(w_packed: torch.Tensor, attr: str, make):
+def _derived_weight(w_packed: torch.Tensor, attr: str, make, refill=None):
     """A form of a packed weight made once and cached on it as ``attr``; re-made in place when train.WeightPacker has
-    refilled the packed buffer since (``_bts_pack_seq``)."""
+    refilled the packed buffer since (``_bts_pack_seq``, bumped whenever it refills the buffer): by ``refill(w_packed,
+    cached)`` when the form can be written straight into its buffer, else by a copy of ``make(w_packed)``."""
     cached = getattr(w_packed, attr, None)
     seq = getattr(w_packed, "_bts_pack_seq", 0)
     if cached is None or getattr(w_packed, attr + "_seq", 0) != seq:
         if cached is None:
             cached = make(w_packed)
+        elif refill is not None:
+            refill(w_packed, cached)
         else:
             cached.copy_(make(w_packed))
         setattr(w_packed, attr, cached)
@@ -659,6 +659,149 @@ def pack_wino_weight_reference(w_packed: torch.Tensor, c_in_ld: int, n_tail: int
     return U.permute(6, 2, 0, 3, 4, 1, 5).contiguous().view(-1)                                  # (xi, chunk, ct, g, lh, li, q)
 
 
+def _conv_describe(x2d, B, h_in, w_in, w_packed, c_out, ksize, dil, up, c_in_ld, pre, pre_relu, e1, act, e2, y2d, y_nchw,
+                   stride, pad, y2_2d, subpixel, splitk_ws, res2d, n_bundles, tail_planes):
+    """conv_forward's argument checks and its descriptor: (filled ConvDesc, output tensor, tensors to keep alive)."""
+    xs, xc = _rows2d(x2d, "conv_forward")
+    _need(w_packed, "conv_forward")
+    n_tail = len(tail_planes) if tail_planes else 0
+    if c_in_ld is None:
+        c_in_ld = xc + (4 if n_tail else 0)
+    if subpixel:
+        if ksize != 3 or up != 2 or dil != 1 or stride != 1 or w_packed.dim() != 3 or w_packed.shape[0] != 4:
+            raise BtsHipError("conv_forward: subpixel needs ksize=3, up=2 and weights from pack_upconv_subpixel")
+        _, c_out_pad, k_pad = w_packed.shape
+    elif n_bundles > 1:
+        if w_packed.dim() != 3 or w_packed.shape[0] != n_bundles or c_in_ld is None:
+            raise BtsHipError("conv_forward: bundled weights must be [n_bundles, c_out_pad, k_pad] with c_in_ld per bundle")
+        _, c_out_pad, k_pad = w_packed.shape
+    else:
+        c_out_pad, k_pad = w_packed.shape
+    if pad is None:
+        pad = dil * (ksize // 2)
+    d = conv_plan.geometry_desc(B, h_in, w_in, c_in_ld, c_out, ksize, dil, stride, pad, up, subpixel, n_bundles, n_tail,
+                                y_nchw is not None, *current_launch_config(), x_pix_stride=xs, c_out_pad=c_out_pad)
+    if k_pad != d.k_pad or not w_packed.is_contiguous():
+        raise BtsHipError("conv_forward: packed weight [%d,%d] does not match ksize %d / c_in_ld %d"
+                          % (c_out_pad, k_pad, ksize, c_in_ld))
+    if c_in_ld % 4 or (c_in_ld - (4 if n_tail else 0)) * n_bundles > xc or x2d.shape[0] != B * h_in * w_in:
+        raise BtsHipError("conv_forward: bad input view (c_in_ld %d, view %s)" % (c_in_ld, tuple(x2d.shape)))
+    if n_tail:
+        if n_tail > 4 or ksize != 3 or stride != 1 or dil != 1 or up != 1 or subpixel or n_bundles > 1:
+            raise BtsHipError("conv_forward: tail_planes need a plain 3x3 / stride 1 / dilation 1 convolution and at most 4 planes")
+        for j, t in enumerate(tail_planes):
+            _need(t, "conv_forward")
+            if t.numel() != B * h_in * w_in or not t.is_contiguous():
+                raise BtsHipError("conv_forward: every tail plane must be a contiguous [B,1,h_in,w_in] map")
+            d.tail_planes[j] = t.data_ptr()
+    H, W = conv_out_hw(h_in, w_in, ksize, dil, stride, pad, up)
+    d.x, d.w = x2d.data_ptr(), w_packed.data_ptr()
+    keep = []
+    for name, pair, n in (("pre", pre, c_in_ld * n_bundles), ("e1", e1, c_out_pad * n_bundles), ("e2", e2, c_out_pad * n_bundles)):
+        if pair is not None:
+            s, b = pair
+            if s.numel() != n or b.numel() != n:
+                raise BtsHipError("conv_forward: %s vectors must have %d elements" % (name, n))
+            _need(s, "conv_forward")
+            _need(b, "conv_forward")
+            keep += [s, b]
+            setattr(d, name + "_scale", s.data_ptr())
+            setattr(d, name + "_shift", b.data_ptr())
+    d.pre_relu, d.act = int(bool(pre_relu)), int(act)
+    if (y2d is None) == (y_nchw is None):
+        raise BtsHipError("conv_forward: give exactly one of y2d / y_nchw")
+    if y2d is not None:
+        def rows(t, what):                                 # an NHWC view of the whole output: (pointer, pixel stride)
+            ts, tc = _rows2d(t, "conv_forward")
+            if tc != c_out * n_bundles or t.shape[0] != B * H * W:
+                raise BtsHipError("conv_forward: bad %s" % what)
+            return t.data_ptr(), ts
+
+        out = y2d
+        d.y, d.y_pix_stride = rows(y2d, "output view")
+        if y2_2d is not None:
+            d.y2, d.y2_pix_stride = rows(y2_2d, "second output view")
+        if res2d is not None:
+            d.res, d.res_pix_stride = rows(res2d, "residual view %s" % (tuple(res2d.shape),))
+    else:
+        if res2d is not None or n_bundles > 1:
+            raise BtsHipError("conv_forward: residual / bundled convolutions write NHWC only")
+        _need(y_nchw, "conv_forward")
+        if tuple(y_nchw.shape) != (B, c_out, H, W) or not y_nchw.is_contiguous():
+            raise BtsHipError("conv_forward: y_nchw must be contiguous [B,c_out,H,W]")
+        d.y = y_nchw.data_ptr()
+        out = y_nchw
+    if splitk_ws is not None:
+        _need(splitk_ws, "conv_forward")
+        if not splitk_ws.is_contiguous():
+            raise BtsHipError("conv_forward: splitk_ws must be contiguous")
+        d.splitk_ws, d.splitk_ws_floats = splitk_ws.data_ptr(), splitk_ws.numel()
+    return d, out, keep
+
+
+def _conv_derived_weights(d: ConvDesc, w_packed: torch.Tensor, keep: list):
+    """The forms of ``w_packed`` this descriptor's mode wants besides the packed fp32 matrix, each made once per packed
+    weight tensor and kept on it: (bf16 planes or None, Winograd form or None), also set on ``d``."""
+    wsplit_t = uw = None
+    c_main = d.c_in_ld - (4 if d.n_tail else 0)
+    if d.precision in (1, 2) and not d.n_bundles and not d.n_tail:
+        # weights pre-split into bf16 planes (precision 1) or pre-rounded to one bf16 plane (precision 2) for the halo-tile
+        # kernels of those modes (LDS-DMA of plain bytes)
+        wsplit_t = (_derived_weight(w_packed, "_bts_split3", split_bf16x3) if d.precision == 1 else
+                    _derived_weight(w_packed, "_bts_round1", round_bf16))
+        keep.append(wsplit_t)
+        d.w_split = wsplit_t.data_ptr()
+    if (_WINO and d.precision == 0 and d.ksize == 3 and d.stride == 1 and d.dil == 1 and d.pad == 1 and d.up == 1
+            and not d.n_bundles and c_main % 32 == 0 and d.c_in_ld > 4 and not d.y_nchw):
+        # Winograd-form weights for the fused F(2x2,3x3) kernel
+        def make(w):
+            # which channel tile the library will use for this layer (its own decision on the COMPLETE descriptor, asked
+            # once per weight: the two packings differ): 48 -> the 16x16x4 tile.  (bn is choose_tile's pure function of
+            # c_out, whatever kernel family this particular launch ends up on)
+            d.w_wino = w.data_ptr()
+            w._bts_wino_c16 = d.c_out if conv_plan.query(d).bn == 48 else 0
+            return pack_wino_weight(w, d.c_in_ld, d.n_tail, c_out16=w._bts_wino_c16)
+
+        uw = _derived_weight(w_packed, "_bts_wino", make, refill=lambda w, out: pack_wino_weight(
+            w, d.c_in_ld, d.n_tail, c_out16=getattr(w, "_bts_wino_c16", 0), out=out))
+        keep.append(uw)
+        d.w_wino = uw.data_ptr()
+    return wsplit_t, uw
+
+
+def _conv_trace_accounting(d: ConvDesc, c_in_real: Optional[int], algo_flops: Optional[float]):
+    """What a KernelTrace records for this launch: (kernel name, algorithmic FLOPs, algorithmic bytes, FLOPs the kernel's
+    own formulation issues).  Only called while a trace is active."""
+    B, c_in_ld = d.B, d.c_in_ld
+    H, W = (2 * d.h_in, 2 * d.w_in) if d.subpixel else conv_out_hw(d.h_in, d.w_in, d.ksize, d.dil, d.stride, d.pad, d.up)
+    flops_taps, taps = (9, 4) if d.subpixel else (d.ksize * d.ksize,) * 2
+    cin = c_in_real if c_in_real is not None else c_in_ld
+    npix_out = B * H * W
+    c_out = d.c_out * max(d.n_bundles, 1)                  # algorithmic FLOPs of the grouped conv are passed in c_in_real
+    #                                                        (real input channels per OUTPUT channel = channels per group)
+    flops = 2.0 * npix_out * c_out * cin * flops_taps      # algorithmic: the reference's 3x3 on the upsampled map
+    if algo_flops is not None:
+        flops = float(algo_flops)
+    nbytes = 4.0 * (B * d.h_in * d.w_in * cin + npix_out * c_out + flops_taps * c_out * cin)
+    plan = conv_plan.query(d, ksteps=True)
+    variant = conv_plan.kernel_name(plan, bool(d.y_nchw), bool(d.subpixel))
+    xflops = 2.0 * npix_out * c_out * (c_in_ld if d.n_bundles > 1 else cin) * taps
+    if plan.family == conv_plan.Family.WINO:
+        # MFMA products the Winograd kernel ISSUES: 16 transform positions x 32 tiles x BN channels x c_in per workgroup
+        # (4 instead of 9 per output and input channel, plus the ragged 8x16-pixel tiles and the channels padded to BN)
+        nwg = B * ((H + 7) // 8) * ((W + 15) // 16) * ((c_out + plan.bn - 1) // plan.bn)
+        xflops = 2.0 * nwg * 16 * 32 * plan.bn * c_in_ld
+    if plan.dense > 0:                                     # tap skipping (dilated ASPP branches): FLOPs really issued
+        xflops *= plan.issued / plan.dense
+    return variant, flops, nbytes, xflops
+
+
+# bts_hip::conv_fwd's `geom` argument: these descriptor fields, in the order csrc/torch_ops.cpp unpacks them
+_GEOM_FIELDS = ("x_pix_stride", "c_in_ld", "k_pad", "B", "h_in", "w_in", "up", "ksize", "dil", "stride", "pad", "c_out", "c_out_pad",
+                "pre_relu", "act", "y_pix_stride", "y_nchw", "subpixel", "y2_pix_stride", "res_pix_stride", "n_bundles", "precision",
+                "fill_frames")
+
+
 def conv_forward(x2d: torch.Tensor, B: int, h_in: int, w_in: int, w_packed: torch.Tensor, c_out: int,
                  ksize: int, dil: int = 1, up: int = 1, c_in_ld: Optional[int] = None,
                  pre: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, pre_relu: bool = False,
@@ -682,182 +825,20 @@ def conv_forward(x2d: torch.Tensor, B: int, h_in: int, w_in: int, w_packed: torc
     ``res2d``: residual [B*H*W, c_out] added after e1, before the activation.  ``n_bundles`` > 1: grouped convolution
     as independent channel bundles (w_packed [n_bundles, c_out_pad, k_pad] from pack_grouped_conv_weight; c_in_ld /
     c_out are PER BUNDLE, x2d / y2d hold all n_bundles*c_in_ld / n_bundles*c_out channels)."""
-    xs, xc = _rows2d(x2d, "conv_forward")
-    _need(w_packed, "conv_forward")
-    n_tail = len(tail_planes) if tail_planes else 0
-    if c_in_ld is None:
-        c_in_ld = xc + (4 if n_tail else 0)
-    flops_taps = ksize * ksize
-    if subpixel:
-        if ksize != 3 or up != 2 or dil != 1 or stride != 1 or w_packed.dim() != 3 or w_packed.shape[0] != 4:
-            raise BtsHipError("conv_forward: subpixel needs ksize=3, up=2 and weights from pack_upconv_subpixel")
-        _, c_out_pad, k_pad = w_packed.shape
-        taps = 4
-    elif n_bundles > 1:
-        if w_packed.dim() != 3 or w_packed.shape[0] != n_bundles or c_in_ld is None:
-            raise BtsHipError("conv_forward: bundled weights must be [n_bundles, c_out_pad, k_pad] with c_in_ld per bundle")
-        _, c_out_pad, k_pad = w_packed.shape
-        taps = ksize * ksize
-    else:
-        c_out_pad, k_pad = w_packed.shape
-        taps = ksize * ksize
-    if k_pad != round_up(taps * c_in_ld, 32) or not w_packed.is_contiguous():
-        raise BtsHipError("conv_forward: packed weight [%d,%d] does not match ksize %d / c_in_ld %d"
-                          % (c_out_pad, k_pad, ksize, c_in_ld))
-    if c_in_ld % 4 or (c_in_ld - (4 if n_tail else 0)) * n_bundles > xc or x2d.shape[0] != B * h_in * w_in:
-        raise BtsHipError("conv_forward: bad input view (c_in_ld %d, view %s)" % (c_in_ld, tuple(x2d.shape)))
-    if n_tail:
-        if n_tail > 4 or ksize != 3 or stride != 1 or dil != 1 or up != 1 or subpixel or n_bundles > 1:
-            raise BtsHipError("conv_forward: tail_planes need a plain 3x3 / stride 1 / dilation 1 convolution and at most 4 planes")
-        for t in tail_planes:
-            _need(t, "conv_forward")
-            if t.numel() != B * h_in * w_in or not t.is_contiguous():
-                raise BtsHipError("conv_forward: every tail plane must be a contiguous [B,1,h_in,w_in] map")
-    if pad is None:
-        pad = dil * (ksize // 2)
-    H = (h_in * up + 2 * pad - dil * (ksize - 1) - 1) // stride + 1
-    W = (w_in * up + 2 * pad - dil * (ksize - 1) - 1) // stride + 1
-    d = ConvDesc()
-    d.x, d.x_pix_stride, d.c_in_ld, d.k_pad = x2d.data_ptr(), xs, c_in_ld, k_pad
-    d.B, d.h_in, d.w_in, d.up, d.ksize, d.dil, d.stride, d.pad = B, h_in, w_in, up, ksize, dil, stride, pad
-    if subpixel:
-        d.up, d.ksize, d.pad, d.subpixel = 1, 2, 0, 1
-    d.w, d.c_out, d.c_out_pad = w_packed.data_ptr(), c_out, c_out_pad
-    keep = []
-    d.n_bundles = n_bundles if n_bundles > 1 else 0
-    d.fill_frames, d.precision = current_launch_config()
-    wsplit_t = None
-    if d.precision in (1, 2) and n_bundles <= 1 and not n_tail:
-        # weights pre-split into bf16 planes (precision 1) or pre-rounded to one bf16 plane (precision 2) for the halo-tile
-        # kernels of those modes (LDS-DMA of plain bytes); made once per packed weight tensor and kept on it
-        if d.precision == 1:
-            wsplit_t = _derived_weight(w_packed, "_bts_split3", split_bf16x3)
-        else:
-            wsplit_t = _derived_weight(w_packed, "_bts_round1", round_bf16)
-        keep.append(wsplit_t)
-        d.w_split = wsplit_t.data_ptr()
-    d.n_tail = n_tail
-    for j in range(n_tail):
-        d.tail_planes[j] = tail_planes[j].data_ptr()
-    for name, pair, n in (("pre", pre, c_in_ld * n_bundles), ("e1", e1, c_out_pad * n_bundles), ("e2", e2, c_out_pad * n_bundles)):
-        if pair is not None:
-            s, b = pair
-            if s.numel() != n or b.numel() != n:
-                raise BtsHipError("conv_forward: %s vectors must have %d elements" % (name, n))
-            _need(s, "conv_forward")
-            _need(b, "conv_forward")
-            keep += [s, b]
-            setattr(d, name + "_scale", s.data_ptr())
-            setattr(d, name + "_shift", b.data_ptr())
-    d.pre_relu, d.act = int(bool(pre_relu)), int(act)
-    if (y2d is None) == (y_nchw is None):
-        raise BtsHipError("conv_forward: give exactly one of y2d / y_nchw")
-    if y2d is not None:
-        ys, yc = _rows2d(y2d, "conv_forward")
-        if yc != c_out * n_bundles or y2d.shape[0] != B * H * W:
-            raise BtsHipError("conv_forward: bad output view")
-        d.y, d.y_pix_stride, d.y_nchw = y2d.data_ptr(), ys, 0
-        out = y2d
-        if y2_2d is not None:
-            y2s, y2c = _rows2d(y2_2d, "conv_forward")
-            if y2c != c_out * n_bundles or y2_2d.shape[0] != B * H * W:
-                raise BtsHipError("conv_forward: bad second output view")
-            d.y2, d.y2_pix_stride = y2_2d.data_ptr(), y2s
-        if res2d is not None:
-            rs, rc = _rows2d(res2d, "conv_forward")
-            if rc != c_out * n_bundles or res2d.shape[0] != B * H * W:
-                raise BtsHipError("conv_forward: bad residual view %s" % (tuple(res2d.shape),))
-            d.res, d.res_pix_stride = res2d.data_ptr(), rs
-    else:
-        if res2d is not None or n_bundles > 1:
-            raise BtsHipError("conv_forward: residual / bundled convolutions write NHWC only")
-        _need(y_nchw, "conv_forward")
-        if tuple(y_nchw.shape) != (B, c_out, H, W) or not y_nchw.is_contiguous():
-            raise BtsHipError("conv_forward: y_nchw must be contiguous [B,c_out,H,W]")
-        d.y, d.y_pix_stride, d.y_nchw = y_nchw.data_ptr(), 0, 1
-        out = y_nchw
-    if splitk_ws is not None:
-        _need(splitk_ws, "conv_forward")
-        if not splitk_ws.is_contiguous():
-            raise BtsHipError("conv_forward: splitk_ws must be contiguous")
-        d.splitk_ws, d.splitk_ws_floats = splitk_ws.data_ptr(), splitk_ws.numel()
-    if (_WINO and d.precision == 0 and ksize == 3 and stride == 1 and dil == 1 and pad == 1 and up == 1 and not subpixel
-            and n_bundles <= 1 and (c_in_ld - (4 if n_tail else 0)) % 32 == 0 and c_in_ld > 4 and y_nchw is None):
-        # Winograd-form weights for the fused F(2x2,3x3) kernel: made once per packed weight and kept on it
-        uw = getattr(w_packed, "_bts_wino", None)
-        seq = getattr(w_packed, "_bts_pack_seq", 0)        # bumped by train.WeightPacker whenever it refills this buffer in place
-        if uw is not None and getattr(w_packed, "_bts_wino_seq", 0) != seq:
-            pack_wino_weight(w_packed, c_in_ld, n_tail, c_out16=getattr(w_packed, "_bts_wino_c16", 0), out=uw)
-            w_packed._bts_wino_seq = seq
-        if uw is None:
-            # which channel tile the library will use for this layer (its own decision on the COMPLETE descriptor, asked
-            # once per weight: the two packings differ): 48 -> the 16x16x4 tile
-            d.w_wino = w_packed.data_ptr()
-            bm_, bn_, kind_ = C.c_int(0), C.c_int(0), C.c_int(0)
-            _lib.load_real().bts_conv_plan_f32(C.byref(d), C.byref(bm_), C.byref(bn_), C.byref(kind_))
-            # (bn is choose_tile's pure function of c_out, whatever kernel family this particular launch ends up on)
-            w_packed._bts_wino_c16 = d.c_out if bn_.value == 48 else 0
-            uw = pack_wino_weight(w_packed, c_in_ld, n_tail, c_out16=w_packed._bts_wino_c16)
-            w_packed._bts_wino, w_packed._bts_wino_seq = uw, seq
-        keep.append(uw)
-        d.w_wino = uw.data_ptr()
-    cin = c_in_real if c_in_real is not None else c_in_ld
-    npix_out = B * H * W
-    if n_bundles > 1:                                      # algorithmic FLOPs of the grouped conv are passed in c_in_real
-        c_out = c_out * n_bundles                          # (real input channels per OUTPUT channel = channels per group)
-    flops = 2.0 * npix_out * c_out * cin * flops_taps      # algorithmic: the reference's 3x3 on the upsampled map
-    if algo_flops is not None:
-        flops = float(algo_flops)
-    nbytes = 4.0 * (B * h_in * w_in * cin + npix_out * c_out + flops_taps * c_out * cin)
-    variant = "conv"
-    if _trace is not None:
-        bm, bn, kind = C.c_int(0), C.c_int(0), C.c_int(0)
-        _lib.load().bts_conv_plan_f32(C.byref(d), C.byref(bm), C.byref(bn), C.byref(kind))
-        lay = "nchw" if y_nchw is not None else "nhwc"
-        if (kind.value & 15) == 8:
-            variant = "conv_halo_emu_kernel<%d,k%d,bf16>" % (bn.value, 2 if subpixel else 3)
-        elif (kind.value & 15) == 7:
-            variant = "conv_fwd_kernel<%d,%d,%s%s,bf16>" % (bm.value, bn.value, lay, ",splitk" if kind.value & 16 else "")
-        elif (kind.value & 15) == 6:
-            variant = "conv_wino_kernel<%d>" % bn.value
-        elif (kind.value & 15) == 5:
-            variant = "conv_halo_emu_kernel<%d,k%d>" % (bn.value, 2 if subpixel else 3)
-        elif (kind.value & 15) == 4:
-            variant = "conv_stem_kernel<%d>" % bn.value
-        elif (kind.value & 15) == 3:
-            variant = "conv1x1_kernel<%d,%d>" % (bn.value, bm.value // 32)      # <BN, WM>: rows = 32 * WM, as rocprofv3 names it
-        elif kind.value & 15:
-            variant = "conv_halo_kernel<%d,k%d,%s%s%s%s>" % (bn.value, 2 if subpixel else 3, lay, ",tail" if (kind.value & 15) == 2 else "",
-                                                            ",w8" if kind.value & 32 else "", ",dil" if kind.value & 64 else "")
-        else:
-            variant = "conv_fwd_kernel<%d,%d,%s%s>" % (bm.value, bn.value, lay, ",splitk" if kind.value & 16 else "")
-    xflops = 2.0 * npix_out * c_out * (c_in_ld if n_bundles > 1 else cin) * taps
-    if _trace is not None and variant.startswith("conv_wino_kernel"):
-        # MFMA products the Winograd kernel ISSUES: 16 transform positions x 32 tiles x BN channels x c_in per workgroup
-        # (4 instead of 9 per output and input channel, plus the ragged 8x16-pixel tiles and the channels padded to BN)
-        bn_w = bn.value
-        nwg = B * ((H + 7) // 8) * ((W + 15) // 16) * ((c_out + bn_w - 1) // bn_w)
-        xflops = 2.0 * nwg * 16 * 32 * bn_w * c_in_ld
-    if _trace is not None:                                 # tap skipping (dilated ASPP branches): FLOPs really issued
-        issued, dense = C.c_long(0), C.c_long(0)
-        _lib.load().bts_conv_plan_ksteps_f32(C.byref(d), C.byref(issued), C.byref(dense))
-        if dense.value > 0:
-            xflops *= issued.value / dense.value
+    d, out, keep = _conv_describe(x2d, B, h_in, w_in, w_packed, c_out, ksize, dil, up, c_in_ld, pre, pre_relu, e1, act, e2,
+                                  y2d, y_nchw, stride, pad, y2_2d, subpixel, splitk_ws, res2d, n_bundles, tail_planes)
+    wsplit_t, uw_t = _conv_derived_weights(d, w_packed, keep)
+    trace = ("conv", 0.0, 0.0, None) if _trace is None else _conv_trace_accounting(d, c_in_real, algo_flops)
     tops = torch_ops()
     if tops is not None:
-        geom = [d.x_pix_stride, d.c_in_ld, d.k_pad, d.B, d.h_in, d.w_in, d.up, d.ksize, d.dil, d.stride, d.pad, d.c_out, d.c_out_pad,
-                d.pre_relu, d.act, d.y_pix_stride, d.y_nchw, d.subpixel, d.y2_pix_stride, d.res_pix_stride, d.n_bundles, d.precision,
-                d.fill_frames]
-        pre_s, pre_b = pre if pre is not None else (None, None)
-        e1_s, e1_b = e1 if e1 is not None else (None, None)
-        e2_s, e2_b = e2 if e2 is not None else (None, None)
-        uw_t = w_packed._bts_wino if d.w_wino else None
+        geom = [getattr(d, f) for f in _GEOM_FIELDS]
+        (pre_s, pre_b), (e1_s, e1_b), (e2_s, e2_b) = (p if p is not None else (None, None) for p in (pre, e1, e2))
         run = lambda: _op(lambda: tops.conv_fwd(x2d, w_packed, pre_s, pre_b, e1_s, e1_b, e2_s, e2_b, out, y2_2d, res2d, splitk_ws,
                                                 list(tail_planes) if tail_planes else [], wsplit_t, uw_t, geom))
     else:
         run = lambda: _lib.load().bts_conv_fwd_f32(C.byref(d), _stream(x2d))
     with torch.cuda.device(x2d.device):
-        rc = _launch(variant, tag, flops, nbytes, run, xflops=xflops)
+        rc = _launch(trace[0], tag, trace[1], trace[2], run, xflops=trace[3])
     _lib.check(rc, "bts_conv_fwd_f32")
     return out
 
@@ -874,8 +855,7 @@ def conv_wgrad(x2d: torch.Tensor, B: int, h_in: int, w_in: int, c_in: int, dy2d:
     ds, dc = _rows2d(dy2d, "conv_wgrad")
     if pad is None:
         pad = dil * (ksize // 2)
-    H = (h_in * up + 2 * pad - dil * (ksize - 1) - 1) // stride + 1
-    W = (w_in * up + 2 * pad - dil * (ksize - 1) - 1) // stride + 1
+    H, W = conv_out_hw(h_in, w_in, ksize, dil, stride, pad, up)
     if c_in % 4 or c_out % 4 or c_in * n_bundles > xc or c_out * n_bundles > dc:
         raise BtsHipError("conv_wgrad: c_in/c_out must be multiples of 4 within the views (%d/%d, %d/%d)" % (c_in, xc, c_out, dc))
     if x2d.shape[0] != B * h_in * w_in or dy2d.shape[0] != B * H * W:

@@ -237,8 +237,7 @@ class _ConvFn(torch.autograd.Function):
             raise BtsHipError("train.conv2d: weight %s (groups %d) does not fit input %s"
                               % (tuple(weight.shape), groups, tuple(x.shape)))
         x2d, c4 = _nhwc_rows(x.detach())
-        H = (h * up + 2 * padding - dilation * (k - 1) - 1) // stride + 1
-        W = (w * up + 2 * padding - dilation * (k - 1) - 1) // stride + 1
+        H, W = ops.conv_out_hw(h, w, k, dilation, stride, padding, up)
         y = torch.empty((B, H, W, cout), dtype=torch.float32, device=x.device)
         if act not in (ops.ACT_NONE, ops.ACT_ELU):
             raise BtsHipError("train.conv2d: only ELU can ride in the epilogue (its derivative is a function of y)")

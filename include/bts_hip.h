@@ -231,13 +231,22 @@ int bts_upconv_combine_f32(const float* taps, long taps_pix_stride, int B, int h
 
 /* Which kernel bts_conv_fwd_f32 will launch for this descriptor (host-side query, no GPU work: it walks the real
  * dispatch path): lets a profiler attribute a launch to its kernel instantiation.
- *   kind & 15: 0 = conv_fwd_kernel (row-tiled, BM x BN), 1 = conv_halo_kernel (spatial 128-pixel tile x BN),
- *              2 = conv_halo_kernel with the planar tail operand, 3 = conv1x1_kernel (bm = 128 or 64 pixels x BN),
- *              4 = conv_stem_kernel (7x7 / stride-2 encoder stem, 8x32-pixel tiles x BN),
- *              5 = conv_halo_emu_kernel (precision 1: bf16x3 halo tile), 6 = conv_wino_kernel (Winograd F(2x2,3x3)),
- *              7 = conv_fwd_kernel with bf16 operands (precision 2, row-tiled), 8 = conv_halo_emu_kernel with one bf16
- *              plane (precision 2, halo tile);
- *   kind & 16: split-K (+ splitk_reduce_kernel);  kind & 32: the eight-wave variant of the 48-wide halo tile (under-filled launches). */
+ *   *kind = one kernel family (kind & BTS_CONV_KIND_MASK) plus any of the BTS_CONV_FLAG_* bits. */
+enum {
+    BTS_CONV_KIND_ROW       = 0,   /* conv_fwd_kernel: row-tiled, BM x BN (precision 0 and 1)                          */
+    BTS_CONV_KIND_HALO      = 1,   /* conv_halo_kernel: spatial 128-pixel tile x BN                                    */
+    BTS_CONV_KIND_HALO_TAIL = 2,   /* conv_halo_kernel with the planar tail operand                                    */
+    BTS_CONV_KIND_WIDE_1X1  = 3,   /* conv1x1_kernel: bm = 128 or 64 pixels x BN                                       */
+    BTS_CONV_KIND_STEM      = 4,   /* conv_stem_kernel: 7x7 / stride-2 encoder stem, 8x32-pixel tiles x BN             */
+    BTS_CONV_KIND_HALO_EMU  = 5,   /* conv_halo_emu_kernel, precision 1: bf16x3 halo tile                              */
+    BTS_CONV_KIND_WINO      = 6,   /* conv_wino_kernel: Winograd F(2x2,3x3)                                            */
+    BTS_CONV_KIND_ROW_BF16  = 7,   /* conv_fwd_kernel with bf16 operands (precision 2, row-tiled)                      */
+    BTS_CONV_KIND_HALO_BF16 = 8,   /* conv_halo_emu_kernel with one bf16 plane (precision 2, halo tile)                */
+    BTS_CONV_KIND_MASK      = 15,
+    BTS_CONV_FLAG_SPLITK    = 16,  /* split-K (+ splitk_reduce_kernel); row-tiled families only                        */
+    BTS_CONV_FLAG_W8        = 32,  /* the eight-wave variant of the 48-wide halo tile (under-filled launches)          */
+    BTS_CONV_FLAG_DIL       = 64   /* the dilated halo tile (dilation 3 / 6 / 12 ASPP branches, c_out 128)             */
+};
 int bts_conv_plan_f32(const bts_conv_desc* desc, int* bm, int* bn, int* kind);
 
 /* Tap-steps the launch really issues vs. the dense count (host-side query, no GPU work).  The row-tiled kernel skips,

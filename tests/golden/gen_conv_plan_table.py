@@ -13,7 +13,6 @@ process, so run this with no BTS_* variable set.
     python tests/golden/gen_conv_plan_table.py --out F    # write F instead
 """
 import argparse
-import ctypes as C
 import hashlib
 import os
 import sys
@@ -23,6 +22,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 from bts_amd._lib import ConvDesc  # noqa: E402
+from bts_amd.conv_plan import FAMILY_MASK, Family as F, query  # noqa: E402
 
 TABLE = os.path.join(ROOT, "tests", "golden", "conv_plan_table.npz")
 
@@ -174,17 +174,10 @@ def grid():
 
 
 def run():
-    lib = C.CDLL(os.path.join(ROOT, "bts_amd", "libbts_hip.so"))
-    plan, ksteps = lib.bts_conv_plan_f32, lib.bts_conv_plan_ksteps_f32
-    plan.argtypes = [C.c_void_p] + [C.POINTER(C.c_int)] * 3
-    ksteps.argtypes = [C.c_void_p, C.POINTER(C.c_long), C.POINTER(C.c_long)]
-    bm, bn, kind, issued, dense = C.c_int(), C.c_int(), C.c_int(), C.c_long(), C.c_long()
     rows, keys = [], hashlib.sha256()
     for d, key in grid():
-        rc = plan(C.addressof(d), C.byref(bm), C.byref(bn), C.byref(kind))
-        rc2 = ksteps(C.addressof(d), C.byref(issued), C.byref(dense))
-        assert rc == rc2, key
-        rows.append((rc, bm.value, bn.value, kind.value, issued.value, dense.value))
+        p = query(d, ksteps=True)                     # (asserts that both queries return the same code)
+        rows.append((p.rc, p.bm, p.bn, p.kind, p.issued, p.dense))
         keys.update(np.asarray(key, np.int64).tobytes())
     t = np.asarray(rows, np.int64)
     return dict(rc=t[:, 0].astype(np.int32), bm=t[:, 1].astype(np.int16), bn=t[:, 2].astype(np.int16),
@@ -192,17 +185,17 @@ def run():
                 grid_sha256=np.frombuffer(keys.digest(), np.uint8))
 
 
-# every (kind & 15, bm, bn) the dispatch returns: 0 row-tiled (fp32 and bf16x3), 1 halo tile, 2 halo tile with planar
-# tail, 3 wide 1x1, 4 stem, 5 bf16x3 halo tile, 6 Winograd
-FAMILIES = {(0, 128, 128), (0, 64, 128), (0, 128, 64), (0, 64, 64), (0, 128, 48), (0, 64, 48), (0, 128, 32),
-            (1, 128, 128), (1, 128, 64), (1, 128, 48), (1, 128, 32), (2, 128, 128), (2, 128, 64), (2, 128, 32),
-            (3, 64, 192), (3, 128, 192), (4, 256, 96), (4, 256, 64), (5, 128, 128), (5, 128, 64),
-            (6, 128, 128), (6, 128, 64), (6, 128, 48)}
+# every (family, bm, bn) the dispatch returns (ROW: fp32 and bf16x3; the grid holds no precision-2 query)
+FAMILIES = {(F.ROW, 128, 128), (F.ROW, 64, 128), (F.ROW, 128, 64), (F.ROW, 64, 64), (F.ROW, 128, 48), (F.ROW, 64, 48), (F.ROW, 128, 32),
+            (F.HALO, 128, 128), (F.HALO, 128, 64), (F.HALO, 128, 48), (F.HALO, 128, 32),
+            (F.HALO_TAIL, 128, 128), (F.HALO_TAIL, 128, 64), (F.HALO_TAIL, 128, 32),
+            (F.WIDE_1X1, 64, 192), (F.WIDE_1X1, 128, 192), (F.STEM, 256, 96), (F.STEM, 256, 64),
+            (F.HALO_EMU, 128, 128), (F.HALO_EMU, 128, 64), (F.WINO, 128, 128), (F.WINO, 128, 64), (F.WINO, 128, 48)}
 
 
 def families(t):
     ok = t["rc"] == 0
-    return {(int(k) & 15, int(m), int(n)) for k, m, n in zip(t["kind"][ok], t["bm"][ok], t["bn"][ok])}
+    return {(int(k) & FAMILY_MASK, int(m), int(n)) for k, m, n in zip(t["kind"][ok], t["bm"][ok], t["bn"][ok])}
 
 
 def main():

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from bts_amd import synth
+from bts_amd.conv_plan import Family
 from parity_util import Params
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -212,24 +213,11 @@ def test_plan_op_layout_matches_header(tmp_path):
 def _ksteps(B, h, w, cin, cout, k, dil, pad, fill=0):
     """issued / dense tap-steps of a conv launch, through the library's host-side query (no GPU work; the pointers are
     never dereferenced)."""
-    import ctypes as C
-    from bts_amd import _lib
-    d = _lib.ConvDesc()
-    d.x = d.w = d.y = 0x1000
-    d.x_pix_stride = cin
-    d.c_in_ld = cin
-    d.k_pad = (k * k * cin + 31) // 32 * 32
-    d.B, d.h_in, d.w_in, d.up = B, h, w, 1
-    d.ksize, d.dil, d.stride, d.pad = k, dil, 1, pad
-    d.c_out, d.c_out_pad = cout, (cout + 31) // 32 * 32
-    d.y_pix_stride = cout
-    d.fill_frames = fill
-    issued, dense = C.c_long(-1), C.c_long(-1)
-    bm, bn, kind = C.c_int(0), C.c_int(0), C.c_int(0)
-    lib = _lib.load_real()
-    assert lib.bts_conv_plan_f32(C.byref(d), C.byref(bm), C.byref(bn), C.byref(kind)) == 0
-    assert lib.bts_conv_plan_ksteps_f32(C.byref(d), C.byref(issued), C.byref(dense)) == 0
-    return issued.value, dense.value, bm.value, kind.value
+    from bts_amd import conv_plan
+    p = conv_plan.query(conv_plan.geometry_desc(B, h, w, cin, cout, k, dil, pad=pad, fill_frames=fill, fake_pointers=True),
+                        ksteps=True)
+    assert p.rc == 0
+    return p.issued, p.dense, p.bm, p.kind
 
 
 @pytest.mark.parametrize("B,h,w,dil", [(2, 44, 152, 24), (2, 44, 152, 18), (1, 44, 152, 6), (3, 52, 68, 24), (1, 13, 17, 24), (2, 11, 19, 6), (1, 52, 68, 3)])      # (dilation 3 on 44x152 takes the dilated halo tile)
@@ -239,7 +227,7 @@ def test_tap_skipping_rule_is_a_superset_of_the_taps_a_tile_needs(B, h, w, dil):
     issued count must cover every (tile, tap) pair with at least one in-map read, and stay below the dense count
     where the dilation exceeds half the map."""
     issued, dense, bm, kind = _ksteps(B, h, w, 256, 128, 3, dil, dil)
-    assert kind == 0 and bm in (64, 128)                    # row-tiled kernel, no split-K
+    assert kind == Family.ROW and bm in (64, 128)           # row-tiled kernel, no split-K (no flag at all)
     M = B * h * w
     n_mt = (M + bm - 1) // bm
     assert dense == n_mt * 9
@@ -264,23 +252,13 @@ def test_tap_skipping_off_where_it_cannot_apply():
 
 # ------------------------------------------------------------------------------------------ dispatch vs declared fill (host side)
 def _plan(B, h, w, cin, cout, k, fill, ws_floats=1 << 28):
-    """(kernel kind, bm, bn) bts_conv_fwd_f32 would pick -- host-side query, pointers never dereferenced."""
-    import ctypes as C
-    from bts_amd import _lib
-    d = _lib.ConvDesc()
-    d.x = d.w = d.y = 0x1000
+    """(plan, bm, bn) bts_conv_fwd_f32 would pick -- host-side query, pointers never dereferenced."""
+    from bts_amd import conv_plan
+    d = conv_plan.geometry_desc(B, h, w, cin, cout, k, fill_frames=fill, fake_pointers=True)
     d.splitk_ws, d.splitk_ws_floats = 0x2000, ws_floats
-    d.x_pix_stride = cin
-    d.c_in_ld = cin
-    d.k_pad = (k * k * cin + 31) // 32 * 32
-    d.B, d.h_in, d.w_in, d.up = B, h, w, 1
-    d.ksize, d.dil, d.stride, d.pad = k, 1, 1, k // 2
-    d.c_out, d.c_out_pad = cout, (cout + 31) // 32 * 32
-    d.y_pix_stride = cout
-    d.fill_frames = fill
-    bm, bn, kind = C.c_int(0), C.c_int(0), C.c_int(0)
-    assert _lib.load_real().bts_conv_plan_f32(C.byref(d), C.byref(bm), C.byref(bn), C.byref(kind)) == 0
-    return kind.value, bm.value, bn.value
+    p = conv_plan.query(d)
+    assert p.rc == 0
+    return p, p.bm, p.bn
 
 
 def test_block3_kernel_choices_need_a_declaration_above_the_default():
@@ -290,20 +268,20 @@ def test_block3_kernel_choices_need_a_declaration_above_the_default():
     frame -- while a caller that declares 16 frames (bench.py at B=16) gets them.  Never a function of B."""
     for B in (1, 16):
         for fill in (0, 1, 2, 8):
-            kind, bm, bn = _plan(B, 22, 76, 1248, 192, 1, fill)
-            assert kind & 15 == 0, (B, fill, kind)                 # row-tiled kernel
-            kind, _, bn = _plan(B, 22, 76, 192, 48, 3, fill)
-            assert kind & 15 == 0 and kind & 16 and bn == 48, (B, fill, kind)      # row-tiled + split-K
-        kind, bm, bn = _plan(B, 22, 76, 1248, 192, 1, 16)
-        assert kind & 15 == 3 and (bm, bn) == (128, 192), (B, kind, bm, bn)       # wide 1x1, 128-row tile (K > 768)
-        kind, bm, bn = _plan(B, 22, 76, 432, 192, 1, 16)
-        assert kind & 15 == 3 and (bm, bn) == (64, 192)                             # K <= 768: 64-row tile
-        kind, _, bn = _plan(B, 22, 76, 192, 48, 3, 16)
-        assert kind & 15 == 1 and kind & 32 and not kind & 16 and bn == 48         # halo kernel, eight-wave 48-wide tile
+            p, bm, bn = _plan(B, 22, 76, 1248, 192, 1, fill)
+            assert p.family == Family.ROW, (B, fill, p)            # row-tiled kernel
+            p, _, bn = _plan(B, 22, 76, 192, 48, 3, fill)
+            assert p.family == Family.ROW and p.splitk and bn == 48, (B, fill, p)      # row-tiled + split-K
+        p, bm, bn = _plan(B, 22, 76, 1248, 192, 1, 16)
+        assert p.family == Family.WIDE_1X1 and (bm, bn) == (128, 192), (B, p)          # wide 1x1, 128-row tile (K > 768)
+        p, bm, bn = _plan(B, 22, 76, 432, 192, 1, 16)
+        assert p.family == Family.WIDE_1X1 and (bm, bn) == (64, 192)                   # K <= 768: 64-row tile
+        p, _, bn = _plan(B, 22, 76, 192, 48, 3, 16)
+        assert p.family == Family.HALO and p.w8 and not p.splitk and bn == 48          # halo kernel, eight-wave 48-wide tile
     # blocks 1-2 fill the chip at any declaration: wide 1x1 / halo kernels whatever the fill
     for fill in (0, 1, 16):
-        assert _plan(1, 88, 304, 240, 192, 1, fill)[0] & 15 == 3
-        assert _plan(1, 88, 304, 192, 48, 3, fill)[0] & 15 == 1
+        assert _plan(1, 88, 304, 240, 192, 1, fill)[0].family == Family.WIDE_1X1
+        assert _plan(1, 88, 304, 192, 48, 3, fill)[0].family == Family.HALO
 
 
 def test_launch_config_is_a_thread_local_scope():
@@ -384,23 +362,13 @@ def test_winograd_is_chosen_by_per_frame_geometry_only(h, w, cout, expect_wino):
     least 0.70 of its 8x16-pixel tile grid (44x152: 0.87, the NYU decoder's 52x68: 0.79; 26x34: 0.58 and 11x38: 0.54 stay on
     the direct kernels) -- and the answer is the same for every batch size (a frame's bits may not depend on its
     neighbours).  Host-side query: no GPU work, the pointers are never dereferenced."""
-    import ctypes as C
-    from bts_amd import _lib
-    lib = _lib.load_real()
+    from bts_amd import conv_plan
     kinds = set()
     for B in (1, 4, 16):
-        d = _lib.ConvDesc()
-        d.x = d.w = d.y = d.w_wino = 0x1000
-        cin = 192
-        d.x_pix_stride = d.c_in_ld = cin
-        d.k_pad = 9 * cin
-        d.B, d.h_in, d.w_in, d.up = B, h, w, 1
-        d.ksize, d.dil, d.stride, d.pad = 3, 1, 1, 1
-        d.c_out, d.c_out_pad = cout, (cout + 31) // 32 * 32
-        d.y_pix_stride = cout
-        d.fill_frames = 16
-        bm, bn, kind = C.c_int(0), C.c_int(0), C.c_int(0)
-        assert lib.bts_conv_plan_f32(C.byref(d), C.byref(bm), C.byref(bn), C.byref(kind)) == 0
-        kinds.add(kind.value & 15)
+        d = conv_plan.geometry_desc(B, h, w, 192, cout, 3, fill_frames=16, fake_pointers=True)
+        d.w_wino = 0x1000
+        p = conv_plan.query(d)
+        assert p.rc == 0
+        kinds.add(p.family)
     assert len(kinds) == 1, kinds
-    assert (kinds == {6}) == expect_wino, kinds
+    assert (kinds == {Family.WINO}) == expect_wino, kinds
