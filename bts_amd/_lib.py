@@ -19,9 +19,10 @@ SYMBOLS = (
     "bts_conv_wgrad_f32", "bts_bn_train_ws_floats", "bts_bn_train_stats_f32", "bts_bn_apply_nhwc_f32", "bts_bn_train_bwd_f32",
     "bts_pack_weights_blocks", "bts_pack_weights_f32", "bts_pack_wino_floats", "bts_pack_wino_f32", "bts_eval_ws_doubles", "bts_eval_depth_metrics_f32",
     "bts_reduc_lpg_fwd_f32", "bts_plan_run", "bts_upconv_combine_f32",
+    "bts_depth_loss_ws_doubles", "bts_depth_loss_fwd_f32", "bts_depth_loss_bwd_f32",
 )
 
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 
 class ConvDesc(C.Structure):
@@ -175,6 +176,12 @@ def load_real():
     lib.bts_eval_ws_doubles.argtypes = [i, i, i]
     lib.bts_eval_depth_metrics_f32.restype = i
     lib.bts_eval_depth_metrics_f32.argtypes = [vp, i, i, i, vp, i, i, i, i, f, f, i, i, i, i, vp, l, vp, vp, vp]
+    lib.bts_depth_loss_ws_doubles.restype = l
+    lib.bts_depth_loss_ws_doubles.argtypes = [l]
+    lib.bts_depth_loss_fwd_f32.restype = i
+    lib.bts_depth_loss_fwd_f32.argtypes = [vp, vp, vp, f, l, i, f, vp, l, vp, vp, vp]
+    lib.bts_depth_loss_bwd_f32.restype = i
+    lib.bts_depth_loss_bwd_f32.argtypes = [vp, vp, vp, f, l, i, f, vp, vp, vp, vp]
     if lib.bts_hip_abi_version() != ABI_VERSION:
         raise BtsHipError("bts_amd: ABI version mismatch (%d != %d)" % (lib.bts_hip_abi_version(), ABI_VERSION))
     _lib = lib

@@ -53,14 +53,33 @@ def weights_init_xavier(m):
             torch.nn.init.zeros_(m.bias)
 
 
-class silog_loss(nn.Module):
-    """Scale-invariant log loss, same value as reference bts.py:41-48 (plain torch; training callers only)."""
+def _native_loss(module, kind, param, depth_est, depth_gt, mask, gt_min):
+    """The native path of both criteria: ops.depth_loss (csrc/loss.hip), statistics kept on the module."""
+    if mask is None and gt_min is None:
+        raise BtsHipError("%s(native=True): give a mask, or mask=None together with gt_min" % type(module).__name__)
+    loss, module.last_stats = ops.depth_loss(depth_est, depth_gt, mask, 1.0 if gt_min is None else gt_min, kind, param,
+                                             return_stats=True)
+    return loss
 
-    def __init__(self, variance_focus):
+
+class silog_loss(nn.Module):
+    """Scale-invariant log loss, same value as reference bts.py:41-48 (plain torch; training callers only).
+
+    ``native=True`` runs the same formula on the HIP loss kernels instead (``ops.depth_loss``): no boolean gather, so the
+    step does not wait for the device; fp64 sums in a fixed order; ``forward(depth_est, depth_gt, None, gt_min=1.0)`` takes
+    the validity rule ``depth_gt > gt_min`` in place of a mask tensor.  After a native forward ``last_stats`` holds the
+    [4] fp64 device tensor (valid count, mean log error, its second moment, loss) for logging code to read later.  No
+    valid pixel, or a variance <= 0, gives loss 0 with a zero gradient where torch gives NaN.  CUDA tensors only."""
+
+    def __init__(self, variance_focus, native=False):
         super().__init__()
         self.variance_focus = variance_focus
+        self.native = bool(native)
+        self.last_stats = None
 
-    def forward(self, depth_est, depth_gt, mask):
+    def forward(self, depth_est, depth_gt, mask, gt_min=None):
+        if self.native:
+            return _native_loss(self, "silog", self.variance_focus, depth_est, depth_gt, mask, gt_min)
         log_ratio = depth_est[mask].log() - depth_gt[mask].log()
         second_moment, first_moment = log_ratio.pow(2).mean(), log_ratio.mean()
         return 10.0 * torch.sqrt(second_moment - self.variance_focus * first_moment * first_moment)
@@ -68,13 +87,18 @@ class silog_loss(nn.Module):
 
 class depth_l1_loss(nn.Module):
     """Asymmetric L1 depth loss, same value as reference bts.py:50-63: over-estimates are weighted by
-    ``inbalance_to_closer``; the mean runs over ALL masked pixels."""
+    ``inbalance_to_closer``; the mean runs over ALL masked pixels.  ``native=True``: as for ``silog_loss``
+    (``last_stats``: valid count, 0, 0, loss)."""
 
-    def __init__(self, inbalance_to_closer):
+    def __init__(self, inbalance_to_closer, native=False):
         super().__init__()
         self.inbalance_to_closer = inbalance_to_closer
+        self.native = bool(native)
+        self.last_stats = None
 
-    def forward(self, depth_est, depth_gt, mask):
+    def forward(self, depth_est, depth_gt, mask, gt_min=None):
+        if self.native:
+            return _native_loss(self, "l1", self.inbalance_to_closer, depth_est, depth_gt, mask, gt_min)
         err = depth_est[mask] - depth_gt[mask]
         if self.inbalance_to_closer == 1:
             return err.abs().mean()

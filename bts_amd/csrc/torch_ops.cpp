@@ -9,7 +9,8 @@
 //   * hands raw device pointers and dims to the extern "C" entry point -- no torch type crosses that line.
 // Built with g++ only (no device code): `make -C bts_amd/csrc torch` -> bts_amd/libbts_torch.so, loaded by
 // bts_amd/_lib.py with torch.ops.load_library.  Autograd for `bts_hip::lpg` is registered in bts_amd/ops.py
-// (torch.library.register_autograd) on top of `bts_hip::lpg_backward`.
+// (torch.library.register_autograd) on top of `bts_hip::lpg_backward`, and for `bts_hip::depth_loss` on top of
+// `bts_hip::depth_loss_backward`.
 #include <ATen/ATen.h>
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>      // PyTorch-ROCm tensors carry the device type "cuda": its guard / stream
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>         // accessors are the *MasqueradingAsCUDA forms
@@ -238,6 +239,60 @@ void conv_fwd(const Tensor& x, const Tensor& w, OptTensor pre_scale, OptTensor p
     check_rc(bts_conv_fwd_f32(&d, current_stream()), op);
 }
 
+// ------------------------------------------------------------------------------------------------------ training losses
+// silog_loss / depth_l1_loss (pytorch/bts.py:41-63) over the valid pixels of the whole batch, csrc/loss.hip: no boolean gather, no host
+// sync.  kind 0 = silog (param = variance_focus), 1 = asymmetric L1 (param = inbalance_to_closer); mask bool / uint8 or None (gt > gt_min).
+const unsigned char* depth_loss_checks(const char* op, const Tensor& est, const Tensor& gt, const OptTensor& mask, int64_t kind) {
+    need_f32_cuda(est, op, "est");
+    need_f32_cuda(gt, op, "gt");
+    same_device(est, gt, op, "gt");
+    TORCH_CHECK(est.sizes() == gt.sizes(), op, ": est ", est.sizes(), " and gt ", gt.sizes(), " must have the same shape");
+    TORCH_CHECK(est.numel() > 0, op, ": empty depth map");
+    TORCH_CHECK(est.is_contiguous() && gt.is_contiguous(), op, ": est and gt must be contiguous");
+    TORCH_CHECK(kind == 0 || kind == 1, op, ": kind must be 0 (silog) or 1 (L1), got ", kind);
+    if (!(mask.has_value() && mask->defined())) return nullptr;
+    TORCH_CHECK(mask->is_cuda(), op, ": mask must be a CUDA(ROCm) tensor (no CPU fallback)");
+    TORCH_CHECK(mask->scalar_type() == at::kBool || mask->scalar_type() == at::kByte, op, ": mask must be bool or uint8, got ", mask->scalar_type());
+    same_device(est, *mask, op, "mask");
+    TORCH_CHECK(mask->sizes() == est.sizes(), op, ": mask ", mask->sizes(), " and est ", est.sizes(), " must have the same shape");
+    TORCH_CHECK(mask->is_contiguous(), op, ": mask must be contiguous");
+    return static_cast<const unsigned char*>(mask->data_ptr());
+}
+
+// returns (loss 0-d fp32, stats [4] fp64: valid count, mean d, mean d^2 (0, 0 for L1), loss)
+std::tuple<Tensor, Tensor> depth_loss(const Tensor& est, const Tensor& gt, const OptTensor& mask, double gt_min, int64_t kind, double param) {
+    const char* op = "bts_hip::depth_loss";
+    const unsigned char* m = depth_loss_checks(op, est, gt, mask, kind);
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(est.device());
+    const long npix = (long)est.numel(), nws = bts_depth_loss_ws_doubles(npix);
+    Tensor ws = at::empty({nws}, est.options().dtype(at::kDouble));
+    Tensor stats = at::empty({4}, est.options().dtype(at::kDouble));
+    Tensor loss = at::empty({}, est.options());
+    check_rc(bts_depth_loss_fwd_f32(est.data_ptr<float>(), gt.data_ptr<float>(), m, (float)gt_min, npix, (int)kind, (float)param,
+                                    ws.data_ptr<double>(), nws, stats.data_ptr<double>(), loss.data_ptr<float>(), current_stream()), op);
+    return {loss, stats};
+}
+
+// d loss / d est scaled by the DEVICE scalar grad_loss; 0 at invalid pixels
+Tensor depth_loss_backward(const Tensor& est, const Tensor& gt, const OptTensor& mask, double gt_min, int64_t kind, double param,
+                           const Tensor& stats, const Tensor& grad_loss) {
+    const char* op = "bts_hip::depth_loss_backward";
+    const unsigned char* m = depth_loss_checks(op, est, gt, mask, kind);
+    need_f32_cuda(grad_loss, op, "grad_loss");
+    same_device(est, grad_loss, op, "grad_loss");
+    same_device(est, stats, op, "stats");
+    TORCH_CHECK(grad_loss.numel() == 1, op, ": grad_loss must hold one float, got ", grad_loss.sizes());
+    TORCH_CHECK(stats.is_cuda() && stats.scalar_type() == at::kDouble && stats.is_contiguous() && stats.numel() == 4, op,
+                ": stats must be the contiguous float64 [4] tensor the forward returned");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(est.device());
+    // the gradient starts at est's offset from a 16-byte line, so that the kernel can store 16 bytes per lane next to its loads
+    const int64_t off = (reinterpret_cast<uintptr_t>(est.data_ptr()) & 15) >> 2;
+    Tensor g = at::empty({est.numel() + off}, est.options()).narrow(0, off, est.numel()).view(est.sizes());
+    check_rc(bts_depth_loss_bwd_f32(est.data_ptr<float>(), gt.data_ptr<float>(), m, (float)gt_min, (long)est.numel(), (int)kind, (float)param,
+                                    stats.data_ptr<double>(), grad_loss.data_ptr<float>(), g.data_ptr<float>(), current_stream()), op);
+    return g;
+}
+
 }  // namespace
 
 TORCH_LIBRARY(bts_hip, m) {
@@ -249,6 +304,8 @@ TORCH_LIBRARY(bts_hip, m) {
     m.def("conv_fwd(Tensor x, Tensor w, Tensor? pre_scale, Tensor? pre_shift, Tensor? e1_scale, Tensor? e1_shift, Tensor? e2_scale, "
           "Tensor? e2_shift, Tensor(a!) y, Tensor(b!)? y2, Tensor? res, Tensor(c!)? splitk_ws, Tensor[] tail_planes, Tensor? w_split, "
           "Tensor? w_wino, int[] geom) -> ()");
+    m.def("depth_loss(Tensor est, Tensor gt, Tensor? mask, float gt_min, int kind, float param) -> (Tensor loss, Tensor stats)");
+    m.def("depth_loss_backward(Tensor est, Tensor gt, Tensor? mask, float gt_min, int kind, float param, Tensor stats, Tensor grad_loss) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(bts_hip, CUDA, m) {
@@ -257,4 +314,6 @@ TORCH_LIBRARY_IMPL(bts_hip, CUDA, m) {
     m.impl("reduction_1x1", &reduction_1x1);
     m.impl("reduc_lpg", &reduc_lpg);
     m.impl("conv_fwd", &conv_fwd);
+    m.impl("depth_loss", &depth_loss);
+    m.impl("depth_loss_backward", &depth_loss_backward);
 }

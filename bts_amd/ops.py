@@ -116,6 +116,17 @@ def torch_ops():
             return t.lpg_backward(ctx.saved_tensors[0], grad_depth.contiguous(), ctx.upratio), None
 
         torch.library.register_autograd("bts_hip::lpg", _backward, setup_context=_setup)
+
+        def _loss_setup(ctx, inputs, output):
+            est, gt, mask, ctx.gt_min, ctx.kind, ctx.param = inputs
+            ctx.save_for_backward(est, gt, mask, output[1])
+
+        def _loss_backward(ctx, grad_loss, grad_stats):
+            est, gt, mask, stats = ctx.saved_tensors
+            g = t.depth_loss_backward(est, gt, mask, ctx.gt_min, ctx.kind, ctx.param, stats, grad_loss.contiguous())
+            return g, None, None, None, None, None
+
+        torch.library.register_autograd("bts_hip::depth_loss", _loss_backward, setup_context=_loss_setup)
     return t
 
 
@@ -185,6 +196,91 @@ class LpgFunction(torch.autograd.Function):
     def backward(ctx, grad_depth):
         (plane_eq,) = ctx.saved_tensors
         return lpg_backward(plane_eq, grad_depth, ctx.upratio), None, None
+
+
+# ------------------------------------------------------------------------------ training losses
+_LOSS_KINDS = {"silog": 0, "l1": 1, 0: 0, 1: 1}
+
+
+def _depth_loss_fwd(est, gt, mask, gt_min, kind, param):
+    """ctypes binding of bts_depth_loss_fwd_f32 on checked, contiguous tensors: (loss 0-d fp32, stats [4] fp64)."""
+    lib = _lib.load()
+    npix = est.numel()
+    nws = lib.bts_depth_loss_ws_doubles(npix)
+    ws = torch.empty(nws, dtype=torch.float64, device=est.device)
+    stats = torch.empty(4, dtype=torch.float64, device=est.device)
+    loss = torch.empty((), dtype=torch.float32, device=est.device)
+    with torch.cuda.device(est.device):
+        rc = lib.bts_depth_loss_fwd_f32(_ptr(est), _ptr(gt), _ptr(mask), gt_min, npix, kind, param, _ptr(ws), nws, _ptr(stats),
+                                        _ptr(loss), _stream(est))
+    _lib.check(rc, "bts_depth_loss_fwd_f32")
+    return loss, stats
+
+
+def _depth_loss_bwd(est, gt, mask, gt_min, kind, param, stats, grad_loss):
+    # the gradient starts at est's offset from a 16-byte line, so that the kernel can store 16 bytes per lane next to its loads
+    off = (est.data_ptr() & 15) >> 2
+    g = torch.empty(est.numel() + off, dtype=torch.float32, device=est.device)[off:].view(est.shape)
+    with torch.cuda.device(est.device):
+        rc = _lib.load().bts_depth_loss_bwd_f32(_ptr(est), _ptr(gt), _ptr(mask), gt_min, est.numel(), kind, param, _ptr(stats),
+                                                _ptr(grad_loss), _ptr(g), _stream(est))
+    _lib.check(rc, "bts_depth_loss_bwd_f32")
+    return g
+
+
+class DepthLossFunction(torch.autograd.Function):
+    """autograd shell over the two native loss kernels for the ctypes binding (the torch binding registers the same
+    pair on bts_hip::depth_loss).  The upstream gradient stays on the device: the backward kernel reads it there."""
+
+    @staticmethod
+    def forward(ctx, est, gt, mask, gt_min, kind, param):
+        loss, stats = _depth_loss_fwd(est, gt, mask, gt_min, kind, param)
+        ctx.save_for_backward(est, gt, mask, stats)
+        ctx.cfg = (gt_min, kind, param)
+        ctx.mark_non_differentiable(stats)
+        return loss, stats
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_loss, grad_stats):
+        est, gt, mask, stats = ctx.saved_tensors
+        gt_min, kind, param = ctx.cfg
+        g = _depth_loss_bwd(est, gt, mask, gt_min, kind, param, stats, grad_loss.to(torch.float32).contiguous())
+        return g, None, None, None, None, None
+
+
+def depth_loss(est: torch.Tensor, gt: torch.Tensor, mask: Optional[torch.Tensor] = None, gt_min: float = 1.0,
+               kind="silog", param: float = 0.85, return_stats: bool = False):
+    """silog_loss / depth_l1_loss of the reference (bts.py:41-63) over the valid pixels of the whole batch, on the native
+    kernels of csrc/loss.hip: no boolean gather, so nothing waits for the host; fp64 sums in a fixed order.
+
+    ``kind``: "silog" (``param`` = variance_focus) or "l1" (``param`` = inbalance_to_closer).  A pixel is valid where
+    ``mask`` (bool / uint8, est's shape) is set, or -- ``mask=None`` -- where ``gt > gt_min``.  Differentiable in ``est``
+    (``gt`` and ``mask`` get no gradient).  Returns the 0-dim fp32 loss; with ``return_stats`` also the [4] fp64 device
+    tensor (valid count, mean log error, its second moment, loss).  No valid pixel, or a silog variance <= 0: loss 0 and
+    a zero gradient (torch gives NaN there)."""
+    _need(est, "depth_loss")
+    _need(gt, "depth_loss")
+    if kind not in _LOSS_KINDS:
+        raise BtsHipError("depth_loss: kind must be 'silog' or 'l1', got %r" % (kind,))
+    if est.shape != gt.shape or est.device != gt.device or est.numel() == 0:
+        raise BtsHipError("depth_loss: est %s and gt %s must be non-empty maps of one shape on one device" % (tuple(est.shape), tuple(gt.shape)))
+    if mask is not None:
+        if not isinstance(mask, torch.Tensor) or not mask.is_cuda or mask.dtype not in (torch.bool, torch.uint8):
+            raise BtsHipError("depth_loss: mask must be a CUDA/ROCm bool or uint8 tensor (or None: gt > gt_min)")
+        if mask.shape != est.shape or mask.device != est.device:
+            raise BtsHipError("depth_loss: mask %s must have est's shape %s and device" % (tuple(mask.shape), tuple(est.shape)))
+        mask = mask.contiguous()
+    est_c, gt_c = est.contiguous(), gt.detach().contiguous()     # autograd carries the gradient back into est's own layout
+    args = (est_c, gt_c, mask, float(gt_min), _LOSS_KINDS[kind], float(param))
+    tops = torch_ops()
+    if tops is not None:
+        box = []
+        _op(lambda: box.append(tops.depth_loss(*args)))
+        loss, stats = box[0]
+    else:
+        loss, stats = DepthLossFunction.apply(*args)
+    return (loss, stats.detach()) if return_stats else loss
 
 
 def lpg_fused_forward(plane4: torch.Tensor, B: int, h: int, w: int, upratio: int, max_depth: float,

@@ -80,9 +80,13 @@ def train_step(model, optimizer, criterion, image, focal, depth_gt, mask: Option
     backward, learning-rate update, optimiser step.  Returns (loss, the model's 6 outputs)."""
     optimizer.zero_grad(set_to_none=True)
     outs = model(image, focal)
-    if mask is None:
-        mask = gt_mask(depth_gt, dataset)
-    loss = criterion(outs[4], depth_gt, mask.to(torch.bool))
+    if mask is None and getattr(criterion, "native", False):
+        # the native criterion applies the validity rule itself (depth_gt > gt_min): no mask tensor is built
+        loss = criterion(outs[4], depth_gt, None, gt_min=1.0 if dataset == 'kitti' else 0.1)
+    else:
+        if mask is None:
+            mask = gt_mask(depth_gt, dataset)
+        loss = criterion(outs[4], depth_gt, mask.to(torch.bool))
     loss.backward()
     if lr is not None:
         for group in optimizer.param_groups:

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define BTS_HIP_ABI_VERSION 14
+#define BTS_HIP_ABI_VERSION 15
 
 #define BTS_ERR_INVALID      (-1)   /* bad argument (null pointer, non-positive dim, misalignment) */
 #define BTS_ERR_UNSUPPORTED  (-2)   /* valid in the reference but not built here (e.g. odd upratio)  */
@@ -406,6 +406,37 @@ int bts_eval_depth_metrics_f32(const float* pred, int B, int Hp, int Wp, const f
                                int top, int left, float min_depth_eval, float max_depth_eval,
                                int y0, int y1, int x0, int x1, double* ws, long ws_doubles,
                                double* per_frame, double* accum, bts_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Training losses: silog_loss.forward (pytorch/bts.py:41-48) and depth_l1_loss.forward
+ * (pytorch/bts.py:50-63) on the valid pixels of the whole batch, as the training step uses them
+ * (pytorch/bts_main.py:551-565), and their gradient w.r.t. the estimate.  No boolean gather: nothing waits for the host
+ * and no shape depends on the data.
+ *
+ *   est, gt  : [npix] fp32, npix = B*H*W, any 4-byte aligned address (16 bytes per lane are loaded where est, gt and mask
+ *              share their offset to a 16-byte / 4-byte boundary, one element per lane otherwise)
+ *   mask     : [npix] bytes, valid where != 0 (torch.bool or uint8), or NULL: valid where gt > gt_min (bts_main.py:551-553:
+ *              1.0 for KITTI, 0.1 for NYU).  est / gt at invalid pixels are never used (0, negative, inf, NaN are fine).
+ *   kind     : 0 = silog, d = log est - log gt, loss = 10 sqrt(E[d^2] - param E[d]^2), param = variance_focus;
+ *              1 = L1, e = est - gt, loss = E[e > 0 ? param e : -e] (E|e| when param == 1), param = inbalance_to_closer.
+ *   ws       : scratch of the size query's answer, in doubles (8-byte aligned)
+ *   stats    : [4] doubles <- valid count n, E[d], E[d^2] (0, 0 for L1), loss; the backward call reads them
+ *   loss     : one fp32 <- the loss
+ *   grad_loss: one fp32 ON THE DEVICE, the upstream gradient;  grad_est : [npix] fp32 <- d loss / d est, 0 at invalid pixels
+ * Sums are fp64 in a fixed order (no atomics, block count a function of npix): bit-reproducible; rounded to fp32 once.
+ * Deliberate deviations (torch gives NaN / inf): n == 0 -> loss 0, gradient 0;  silog with E[d^2] - param E[d]^2 <= 0 ->
+ * loss 0, gradient 0.  A NaN or non-positive est at a VALID pixel propagates as IEEE log does, as in torch.
+ * All argument checks (BTS_ERR_INVALID: null required pointer, npix <= 0, kind outside {0,1}, ws_doubles below the
+ * query, ws / stats not 8-byte aligned, est / gt / grad_est / loss / grad_loss not 4-byte aligned) come before any HIP call.
+ */
+long bts_depth_loss_ws_doubles(long npix);
+int bts_depth_loss_fwd_f32(const float* est, const float* gt, const unsigned char* mask /*NULL: gt > gt_min*/,
+                           float gt_min, long npix, int kind, float param /*variance_focus | inbalance_to_closer*/,
+                           double* ws, long ws_doubles, double* stats /*[4]: n, mean d, mean d^2 (0,0 for L1), loss*/,
+                           float* loss, bts_stream_t stream);
+int bts_depth_loss_bwd_f32(const float* est, const float* gt, const unsigned char* mask, float gt_min, long npix,
+                           int kind, float param, const double* stats, const float* grad_loss, float* grad_est,
+                           bts_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * One-call execution of a recorded forward ("plan").  A BtsModel forward is a fixed sequence of ~120 (B=1) to ~460

@@ -32,6 +32,7 @@ def main():
     ap.add_argument("--trace", action="store_true")
     ap.add_argument("--decoder-only", action="store_true")
     ap.add_argument("--no-freeze", action="store_true", help="train every encoder parameter (the reference freezes some)")
+    ap.add_argument("--native-loss", action="store_true", help="silog on the HIP loss kernels (no host sync) instead of torch")
     a = ap.parse_args()
     # BASELINE config 5 (B=32 over 8 GPUs = 4 per GPU, DDP): launch with
     #   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 scripts/train_bench.py
@@ -52,7 +53,7 @@ def main():
     torch.manual_seed(0)
     params = Params(a.encoder, 512, 80.0, "kitti")
     model = M.BtsModel(params).train().to(dev)
-    loss_fn = M.silog_loss(0.85)
+    loss_fn = M.silog_loss(0.85, native=a.native_loss)
     if not a.no_freeze:
         trainer.set_misc(model, a.encoder)          # the reference freezes the stem conv and the encoder norm affines
     opt = trainer.make_optimizer(model, 1e-4, 1e-2, 1e-3)
@@ -97,6 +98,7 @@ def main():
         ms = tmax.item()
     res = dict(metric="training step ms (fwd+loss+bwd+AdamW)", ms_per_step=ms, frames_per_s=world * B / ms * 1e3,
                n_gpus=world, ddp=use_dist,
+               loss="silog native (HIP)" if a.native_loss else "silog torch",
                config=dict(encoder=a.encoder, batch_per_gpu=B, height=H, width=W, decoder_only=a.decoder_only),
                peak_mem_gb=torch.cuda.max_memory_allocated() / 2**30)
     if a.trace:
