@@ -217,15 +217,13 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
     }
 }
 
+// `a` and `split` come from prepare_wgrad: a.pix_per_split and the split count are final here.
 template <int BM, int BN, int WM, int WN>
 int launch_wgrad(WgradArgs a, long split, float* dw, float* ws, hipStream_t s) {
     const int m_tiles = (a.c_out + BM - 1) / BM;
     a.n_ntiles = (a.N + BN - 1) / BN;
     const long tiles = (long)m_tiles * a.n_ntiles;
     const long per = (long)a.c_out * a.N * a.n_bundles;
-    long pps = (((long)a.M + split - 1) / split + WBK - 1) / WBK * WBK;
-    split = ((long)a.M + pps - 1) / pps;                         // no empty splits
-    a.pix_per_split = (unsigned)pps;
     a.out = split > 1 ? ws : dw;
     const size_t lds_bytes = (size_t)2 * WBK * (BM + BN) * sizeof(float);
     auto kern = conv_wgrad_kernel<BM, BN, WM, WN>;
@@ -246,9 +244,11 @@ int launch_wgrad(WgradArgs a, long split, float* dw, float* ws, hipStream_t s) {
 //   x  operand bytes / (operand bytes + partial-tile bytes)
 // with the split chosen to reach ~768 workgroups within [>= 4 K-steps per split, <= 1024 splits, workspace size].
 struct WgradPlan { int variant; long split; };
+constexpr int WGRAD_BM[4] = {128, 64, 32, 64}, WGRAD_BN[4] = {128, 128, 128, 64};   // tile of WgradPlan::variant
 
 inline WgradPlan plan_wgrad(int c_out, int N, long M, long ws_floats, bool have_ws, int n_bundles) {
-    static const int bm[4] = {128, 64, 32, 64}, bn[4] = {128, 128, 128, 64};
+    const int* bm = WGRAD_BM;
+    const int* bn = WGRAD_BN;
     static const double eff[4] = {1.0, 0.9, 0.75, 0.8};
     constexpr long target = 768;                                       // workgroups a split aims for (see above)
     const long per = (long)c_out * N * n_bundles;
@@ -275,9 +275,10 @@ inline WgradPlan plan_wgrad(int c_out, int N, long M, long ws_floats, bool have_
     return best;
 }
 
-}  // namespace
-
-extern "C" int bts_conv_wgrad_f32(const bts_conv_wgrad_desc* d, bts_stream_t stream) {
+// Everything bts_conv_wgrad_f32 decides on the host, shared with the plan query (no GPU work): validates the
+// descriptor, fills the kernel arguments (a.out / a.n_ntiles are the launch's), picks the tile and settles the split.
+// Returns 0 or a BTS_ERR_* code.
+int prepare_wgrad(const bts_conv_wgrad_desc* d, WgradArgs& a, WgradPlan& p) {
     if (!d || !d->x || !d->dy || !d->dw) return BTS_ERR_INVALID;
     if (d->B <= 0 || d->h_in <= 0 || d->w_in <= 0 || d->c_in <= 0 || d->c_out <= 0) return BTS_ERR_INVALID;
     if (d->up != 1 && d->up != 2) return BTS_ERR_UNSUPPORTED;
@@ -289,7 +290,6 @@ extern "C" int bts_conv_wgrad_f32(const bts_conv_wgrad_desc* d, bts_stream_t str
     if ((d->dy_pix_stride & 3) || d->dy_pix_stride < d->c_out) return BTS_ERR_INVALID;
     if (((uintptr_t)d->x & 15) || ((uintptr_t)d->dy & 15) || ((uintptr_t)d->dw & 15)) return BTS_ERR_INVALID;
     if (d->ws && (((uintptr_t)d->ws & 15) || d->ws_floats < 0)) return BTS_ERR_INVALID;
-    WgradArgs a;
     a.x = d->x; a.dy = d->dy; a.out = d->dw;
     a.x_pix_stride = d->x_pix_stride; a.dy_pix_stride = d->dy_pix_stride;
     a.c_in = d->c_in; a.c_out = d->c_out;
@@ -306,19 +306,42 @@ extern "C" int bts_conv_wgrad_f32(const bts_conv_wgrad_desc* d, bts_stream_t str
     a.M = (unsigned)mpix;
     a.N = d->ksize * d->ksize * d->c_in;
     a.pix_per_split = 0; a.n_ntiles = 0;
-    hipStream_t s = (hipStream_t)stream;
     a.pre_scale = d->pre_scale; a.pre_shift = d->pre_shift; a.pre_relu = d->pre_relu;
     if (d->pre_scale && (!d->pre_shift || ((uintptr_t)d->pre_scale & 15) || ((uintptr_t)d->pre_shift & 15))) return BTS_ERR_INVALID;
     a.n_bundles = d->n_bundles > 1 ? d->n_bundles : 1;
     if (d->n_bundles < 0 || a.n_bundles > 65535) return BTS_ERR_INVALID;
     if (d->x_pix_stride < (long)a.n_bundles * d->c_in || d->dy_pix_stride < (long)a.n_bundles * d->c_out) return BTS_ERR_INVALID;
-    const WgradPlan p = plan_wgrad(d->c_out, a.N, (long)a.M, d->ws_floats, d->ws != nullptr, a.n_bundles);
+    p = plan_wgrad(d->c_out, a.N, (long)a.M, d->ws_floats, d->ws != nullptr, a.n_bundles);
+    const long pps = (((long)a.M + p.split - 1) / p.split + WBK - 1) / WBK * WBK;
+    p.split = ((long)a.M + pps - 1) / pps;                       // no empty splits
+    a.pix_per_split = (unsigned)pps;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int bts_conv_wgrad_f32(const bts_conv_wgrad_desc* d, bts_stream_t stream) {
+    WgradArgs a;
+    WgradPlan p;
+    if (const int rc = prepare_wgrad(d, a, p); rc != 0) return rc;
+    hipStream_t s = (hipStream_t)stream;
     switch (p.variant) {
         case 0: return launch_wgrad<128, 128, 2, 2>(a, p.split, d->dw, d->ws, s);
         case 1: return launch_wgrad<64, 128, 1, 4>(a, p.split, d->dw, d->ws, s);
         case 2: return launch_wgrad<32, 128, 1, 4>(a, p.split, d->dw, d->ws, s);
         default: return launch_wgrad<64, 64, 2, 2>(a, p.split, d->dw, d->ws, s);
     }
+}
+
+extern "C" int bts_conv_wgrad_plan_f32(const bts_conv_wgrad_desc* d, int* bm, int* bn, long* split, long* pix_per_split) {
+    WgradArgs a;
+    WgradPlan p;
+    if (const int rc = prepare_wgrad(d, a, p); rc != 0) return rc;
+    if (bm) *bm = WGRAD_BM[p.variant];
+    if (bn) *bn = WGRAD_BN[p.variant];
+    if (split) *split = p.split;
+    if (pix_per_split) *pix_per_split = (long)a.pix_per_split;
+    return 0;
 }
 
 // ---------------------------------------------------------------------------------------------------------------

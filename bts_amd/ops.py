@@ -939,6 +939,49 @@ def conv_forward(x2d: torch.Tensor, B: int, h_in: int, w_in: int, w_packed: torc
     return out
 
 
+def _wgrad_desc(B: int, h_in: int, w_in: int, c_in: int, c_out: int, ksize: int, dil: int, stride: int, pad: int, up: int,
+                n_bundles: int, x_pix_stride: int, dy_pix_stride: int) -> ConvWgradDesc:
+    """The geometry fields of a bts_conv_wgrad_desc; the caller adds the pointers."""
+    d = ConvWgradDesc()
+    d.n_bundles = n_bundles if n_bundles > 1 else 0
+    d.x_pix_stride, d.c_in, d.dy_pix_stride, d.c_out = x_pix_stride, c_in, dy_pix_stride, c_out
+    d.B, d.h_in, d.w_in, d.up, d.ksize, d.dil, d.stride, d.pad = B, h_in, w_in, up, ksize, dil, stride, pad
+    return d
+
+
+def conv_wgrad_plan_desc(d: ConvWgradDesc) -> Tuple[int, int, int, int]:
+    """bts_conv_wgrad_plan_f32 on a filled descriptor: (bm, bn, split, pix_per_split).  Host arithmetic only."""
+    bm, bn, split, pps = C.c_int(0), C.c_int(0), C.c_long(0), C.c_long(0)
+    _lib.check(_lib.load().bts_conv_wgrad_plan_f32(C.byref(d), C.byref(bm), C.byref(bn), C.byref(split), C.byref(pps)),
+               "bts_conv_wgrad_plan_f32")
+    return bm.value, bn.value, split.value, pps.value
+
+
+_PLAN_DUMMY_PTR = 1 << 20      # non-null, 16-byte aligned; a plan query checks pointers and never follows them
+
+
+def conv_wgrad_plan(B: int, h_in: int, w_in: int, c_in: int, c_out: int, ksize: int, dil: int = 1, stride: int = 1,
+                    pad: Optional[int] = None, up: int = 1, ws_floats: Optional[int] = None, n_bundles: int = 1,
+                    pre: bool = False, pre_relu: bool = False, x_pix_stride: Optional[int] = None,
+                    dy_pix_stride: Optional[int] = None) -> Tuple[int, int, int, int]:
+    """Which tile and pixel split conv_wgrad will run for this geometry: (bm, bn, split, pix_per_split), from the
+    library's own planner (bts_conv_wgrad_plan_f32).  No tensors and no GPU: the geometry arguments are conv_wgrad's,
+    ``ws_floats`` is the size of the workspace it would get (None = no workspace), ``pre`` says whether an input
+    prologue rides along, and the pixel strides default to the dense ``n_bundles * c``."""
+    if pad is None:
+        pad = dil * (ksize // 2)
+    nb = max(n_bundles, 1)
+    d = _wgrad_desc(B, h_in, w_in, c_in, c_out, ksize, dil, stride, pad, up, n_bundles,
+                    nb * c_in if x_pix_stride is None else x_pix_stride, nb * c_out if dy_pix_stride is None else dy_pix_stride)
+    d.x = d.dy = d.dw = _PLAN_DUMMY_PTR
+    if pre:
+        d.pre_scale = d.pre_shift = _PLAN_DUMMY_PTR
+        d.pre_relu = int(bool(pre_relu))
+    if ws_floats is not None:
+        d.ws, d.ws_floats = _PLAN_DUMMY_PTR, ws_floats
+    return conv_wgrad_plan_desc(d)
+
+
 def conv_wgrad(x2d: torch.Tensor, B: int, h_in: int, w_in: int, c_in: int, dy2d: torch.Tensor, c_out: int,
                ksize: int, dil: int = 1, stride: int = 1, pad: Optional[int] = None, up: int = 1,
                ws: Optional[torch.Tensor] = None, tag: str = "wgrad", n_bundles: int = 1,
@@ -959,16 +1002,12 @@ def conv_wgrad(x2d: torch.Tensor, B: int, h_in: int, w_in: int, c_in: int, dy2d:
                           % (tuple(x2d.shape), tuple(dy2d.shape), B, h_in, w_in, H, W))
     shape = (c_out, ksize * ksize, c_in) if n_bundles <= 1 else (n_bundles, c_out, ksize * ksize, c_in)
     dw = torch.empty(shape, dtype=torch.float32, device=x2d.device)
-    d = ConvWgradDesc()
-    d.n_bundles = n_bundles if n_bundles > 1 else 0
+    d = _wgrad_desc(B, h_in, w_in, c_in, c_out, ksize, dil, stride, pad, up, n_bundles, xs, ds)
     if pre is not None:                       # the forward conv saw [relu](x*scale + shift): gather the same thing
         if pre[0].numel() != c_in * max(n_bundles, 1) or pre[1].numel() != pre[0].numel():
             raise BtsHipError("conv_wgrad: pre vectors must have c_in entries")
         d.pre_scale, d.pre_shift, d.pre_relu = pre[0].data_ptr(), pre[1].data_ptr(), int(bool(pre_relu))
-    d.x, d.x_pix_stride, d.c_in = x2d.data_ptr(), xs, c_in
-    d.dy, d.dy_pix_stride, d.c_out = dy2d.data_ptr(), ds, c_out
-    d.B, d.h_in, d.w_in, d.up, d.ksize, d.dil, d.stride, d.pad = B, h_in, w_in, up, ksize, dil, stride, pad
-    d.dw = dw.data_ptr()
+    d.x, d.dy, d.dw = x2d.data_ptr(), dy2d.data_ptr(), dw.data_ptr()
     if ws is not None:
         _need(ws, "conv_wgrad")
         d.ws, d.ws_floats = ws.data_ptr(), ws.numel()

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define BTS_HIP_ABI_VERSION 15
+#define BTS_HIP_ABI_VERSION 16
 
 #define BTS_ERR_INVALID      (-1)   /* bad argument (null pointer, non-positive dim, misalignment) */
 #define BTS_ERR_UNSUPPORTED  (-2)   /* valid in the reference but not built here (e.g. odd upratio)  */
@@ -290,6 +290,15 @@ typedef struct bts_conv_wgrad_desc {
 } bts_conv_wgrad_desc;
 
 int bts_conv_wgrad_f32(const bts_conv_wgrad_desc* desc, bts_stream_t stream);
+
+/* Which tile and pixel split bts_conv_wgrad_f32 will use for this descriptor (host-side query, no GPU work, no device
+ * needed: it runs the launch's own validation and planning, so it also rejects what the launch rejects).
+ *   bm x bn       : the dw tile of one workgroup -- 128x128, 64x128, 32x128 or 64x64
+ *   split         : workgroups along the pixel axis; > 1 means partials in `ws` plus the fixed-order reduction
+ *   pix_per_split : pixels per split (a multiple of 32); (split-1)*pix_per_split < B*H*W <= split*pix_per_split
+ * The launch writes split * n_bundles * c_out * ksize^2 * c_in floats of `ws` when split > 1.  Pointer fields are only
+ * checked (non-null, alignment), never dereferenced; any of the four outputs may be NULL. */
+int bts_conv_wgrad_plan_f32(const bts_conv_wgrad_desc* desc, int* bm, int* bn, long* split, long* pix_per_split);
 
 /* Batched weight re-packing for the training step (the optimiser rewrites the OIHW parameters every iteration,
  * bts_main.py:606): one launch lays every registered weight out as bts_conv_fwd_f32 wants it.

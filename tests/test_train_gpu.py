@@ -129,6 +129,9 @@ def test_wgrad_split_is_deterministic_and_matches_unsplit():
     split path are bit-identical (fixed-order reduction, no atomics)."""
     from bts_amd import ops
     B, h, w, cin, cout = 4, 44, 76, 64, 32
+    bm, bn, split, _ = ops.conv_wgrad_plan(B, h, w, cin, cout, 3, ws_floats=8 << 20)
+    assert (bm, bn) != (64, 64)        # what this test covers: a tile other than the one the small cases above run ...
+    assert split > 1                   # ... on the split path (partials + wgrad_reduce_kernel)
     gen = torch.Generator().manual_seed(3)
     x = torch.randn(B * h * w, cin, generator=gen).cuda()
     dy = torch.randn(B * h * w, cout, generator=gen).cuda()
