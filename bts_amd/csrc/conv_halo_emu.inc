@@ -332,11 +332,12 @@ __global__ __launch_bounds__(512, 2) void conv_halo_emu_kernel(const ConvArgs a)
                 const long m = ((long)bfr * a.H + y) * a.W + x;
                 float v = acc[i][j][r];
                 if (has_e1) v = v * s1 + b1;
-                if (a.res != nullptr && nok && mok) v += a.res[m * a.res_pix_stride + n];
+                // sub-pixel: source pixel (b,y,x) of this parity class is output pixel (b, 2y+py, 2x+px); the residual lives there too
+                const long op = a.subpix ? ((long)bfr * (2 * a.H) + 2 * y + spy) * (2 * a.W) + 2 * x + spx : m;
+                if (a.res != nullptr && nok && mok) v += a.res[op * a.res_pix_stride + n];
                 v = apply_act(v, a.act);
                 if (has_e2) v = v * s2 + b2;
                 if (nok && mok) {
-                    const long op = a.subpix ? ((long)bfr * (2 * a.H) + 2 * y + spy) * (2 * a.W) + 2 * x + spx : m;
                     a.y[op * a.y_pix_stride + n] = v;
                     if (a.y2) a.y2[op * a.y2_pix_stride + n] = v;
                 }

@@ -743,17 +743,17 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_fwd_kernel(const ConvArgs a
                     const long m = m0 + (wm * TM + i) * MF + drow;
                     float v = acc[i][j][r];
                     if (has_e1) v = v * s1 + b1;
-                    if (a.res != nullptr && nok && m < a.M) v += a.res[m * a.res_pix_stride + n];
+                    long op = m;
+                    if (a.subpix && m < a.M) {     // source pixel (b,Y,X) -> output pixel (b, 2Y+py, 2X+px); the residual lives there too
+                        const unsigned mu = (unsigned)m;
+                        const int b = (int)(mu / (unsigned)HW), yx = (int)(mu - (unsigned)b * (unsigned)HW);
+                        const int Y = (int)((unsigned)yx / (unsigned)a.W), X = yx - Y * a.W;
+                        op = ((long)b * (2 * a.H) + 2 * Y + spy) * (2 * a.W) + 2 * X + spx;
+                    }
+                    if (a.res != nullptr && nok && m < a.M) v += a.res[op * a.res_pix_stride + n];
                     v = apply_act(v, a.act);
                     if (has_e2) v = v * s2 + b2;
                     if (nok && m < a.M) {
-                        long op = m;
-                        if (a.subpix) {            // source pixel (b,Y,X) -> output pixel (b, 2Y+py, 2X+px)
-                            const unsigned mu = (unsigned)m;
-                            const int b = (int)(mu / (unsigned)HW), yx = (int)(mu - (unsigned)b * (unsigned)HW);
-                            const int Y = (int)((unsigned)yx / (unsigned)a.W), X = yx - Y * a.W;
-                            op = ((long)b * (2 * a.H) + 2 * Y + spy) * (2 * a.W) + 2 * X + spx;
-                        }
                         a.y[op * a.y_pix_stride + n] = v;
                         if (a.y2) a.y2[op * a.y2_pix_stride + n] = v;
                     }
