@@ -20,9 +20,10 @@ SYMBOLS = (
     "bts_pack_weights_blocks", "bts_pack_weights_f32", "bts_pack_wino_floats", "bts_pack_wino_f32", "bts_eval_ws_doubles", "bts_eval_depth_metrics_f32",
     "bts_reduc_lpg_fwd_f32", "bts_plan_run", "bts_upconv_combine_f32",
     "bts_depth_loss_ws_doubles", "bts_depth_loss_fwd_f32", "bts_depth_loss_bwd_f32",
+    "bts_reduc_bwd_f32", "bts_reduc_bwd_max_waves",
 )
 
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 
 class ConvDesc(C.Structure):
@@ -134,6 +135,10 @@ def load_real():
     lib.bts_reduc_fwd_f32.argtypes = [vp, l, l, i, i, vp, l, f, i, i, vp, vp]
     lib.bts_reduc_lpg_fwd_f32.restype = i
     lib.bts_reduc_lpg_fwd_f32.argtypes = [vp, l, i, i, i, i, i, vp, l, f, i, vp, vp, vp, vp, vp]
+    lib.bts_reduc_bwd_f32.restype = i
+    lib.bts_reduc_bwd_f32.argtypes = [vp, l, i, i, i, i, i, vp, l, vp, l, f, i, vp, vp, l, vp, vp, vp]
+    lib.bts_reduc_bwd_max_waves.restype = l
+    lib.bts_reduc_bwd_max_waves.argtypes = [i, i, i]
     lib.bts_conv_fwd_f32.restype = i
     lib.bts_conv_fwd_f32.argtypes = [C.POINTER(ConvDesc), vp]
     lib.bts_conv_wgrad_f32.restype = i

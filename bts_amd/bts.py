@@ -258,10 +258,16 @@ class reduction_1x1(nn.Sequential):
                 stack.add_module('plane_params', nn.Conv2d(cin, 3, kernel_size=1, bias=False))
         self.reduc = stack
         self._packs = PackCache(self)
+        self._packs_train = PackCache(self)
 
     def packed(self) -> torch.Tensor:
         ws = [m.weight.detach() for m in self.reduc.modules() if isinstance(m, nn.Conv2d)]
         return self._packs.get(ws[0].device, lambda: ops.pack_reduc_weights(ws))
+
+    def packed_train(self):
+        """(w_frag, w_frag_wide, wt_frag) for the fused training kernels (ops.reduc_train_packs), cached like packed()."""
+        ws = [m.weight.detach() for m in self.reduc.modules() if isinstance(m, nn.Conv2d)]
+        return self._packs_train.get(ws[0].device, lambda: ops.reduc_train_packs(ws))
 
     def run_nhwc(self, x2d, out, normalize):
         ops.reduc_forward_nhwc(x2d, self.c_in, self.c_first_out, self.packed(), self.max_depth, self.is_final,
@@ -362,6 +368,9 @@ class bts(nn.Module):
         self._bufs = WorkspaceCache(max_entries=8)      # per-shape NHWC workspaces; shared with replicas, graph-pinnable
         self.fill_frames = None                         # launch declaration when the decoder is called on its own
         self.conv_precision = "fp32"                    # (BtsModel.forward opens its own scope: see BtsModel.fill_frames)
+        self.fused_reduction_train = False              # train() mode: True runs each reduction_1x1 -> LPG scale and reduc1x1 as one
+                                                        # autograd node on the fused kernels (train.fused_lpg_scale);
+                                                        # chains the library does not build (bts_size 256) keep the layer graph
 
     # ------------------------------------------------------------------ weight packing (lazy)
     _OWN = ("bn5", "conv5", "bn4", "conv4", "bn4_2", "daspp_conv", "bn3", "conv3", "bn2", "conv2", "conv1", "get_depth")
@@ -641,6 +650,15 @@ class BtsModel(nn.Module):
         self._fp_state = [0, None, -1]      # workspace.tensor_fingerprint: [structure token, cached tensor list, its token]
         self._origin = [self]               # reaches DataParallel replicas through replicate()'s shallow __dict__ copy
         self._enc_plans = {}                # device -> DenseNetHip / ResNetHip (packs + workspaces), shared with replicas
+
+    @property
+    def fused_reduction_train(self) -> bool:
+        """The decoder's switch of the same name (bts.fused_reduction_train), default False."""
+        return self.decoder.fused_reduction_train
+
+    @fused_reduction_train.setter
+    def fused_reduction_train(self, on: bool):
+        self.decoder.fused_reduction_train = bool(on)
 
     def _native_ok(self, x):
         return (self.native_encoder and not self.training and isinstance(x, torch.Tensor) and x.is_cuda

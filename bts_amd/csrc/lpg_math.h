@@ -35,3 +35,25 @@ __device__ __forceinline__ void lpg_cell_outputs(float n1, float n2, float n3, f
         res[i] = n4 * __builtin_amdgcn_rcpf(d * max_depth);           // bts.py:173, 255
     }
 }
+
+// Gradient of lpg_cell_outputs: NOUT consecutive incoming gradients g[i] (of depth/max_depth) at columns ck0.. of row
+// phase rk are folded into the cell's plane gradient.  The denominator and its clamp are the forward's own expressions;
+// where the clamp replaced den by a constant, d/dn1..n3 is zero and d/dn4 keeps 1/(clamped den) -- the treatment of
+// bts_lpg_bwd_f32 (lpg.hip).  Divisions are IEEE.  The caller fixes the order in which (rk, ck0) are visited.
+template <int K, int NOUT>
+__device__ __forceinline__ void lpg_cell_grads(float n1, float n2, float n3, float n4, int rk, int ck0, float max_depth,
+                                               const float (&g)[NOUT], float& g1, float& g2, float& g3, float& g4) {
+    constexpr float invK = 1.0f / (float)K;
+    const float v = ((float)rk - (float)(K - 1) * 0.5f) * invK;
+    const float base = fmaf(n2, v, n3);
+    const float u0 = ((float)ck0 - (float)(K - 1) * 0.5f) * invK;
+#pragma unroll
+    for (int i = 0; i < NOUT; ++i) {
+        const float u = u0 + (float)i * invK;
+        const float d = fmaf(n1, u, base);
+        const float dc = lpg_clamp(d);
+        g4 += g[i] / (dc * max_depth);
+        const float gd = dc != d ? 0.f : -g[i] * n4 / (d * d * max_depth);
+        g1 += gd * u; g2 += gd * v; g3 += gd;
+    }
+}

@@ -18,6 +18,7 @@
 #include <stdint.h>
 #include "common.h"
 #include "lpg_math.h"
+#include "reduc_chain.h"      // dense_layer, chain_frag_float4s
 
 namespace {
 
@@ -96,41 +97,6 @@ __device__ __forceinline__ void lpg_publish_key(int key, int* abs_min_key) {
     }
 }
 
-// One dense layer: acc[mt] (32 out-rows each) = W * x, K real input channels (multiple of 8).
-// wf points at this layer's fragments: float4 index ((mt*(K/8) + g)*64 + lane).
-template <int K, int MT, int NX>
-__device__ __forceinline__ void dense_layer(const float4* __restrict__ wf, int lane, const float (&x)[NX],
-                                            f32x16 (&acc)[MT]) {
-    static_assert(NX >= K / 2, "activation registers");
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[mt][r] = 0.f;
-    // software-prefetch one g-step of weight fragments; the sched_barrier keeps hipcc from
-    // hoisting every ds_read of the layer to its top (which spills: 64 x b128 for 128->128)
-    float4 wn[MT];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) wn[mt] = wf[(mt * (K / 8)) * 64 + lane];
-#pragma unroll
-    for (int g = 0; g < K / 8; ++g) {
-        float4 w[MT];
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) w[mt] = wn[mt];
-        if (g + 1 < K / 8) {
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt) wn[mt] = wf[(mt * (K / 8) + g + 1) * 64 + lane];
-        }
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-            acc[mt] = mfma32x2(w[mt].x, x[4 * g + 0], acc[mt]);
-            acc[mt] = mfma32x2(w[mt].y, x[4 * g + 1], acc[mt]);
-            acc[mt] = mfma32x2(w[mt].z, x[4 * g + 2], acc[mt]);
-            acc[mt] = mfma32x2(w[mt].w, x[4 * g + 3], acc[mt]);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    }
-}
-
 // Mirrors the while-loop of reduction_1x1.__init__ (bts.py:105-122): K = num_in_filters,
 // M = num_out_filters.  Leaves the last layer's first rows in o[0..2] (valid on lanes < 32).
 template <int K, int M, int NX>
@@ -149,15 +115,6 @@ __device__ __forceinline__ void chain(const float4* __restrict__ wf, int lane, c
         for (int i = 0; i < NY; ++i) y[i] = elu1(acc[i / 16][i % 16]);      // conv + ELU, bts.py:116-119
         chain<M, M / 2, NY>(wf + MT * (K / 8) * 64, lane, y, o);
     }
-}
-
-template <int C0, int M0>
-constexpr long chain_frag_float4s() {
-    long n = 0;
-    int k = C0, m = M0;
-    while (m >= 8) { n += (long)((m + 31) / 32) * (k / 8) * 64; k = m; m = m / 2; }
-    n += (long)(k / 8) * 64;
-    return n;
 }
 
 template <int C0, int M0, bool FINAL, int LPGK = 0>

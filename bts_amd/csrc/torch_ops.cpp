@@ -9,8 +9,8 @@
 //   * hands raw device pointers and dims to the extern "C" entry point -- no torch type crosses that line.
 // Built with g++ only (no device code): `make -C bts_amd/csrc torch` -> bts_amd/libbts_torch.so, loaded by
 // bts_amd/_lib.py with torch.ops.load_library.  Autograd for `bts_hip::lpg` is registered in bts_amd/ops.py
-// (torch.library.register_autograd) on top of `bts_hip::lpg_backward`, and for `bts_hip::depth_loss` on top of
-// `bts_hip::depth_loss_backward`.
+// (torch.library.register_autograd) on top of `bts_hip::lpg_backward`, for `bts_hip::depth_loss` on top of
+// `bts_hip::depth_loss_backward`, and for `bts_hip::reduc_lpg_train` / `reduction_1x1_train` on top of `bts_hip::reduc_bwd`.
 #include <ATen/ATen.h>
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>      // PyTorch-ROCm tensors carry the device type "cuda": its guard / stream
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>         // accessors are the *MasqueradingAsCUDA forms
@@ -133,6 +133,79 @@ void reduc_lpg(const Tensor& x2d, int64_t B, int64_t h, int64_t w, int64_t c_in,
                                    w_frag.numel(), (float)max_depth, (int)k, opt_ptr(plane4), depth_scaled.data_ptr<float>(), opt_ptr(ds_out),
                                    opt_ptr(abs_min), current_stream()),
              "bts_hip::reduc_lpg");
+}
+
+// ---------------------------------------------------------------------------------------------- reduction, training
+// Backward-data of one reduction scale (csrc/reduc_bwd.hip): fills Y, and G / dx when given.  upratio 0 = the final chain.
+void reduc_bwd(const Tensor& x2d, int64_t B, int64_t h, int64_t w, int64_t c_in, int64_t c_first_out, const Tensor& w_frag,
+               const Tensor& wt_frag, double max_depth, int64_t upratio, const Tensor& grad_out, OptTensor dx, OptTensor G, Tensor Y) {
+    const char* op = "bts_hip::reduc_bwd";
+    const long xs = rows2d_stride(x2d, op, "x2d");
+    const int64_t npix = B * h * w, kk = upratio > 0 ? upratio * upratio : 1;
+    TORCH_CHECK(B > 0 && h > 0 && w > 0 && x2d.size(0) == npix && x2d.size(1) >= c_in, op, ": x2d ", x2d.sizes(), " does not match B=", B, " ", h,
+                "x", w, " with ", c_in, " channels");
+    for (const Tensor* t : {&w_frag, &wt_frag, &grad_out, (const Tensor*)&Y}) {
+        need_f32_cuda(*t, op, "tensor argument");
+        same_device(x2d, *t, op, "tensor argument");
+        TORCH_CHECK(t->is_contiguous(), op, ": w_frag, wt_frag, grad_out and Y must be contiguous");
+    }
+    TORCH_CHECK(grad_out.numel() == npix * kk, op, ": grad_out must hold ", npix * kk, " floats");
+    TORCH_CHECK(Y.dim() == 2 && Y.size(0) == npix, op, ": Y must be [npix, YC]");
+    const int64_t yc = Y.size(1);
+    float* gp = nullptr;
+    if (G.has_value() && G->defined()) {
+        need_f32_cuda(*G, op, "G");
+        same_device(x2d, *G, op, "G");
+        TORCH_CHECK(G->is_contiguous() && G->dim() == 2 && G->size(0) == npix && G->size(1) == yc + 4, op, ": G must be contiguous [npix, YC + 4]");
+        gp = G->data_ptr<float>();
+    }
+    float* dxp = nullptr;
+    long dxs = 0;
+    if (dx.has_value() && dx->defined()) {
+        dxs = rows2d_stride(*dx, op, "dx");
+        same_device(x2d, *dx, op, "dx");
+        TORCH_CHECK(dx->size(0) == npix && dx->size(1) >= c_in, op, ": dx must be a [npix, >= c_in] view");
+        dxp = dx->data_ptr<float>();
+    }
+    // the kernel addresses Y by the chain's own column count: refuse a buffer of another width before it runs
+    int64_t want = 0;
+    for (int64_t m = c_first_out; m >= 8; m /= 2) want += m;
+    TORCH_CHECK(yc == want, op, ": Y has ", yc, " columns, the chain (", c_in, ",", c_first_out, ") writes ", want);
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(x2d.device());
+    check_rc(bts_reduc_bwd_f32(x2d.data_ptr<float>(), xs, (int)B, (int)h, (int)w, (int)c_in, (int)c_first_out, w_frag.data_ptr<float>(),
+                               w_frag.numel(), wt_frag.data_ptr<float>(), wt_frag.numel(), (float)max_depth, (int)upratio,
+                               grad_out.data_ptr<float>(), dxp, dxs, gp, Y.data_ptr<float>(), current_stream()), op);
+}
+
+void train_args(const char* op, const Tensor& x2d, const std::vector<Tensor>& weights, const std::vector<Tensor>& packs) {
+    TORCH_CHECK(!weights.empty() && weights[0].dim() == 4, op, ": weights must be the chain's [cout,cin,1,1] tensors");
+    TORCH_CHECK(packs.size() == 3, op, ": packs must be ops.reduc_train_packs(weights): (w_frag, w_frag_wide, wt_frag)");
+    for (const Tensor& t : packs) { need_f32_cuda(t, op, "pack"); same_device(x2d, t, op, "pack"); }
+}
+
+// Out-of-place forms of reduc_lpg / reduction_1x1 for training callers: fresh outputs, and autograd registered in
+// bts_amd/ops.py on top of bts_hip::reduc_bwd.  `weights` are there to be differentiated; the kernels read `packs`.
+std::tuple<Tensor, Tensor> reduc_lpg_train(const Tensor& x2d, int64_t B, int64_t h, int64_t w, std::vector<Tensor> weights,
+                                           std::vector<Tensor> packs, double max_depth, int64_t upratio) {
+    train_args("bts_hip::reduc_lpg_train", x2d, weights, packs);
+    need_f32_cuda(x2d, "bts_hip::reduc_lpg_train", "x2d");
+    TORCH_CHECK(upratio == 8 || upratio == 4 || upratio == 2, "bts_hip::reduc_lpg_train: upratio must be 8, 4 or 2, got ", upratio);
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(x2d.device());
+    Tensor depth = at::empty({B, 1, h * upratio, w * upratio}, x2d.options());
+    Tensor abs_min = at::empty({}, x2d.options());
+    reduc_lpg(x2d, B, h, w, weights[0].size(1), weights[0].size(0), packs[0], max_depth, upratio, depth, OptTensor(), abs_min, OptTensor());
+    return {depth, abs_min};
+}
+
+Tensor reduction_1x1_train(const Tensor& x2d, int64_t B, int64_t h, int64_t w, std::vector<Tensor> weights, std::vector<Tensor> packs,
+                           double max_depth) {
+    train_args("bts_hip::reduction_1x1_train", x2d, weights, packs);
+    need_f32_cuda(x2d, "bts_hip::reduction_1x1_train", "x2d");
+    TORCH_CHECK(B > 0 && h > 0 && w > 0 && x2d.dim() == 2 && x2d.size(0) == B * h * w, "bts_hip::reduction_1x1_train: x2d must have B*h*w rows");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(x2d.device());
+    Tensor out = at::empty({B, 1, h, w}, x2d.options());
+    reduction_1x1(x2d, weights[0].size(1), weights[0].size(0), packs[0], max_depth, /*is_final=*/true, /*normalize=*/false, out);
+    return out;
 }
 
 // ------------------------------------------------------------------------------------------------------------- conv
@@ -301,6 +374,10 @@ TORCH_LIBRARY(bts_hip, m) {
     m.def("reduction_1x1(Tensor x2d, int c_in, int c_first_out, Tensor w_frag, float max_depth, bool is_final, bool normalize, Tensor(a!) out) -> ()");
     m.def("reduc_lpg(Tensor x2d, int B, int h, int w, int c_in, int c_first_out, Tensor w_frag, float max_depth, int upratio, "
           "Tensor(a!) depth_scaled, Tensor(b!)? ds_out, Tensor(c!)? abs_min, Tensor(d!)? plane4) -> ()");
+    m.def("reduc_bwd(Tensor x2d, int B, int h, int w, int c_in, int c_first_out, Tensor w_frag, Tensor wt_frag, float max_depth, int upratio, "
+          "Tensor grad_out, Tensor(a!)? dx, Tensor(b!)? G, Tensor(c!) Y) -> ()");
+    m.def("reduc_lpg_train(Tensor x2d, int B, int h, int w, Tensor[] weights, Tensor[] packs, float max_depth, int upratio) -> (Tensor, Tensor)");
+    m.def("reduction_1x1_train(Tensor x2d, int B, int h, int w, Tensor[] weights, Tensor[] packs, float max_depth) -> Tensor");
     m.def("conv_fwd(Tensor x, Tensor w, Tensor? pre_scale, Tensor? pre_shift, Tensor? e1_scale, Tensor? e1_shift, Tensor? e2_scale, "
           "Tensor? e2_shift, Tensor(a!) y, Tensor(b!)? y2, Tensor? res, Tensor(c!)? splitk_ws, Tensor[] tail_planes, Tensor? w_split, "
           "Tensor? w_wino, int[] geom) -> ()");
@@ -313,6 +390,9 @@ TORCH_LIBRARY_IMPL(bts_hip, CUDA, m) {
     m.impl("lpg_backward", &lpg_backward);
     m.impl("reduction_1x1", &reduction_1x1);
     m.impl("reduc_lpg", &reduc_lpg);
+    m.impl("reduc_bwd", &reduc_bwd);
+    m.impl("reduc_lpg_train", &reduc_lpg_train);
+    m.impl("reduction_1x1_train", &reduction_1x1_train);
     m.impl("conv_fwd", &conv_fwd);
     m.impl("depth_loss", &depth_loss);
     m.impl("depth_loss_backward", &depth_loss_backward);

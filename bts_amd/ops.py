@@ -11,6 +11,7 @@ import threading
 from typing import List, Optional, Sequence, Tuple
 
 import torch
+import torch.nn.functional as F
 
 from . import _lib, conv_plan
 from ._lib import BtsHipError, ConvDesc, ConvWgradDesc
@@ -127,6 +128,34 @@ def torch_ops():
             return g, None, None, None, None, None
 
         torch.library.register_autograd("bts_hip::depth_loss", _loss_backward, setup_context=_loss_setup)
+
+        # the out-of-place training forms of the reduction scales: backward = bts_hip::reduc_bwd + one wgrad per layer
+        def _reduc_setup(lpg):
+            def setup(ctx, inputs, output):
+                if lpg:
+                    x2d, ctx.B, ctx.h, ctx.w, weights, packs, ctx.md, ctx.k = inputs
+                else:
+                    x2d, ctx.B, ctx.h, ctx.w, weights, packs, ctx.md = inputs
+                    ctx.k = 0
+                ctx.save_for_backward(x2d, *weights)
+                ctx.packs = list(packs)
+                ctx.need = (x2d.requires_grad, [wt.requires_grad for wt in weights])
+            return setup
+
+        def _reduc_backward(lpg):
+            def backward(ctx, grad_out, *unused):
+                x2d, *weights = ctx.saved_tensors
+                dx, dws = reduc_train_backward(x2d, ctx.B, ctx.h, ctx.w, weights, ctx.packs, ctx.md, ctx.k, grad_out,
+                                               ctx.need[0], ctx.need[1])
+                if dx is not None:
+                    dx = dx.view(x2d.shape[0], -1)
+                    if dx.shape[1] != x2d.shape[1]:                       # a view wider than the chain reads
+                        dx = F.pad(dx, (0, x2d.shape[1] - dx.shape[1]))
+                return (dx, None, None, None, dws, [None] * len(ctx.packs), None) + ((None,) if lpg else ())
+            return backward
+
+        torch.library.register_autograd("bts_hip::reduc_lpg_train", _reduc_backward(True), setup_context=_reduc_setup(True))
+        torch.library.register_autograd("bts_hip::reduction_1x1_train", _reduc_backward(False), setup_context=_reduc_setup(False))
     return t
 
 
@@ -325,33 +354,115 @@ def reduc_uses_mfma16(c_in: int, c_first_out: int) -> bool:
     return (c_in, c_first_out) in ((64, 32), (32, 16), (64, 64), (16, 8))      # the last two: bts_size 256
 
 
-def pack_reduc_weights(weights: Sequence[torch.Tensor]) -> torch.Tensor:
+def _pack_reduc_layers(mats: Sequence[torch.Tensor], narrow: bool) -> torch.Tensor:
+    """Fragment order of a chain's [cout, cin] matrices (any dtype: the index tables of reduc_train_packs run through it)."""
+    parts = []
+    for w in mats:
+        cout, cin = w.shape
+        assert cin % 8 == 0, "reduction chain widths are multiples of 8"
+        if narrow:
+            mt, g = (cout + 15) // 16, (cin + 15) // 16
+            wp = torch.zeros((mt * 16, g * 16), dtype=w.dtype, device=w.device)
+            wp[:cout, :cin] = w
+            # (mt, i, g, kq, q4) -> (mt, g, kq, i, q4)
+            parts.append(wp.view(mt, 16, g, 4, 4).permute(0, 2, 3, 1, 4).contiguous().view(-1))
+        else:
+            mt = (cout + 31) // 32
+            wp = torch.zeros((mt * 32, cin), dtype=w.dtype, device=w.device)
+            wp[:cout] = w
+            # (mt, i, g, h, q) -> (mt, g, h, i, q)
+            parts.append(wp.view(mt, 32, cin // 8, 2, 4).permute(0, 2, 3, 1, 4).contiguous().view(-1))
+    return torch.cat(parts).contiguous()
+
+
+def pack_reduc_weights(weights: Sequence[torch.Tensor], wide: Optional[bool] = None) -> torch.Tensor:
     """Pack a reduction chain's 1x1 weights ([cout,cin,1,1] each) into MFMA fragment order.
 
     Wide chains (first layer 128 -> ..): per layer (K=cin, rows padded to 32*MT) float4 index
     ((mt*(K/8)+g)*64 + 32*h + i) holds W[32*mt+i][4*(2g+h) + 0..3] -- lane (i,h) of v_mfma_f32_32x32x2_f32's A operand
     for the four k-steps of group g.  Narrow chains (see reduc_uses_mfma16): rows padded to 16*MT, K to 16*G, float4
-    index ((mt*G+g)*64 + 16*kq + i) holds W[16*mt+i][16*g + 4*kq + 0..3] -- lane (i,kq) of v_mfma_f32_16x16x4_f32."""
-    c_in = weights[0].shape[1]
-    c_first = weights[0].shape[0]
-    narrow = reduc_uses_mfma16(c_in, c_first)
-    parts = []
-    for w in weights:
-        cout, cin = w.shape[0], w.shape[1]
-        assert cin % 8 == 0, "reduction chain widths are multiples of 8"
-        if narrow:
-            mt, g = (cout + 15) // 16, (cin + 15) // 16
-            wp = torch.zeros((mt * 16, g * 16), dtype=torch.float32, device=w.device)
-            wp[:cout, :cin] = w.reshape(cout, cin).float()
-            # (mt, i, g, kq, q4) -> (mt, g, kq, i, q4)
-            parts.append(wp.view(mt, 16, g, 4, 4).permute(0, 2, 3, 1, 4).contiguous().view(-1))
-        else:
-            mt = (cout + 31) // 32
-            wp = torch.zeros((mt * 32, cin), dtype=torch.float32, device=w.device)
-            wp[:cout] = w.reshape(cout, cin).float()
-            # (mt, i, g, h, q) -> (mt, g, h, i, q)
-            parts.append(wp.view(mt, 32, cin // 8, 2, 4).permute(0, 2, 3, 1, 4).contiguous().view(-1))
-    return torch.cat(parts).contiguous()
+    index ((mt*G+g)*64 + 16*kq + i) holds W[16*mt+i][16*g + 4*kq + 0..3] -- lane (i,kq) of v_mfma_f32_16x16x4_f32.
+    ``wide=True`` forces the first order for any chain: what the backward kernel (bts_reduc_bwd_f32) reads."""
+    narrow = reduc_uses_mfma16(weights[0].shape[1], weights[0].shape[0]) if wide is None else not wide
+    return _pack_reduc_layers([w.reshape(w.shape[0], w.shape[1]).float() for w in weights], narrow)
+
+
+def _reduc_transposed(mats: Sequence[torch.Tensor]) -> List[torch.Tensor]:
+    """W_l^T in reverse layer order, the last layer's 3 (1) outputs zero-padded to 8 columns."""
+    out = []
+    for w in reversed(list(mats)):
+        wt = w.t()
+        if wt.shape[1] % 8:
+            wt = F.pad(wt, (0, 8 - wt.shape[1] % 8))
+        out.append(wt)
+    return out
+
+
+def pack_reduc_weights_bwd(weights: Sequence[torch.Tensor]) -> torch.Tensor:
+    """The second fragment buffer of bts_reduc_bwd_f32: the backward walk dy_{l-1} = W_l^T dpre_l is the forward chain
+    mirrored, so its fragments are pack_reduc_weights' wide order applied to W_l^T, last layer first."""
+    return _pack_reduc_layers(_reduc_transposed([w.reshape(w.shape[0], w.shape[1]).float() for w in weights]), False)
+
+
+def unpack_reduc_weights(frag: torch.Tensor, shapes: Sequence[Tuple[int, int]]) -> List[torch.Tensor]:
+    """Inverse of the wide fragment order: ``shapes`` = (rows, cols) per packed matrix, in buffer order."""
+    out, off = [], 0
+    for rows, cols in shapes:
+        mt = (rows + 31) // 32
+        n = mt * 32 * cols
+        out.append(frag[off:off + n].view(mt, cols // 8, 2, 32, 4).permute(0, 3, 1, 2, 4).reshape(mt * 32, cols)[:rows])
+        off += n
+    assert off == frag.numel(), "fragment buffer does not match the shapes"
+    return out
+
+
+REDUC_TRAIN_CHAINS = ((128, 128, 8), (128, 64, 4), (64, 32, 2), (32, 16, 0))     # (c_in, c_first_out, upratio; 0 = final)
+
+
+def reduc_train_supported(c_in: int, c_first_out: int, upratio: int) -> bool:
+    """Whether bts_reduc_bwd_f32 is built for this chain (bts_size 512's four; upratio 0 = the final chain)."""
+    return (int(c_in), int(c_first_out), int(upratio)) in REDUC_TRAIN_CHAINS
+
+
+def reduc_train_cols(c_in: int, c_first_out: int) -> Tuple[List[Tuple[int, int]], int]:
+    """Column table of bts_reduc_bwd_f32's row buffers: ([(first column, width) per layer], YC).  Y holds the hidden
+    layers (all entries but the last, YC columns), G every layer (YC + 4 columns: the last layer padded to 4)."""
+    cols, c = [], 0
+    for _, cout in reduc_chain(c_in, c_first_out):
+        width = cout if cout > 0 else 4
+        cols.append((c, width))
+        c += width
+    return cols, c - 4
+
+
+_TRAIN_PACK_INDEX = {}
+
+
+def reduc_train_packs(weights: Sequence[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(w_frag, w_frag_wide, wt_frag) for one chain in TWO launches: pack_reduc_weights(weights),
+    pack_reduc_weights(weights, wide=True) and pack_reduc_weights_bwd(weights) are three fixed permutations (with zero
+    padding) of the same numbers, so one gather through a cached index table fills all of them.  On the wide chains the
+    first two are one buffer."""
+    shapes = tuple((w.shape[0], w.shape[1]) for w in weights)
+    dev = weights[0].device
+    key = (shapes, str(dev))
+    hit = _TRAIN_PACK_INDEX.get(key)
+    if hit is None:
+        fakes, off = [], 1                                     # 0 = the zero every padding position reads
+        for co, ci in shapes:
+            fakes.append(torch.arange(off, off + co * ci, dtype=torch.int64).view(co, ci))
+            off += co * ci
+        narrow = reduc_uses_mfma16(shapes[0][1], shapes[0][0])
+        wide = _pack_reduc_layers(fakes, False)
+        wt = _pack_reduc_layers(_reduc_transposed(fakes), False)
+        parts = ([_pack_reduc_layers(fakes, True)] if narrow else []) + [wide, wt]
+        hit = _TRAIN_PACK_INDEX[key] = (torch.cat(parts).to(dev), [p.numel() for p in parts])
+    idx, sizes = hit
+    src = torch.cat([torch.zeros(1, dtype=torch.float32, device=dev)] + [w.detach().reshape(-1).float() for w in weights])
+    packs = list(torch.split(src[idx], sizes))
+    if len(packs) == 2:
+        packs.insert(0, packs[0])
+    return tuple(packs)
 
 
 def reduc_forward_nhwc(x2d: torch.Tensor, c_in: int, c_first_out: int, w_frag: torch.Tensor, max_depth: float,
@@ -419,6 +530,171 @@ def reduc_lpg_forward(x2d: torch.Tensor, B: int, h: int, w: int, c_in: int, c_fi
         rc = _launch("reduc_lpg_kernel<%d,%d,k%d>" % (c_in, c_first_out, k), "reduc_lpg", 2.0 * npix * macs + 8.0 * npix * k * k, nbytes, run)
     _lib.check(rc, "bts_reduc_lpg_fwd_f32")
     return depth_scaled
+
+
+# ------------------------------------------------------------------------ reduction, training
+def nhwc_rows(x: torch.Tensor) -> Tuple[torch.Tensor, int]:
+    """[B,C,H,W] (any strides) -> ([B*H*W, C4] NHWC rows with C padded to a multiple of 4, C4).
+    A channels_last tensor with C % 4 == 0 is viewed, not copied -- and so is a CHANNEL SLICE of one (what autograd hands
+    back for the inputs of a torch.cat, and what a dense block's layers read): the kernels take a pixel stride."""
+    B, C, H, W = x.shape
+    c4 = round_up(C, 4)
+    if c4 == C and B * H * W > 0 and x.stride(1) == 1 and W > 1 and H > 1:
+        ct = x.stride(3)
+        if (ct >= C and ct % 4 == 0 and x.stride(2) == W * ct and (B == 1 or x.stride(0) == H * W * ct)
+                and x.data_ptr() % 16 == 0):
+            return x.as_strided((B * H * W, C), (ct, 1)), c4
+    rows = x.permute(0, 2, 3, 1)
+    if c4 != C:
+        rows = F.pad(rows, (0, c4 - C))
+    return rows.contiguous().view(B * H * W, c4), c4
+
+
+def reduc_bwd_max_waves(c_in: int, c_first_out: int, upratio: int) -> int:
+    """The most waves one bts_reduc_bwd_f32 launch runs for this chain (each walks 32-pixel tiles in a grid-stride loop)."""
+    n = _lib.load_real().bts_reduc_bwd_max_waves(int(c_in), int(c_first_out), int(upratio))
+    if n < 0:
+        _lib.check(n, "bts_reduc_bwd_max_waves")
+    return n
+
+
+def reduc_backward(x2d: torch.Tensor, B: int, h: int, w: int, c_in: int, c_first_out: int, w_frag_wide: torch.Tensor,
+                   wt_frag: torch.Tensor, max_depth: float, upratio: int, grad_out: torch.Tensor, Y: torch.Tensor,
+                   G: Optional[torch.Tensor] = None, dx2d: Optional[torch.Tensor] = None):
+    """Backward-data of one reduction scale in ONE launch (bts_reduc_bwd_f32).  x2d: [B*h*w, >=c_in] NHWC view;
+    ``upratio`` 8 / 4 / 2: grad_out is the gradient of depth_scaled [B,1,h*k,w*k]; 0: the final chain, grad_out
+    [B,1,h,w].  Fills Y [npix, YC], and when given G [npix, YC+4] and dx2d ([npix, >=c_in] view, any pixel stride that
+    is a multiple of 4; columns >= c_in untouched).  Column tables: reduc_train_cols."""
+    stride, cview = _rows2d(x2d, "reduc_backward")
+    for t in (w_frag_wide, wt_frag, grad_out, Y):
+        _need(t, "reduc_backward")
+    k = int(upratio)
+    npix = B * h * w
+    cols, yc = reduc_train_cols(c_in, c_first_out)
+    if cview < c_in or x2d.shape[0] != npix:
+        raise BtsHipError("reduc_backward: bad input view %s for B=%d %dx%d, %d channels" % (tuple(x2d.shape), B, h, w, c_in))
+    if grad_out.numel() != npix * max(k * k, 1) or not grad_out.is_contiguous():
+        raise BtsHipError("reduc_backward: grad_out must be contiguous with %d elements" % (npix * max(k * k, 1)))
+    if tuple(Y.shape) != (npix, yc) or not Y.is_contiguous():
+        raise BtsHipError("reduc_backward: Y must be contiguous [%d, %d]" % (npix, yc))
+    if G is not None:
+        _need(G, "reduc_backward")
+        if tuple(G.shape) != (npix, yc + 4) or not G.is_contiguous():
+            raise BtsHipError("reduc_backward: G must be contiguous [%d, %d]" % (npix, yc + 4))
+    dxs = 0
+    if dx2d is not None:
+        dxs, dxc = _rows2d(dx2d, "reduc_backward")
+        if dxc < c_in or dx2d.shape[0] != npix or dxs % 4:
+            raise BtsHipError("reduc_backward: dx2d must be a [%d, >=%d] view with a pixel stride that is a multiple of 4" % (npix, c_in))
+    macs = sum(ci * co for ci, (_, co) in zip([c for c, _ in reduc_chain(c_in, c_first_out)], cols))
+    nbytes = 4.0 * (npix * (c_in + yc + (yc + 4 if G is not None else 0) + (c_in if dx2d is not None else 0) + max(k * k, 1)) + 2 * macs)
+    tops = torch_ops()
+    if tops is not None:
+        run = lambda: _op(lambda: tops.reduc_bwd(x2d, B, h, w, int(c_in), int(c_first_out), w_frag_wide, wt_frag, float(max_depth), k,
+                                                 grad_out, dx2d, G, Y))
+    else:
+        run = lambda: _lib.load().bts_reduc_bwd_f32(_ptr(x2d), stride, B, h, w, int(c_in), int(c_first_out), _ptr(w_frag_wide),
+                                                    w_frag_wide.numel(), _ptr(wt_frag), wt_frag.numel(), float(max_depth), k,
+                                                    _ptr(grad_out), _ptr(dx2d), dxs, _ptr(G), _ptr(Y), _stream(x2d))
+    with torch.cuda.device(x2d.device):
+        rc = _launch("reduc_bwd_kernel<%d,%d,k%d>" % (c_in, c_first_out, k), "reduc_bwd", 4.0 * npix * macs + 12.0 * npix * k * k, nbytes, run)
+    _lib.check(rc, "bts_reduc_bwd_f32")
+
+
+def reduc_train_backward(x2d: torch.Tensor, B: int, h: int, w: int, weights: Sequence[torch.Tensor], packs, max_depth: float,
+                         upratio: int, grad_out: torch.Tensor, need_dx: bool, need_dw: Sequence[bool],
+                         ws: Optional[torch.Tensor] = None):
+    """All gradients of one scale: one bts_reduc_bwd_f32 launch, then one bts_conv_wgrad_f32 (ksize 1) per layer whose
+    weight wants a gradient, on column slices of the row buffers.  Returns (dx [B,h,w,c_in] or None, [dW or None])."""
+    c_in, c_first = weights[0].shape[1], weights[0].shape[0]
+    npix = B * h * w
+    cols, yc = reduc_train_cols(c_in, c_first)
+    dev = x2d.device
+    any_dw = any(need_dw)
+    Y = torch.empty((npix, yc), dtype=torch.float32, device=dev)
+    G = torch.empty((npix, yc + 4), dtype=torch.float32, device=dev) if any_dw else None
+    dx = torch.empty((B, h, w, c_in), dtype=torch.float32, device=dev) if need_dx else None
+    reduc_backward(x2d, B, h, w, c_in, c_first, packs[1], packs[2], max_depth, upratio, grad_out.contiguous(), Y, G,
+                   None if dx is None else dx.view(npix, c_in))
+    dws = []
+    for l, (wt, (c0, width)) in enumerate(zip(weights, cols)):
+        if not need_dw[l]:
+            dws.append(None)
+            continue
+        cin_l = wt.shape[1]
+        src = x2d[:, :cin_l] if l == 0 else Y[:, cols[l - 1][0]:cols[l - 1][0] + cin_l]
+        g = conv_wgrad(src, B, h, w, cin_l, G[:, c0:c0 + width], width, 1, ws=ws, tag="reduc.wgrad")
+        dws.append(g[:wt.shape[0]].reshape(wt.shape[0], cin_l, 1, 1))
+    return dx, dws
+
+
+def _check_train_chain(weights, upratio):
+    c_in, c_first = weights[0].shape[1], weights[0].shape[0]
+    if not reduc_train_supported(c_in, c_first, upratio):
+        raise BtsHipError("reduction training kernels: chain (%d,%d) at upratio %d is not built" % (c_in, c_first, upratio))
+    return c_in, c_first
+
+
+class ReducLpgFunction(torch.autograd.Function):
+    """One LPG scale of the decoder in train() mode as ONE autograd node: forward is the inference launch
+    (bts_reduc_lpg_fwd_f32, reduction_1x1 -> normalize -> LPG -> /max_depth), backward bts_reduc_bwd_f32 plus one
+    bts_conv_wgrad_f32 per layer.  x: [B,C,h,w] (channels_last is read in place); packs: reduc_train_packs(weights);
+    abs_min: optional 0-d tensor that receives min |den|; ws: optional wgrad split workspace.  Returns depth_scaled
+    [B,1,h*k,w*k]."""
+
+    @staticmethod
+    def forward(ctx, x, max_depth, upratio, packs, abs_min, ws, *weights):
+        c_in, c_first = _check_train_chain(weights, int(upratio))
+        if int(upratio) == 0:
+            raise BtsHipError("ReducLpgFunction: upratio must be 8, 4 or 2 (the final chain is ReducFinalFunction)")
+        _need(x, "ReducLpgFunction")
+        B, C, h, w = x.shape
+        if C != c_in:
+            raise BtsHipError("ReducLpgFunction: input has %d channels, the chain reads %d" % (C, c_in))
+        k = int(upratio)
+        x2d, _ = nhwc_rows(x.detach())
+        out = torch.empty((B, 1, h * k, w * k), dtype=torch.float32, device=x.device)
+        reduc_lpg_forward(x2d[:, :c_in], B, h, w, c_in, c_first, packs[0], max_depth, k, out, abs_min=abs_min)
+        ctx.save_for_backward(x2d, *weights)
+        ctx.cfg = (B, h, w, float(max_depth), k, packs, ws)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        x2d, *weights = ctx.saved_tensors
+        B, h, w, md, k, packs, ws = ctx.cfg
+        dx, dws = reduc_train_backward(x2d, B, h, w, weights, packs, md, k, grad_out, ctx.needs_input_grad[0],
+                                       ctx.needs_input_grad[6:], ws)
+        return (None if dx is None else dx.permute(0, 3, 1, 2), None, None, None, None, None) + tuple(dws)
+
+
+class ReducFinalFunction(torch.autograd.Function):
+    """reduc1x1 (the final chain, 32 -> 16 -> 8 -> 1 + sigmoid) in train() mode as one autograd node: forward
+    bts_reduc_fwd_f32, backward bts_reduc_bwd_f32 + one wgrad per layer.  Returns [B,1,h,w]."""
+
+    @staticmethod
+    def forward(ctx, x, max_depth, packs, ws, *weights):
+        c_in, c_first = _check_train_chain(weights, 0)
+        _need(x, "ReducFinalFunction")
+        B, C, h, w = x.shape
+        if C != c_in:
+            raise BtsHipError("ReducFinalFunction: input has %d channels, the chain reads %d" % (C, c_in))
+        x2d, _ = nhwc_rows(x.detach())
+        out = torch.empty((B, 1, h, w), dtype=torch.float32, device=x.device)
+        reduc_forward_nhwc(x2d[:, :c_in], c_in, c_first, packs[0], max_depth, True, False, out)
+        ctx.save_for_backward(x2d, *weights)
+        ctx.cfg = (B, h, w, float(max_depth), packs, ws)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        x2d, *weights = ctx.saved_tensors
+        B, h, w, md, packs, ws = ctx.cfg
+        dx, dws = reduc_train_backward(x2d, B, h, w, weights, packs, md, 0, grad_out, ctx.needs_input_grad[0],
+                                       ctx.needs_input_grad[4:], ws)
+        return (None if dx is None else dx.permute(0, 3, 1, 2), None, None, None) + tuple(dws)
 
 
 # ---------------------------------------------------------------------------- layout

@@ -53,21 +53,7 @@ def _splitk_workspace(device: torch.device) -> torch.Tensor:
     return ws
 
 
-def _nhwc_rows(x: torch.Tensor) -> Tuple[torch.Tensor, int]:
-    """[B,C,H,W] (any strides) -> ([B*H*W, C4] NHWC rows with C padded to a multiple of 4, C4).
-    A channels_last tensor with C % 4 == 0 is viewed, not copied -- and so is a CHANNEL SLICE of one (what autograd hands
-    back for the inputs of a torch.cat, and what a dense block's layers read): the kernels take a pixel stride."""
-    B, C, H, W = x.shape
-    c4 = ops.round_up(C, 4)
-    if c4 == C and B * H * W > 0 and x.stride(1) == 1 and W > 1 and H > 1:
-        ct = x.stride(3)
-        if (ct >= C and ct % 4 == 0 and x.stride(2) == W * ct and (B == 1 or x.stride(0) == H * W * ct)
-                and x.data_ptr() % 16 == 0):
-            return x.as_strided((B * H * W, C), (ct, 1)), c4
-    rows = x.permute(0, 2, 3, 1)
-    if c4 != C:
-        rows = F.pad(rows, (0, c4 - C))
-    return rows.contiguous().view(B * H * W, c4), c4
+_nhwc_rows = ops.nhwc_rows
 
 
 class WeightPacker:
@@ -456,6 +442,35 @@ def reduction_forward(m, net):
     return torch.stack([sin_t * torch.cos(phi), sin_t * torch.sin(phi), torch.cos(theta), dist], dim=1)
 
 
+# ---- fused reduction scales (decoder.fused_reduction_train): one forward launch, one backward-data launch and one
+# weight-gradient launch per layer instead of the layer-by-layer graph above
+def _reduc_weights(m):
+    return [c.weight for c in m.reduc.modules() if isinstance(c, torch.nn.Conv2d)]
+
+
+def fused_reduction_available(m, upratio: int) -> bool:
+    """Whether the fused training kernels cover this reduction_1x1 module at this upratio (0: the final chain).  The
+    chains of bts_size 256 are not built: the caller stays on the layer-by-layer path for them."""
+    return bool(m.is_final) == (upratio == 0) and ops.reduc_train_supported(m.c_in, m.c_first_out, upratio)
+
+
+def fused_lpg_scale(reduc_mod, lpg_mod, feat):
+    """reduction_1x1 -> F.normalize -> LPG -> /max_depth of one scale (bts.py:249-256) as one autograd node."""
+    refuse_bf16("train.fused_lpg_scale")
+    am = torch.empty((), dtype=torch.float32, device=feat.device)
+    depth = ops.ReducLpgFunction.apply(feat, reduc_mod.max_depth, int(lpg_mod.upratio), reduc_mod.packed_train(), am,
+                                       _workspace(feat.device), *_reduc_weights(reduc_mod))
+    lpg_mod.abs_min = am
+    return depth
+
+
+def fused_reduction_final(reduc_mod, feat):
+    """reduc1x1 (bts.py:285): the final chain and its sigmoid as one autograd node."""
+    refuse_bf16("train.fused_reduction_final")
+    return ops.ReducFinalFunction.apply(feat, reduc_mod.max_depth, reduc_mod.packed_train(), _workspace(feat.device),
+                                        *_reduc_weights(reduc_mod))
+
+
 def _conv_elu(seq, x, tag):
     return conv2d(x, seq[0].weight, padding=1, tag=tag, act=ops.ACT_ELU)
 
@@ -486,7 +501,11 @@ def _decoder_forward(dec, features, focal):
         inp = grown
     daspp_feat = _conv_elu(dec.daspp_conv, torch.cat([iconv4] + branches, 1), "daspp_conv")
 
+    fused = bool(getattr(dec, "fused_reduction_train", False))
+
     def lpg_scale(reduc_mod, lpg_mod, feat):
+        if fused and fused_reduction_available(reduc_mod, int(lpg_mod.upratio)):
+            return fused_lpg_scale(reduc_mod, lpg_mod, feat)
         r = reduction_forward(reduc_mod, feat)
         plane_eq = torch.cat([F.normalize(r[:, :3], 2, 1), r[:, 3:4]], 1).contiguous()
         return lpg_mod(plane_eq, focal).unsqueeze(1) / md
@@ -499,7 +518,10 @@ def _decoder_forward(dec, features, focal):
     iconv2 = _conv_elu(dec.conv2, torch.cat([x, skip0, depth_4x4[:, :, ::2, ::2]], 1), "conv2")
     depth_2x2 = lpg_scale(dec.reduc2x2, dec.lpg2x2, iconv2)
     upconv1 = upconv_forward(dec.upconv1, iconv2)
-    reduc1x1 = reduction_forward(dec.reduc1x1, upconv1)
+    if fused and fused_reduction_available(dec.reduc1x1, 0):
+        reduc1x1 = fused_reduction_final(dec.reduc1x1, upconv1)
+    else:
+        reduc1x1 = reduction_forward(dec.reduc1x1, upconv1)
     iconv1 = _conv_elu(dec.conv1, torch.cat([upconv1, reduc1x1, depth_2x2, depth_4x4, depth_8x8], 1), "conv1")
     final_depth = md * torch.sigmoid(conv2d(iconv1, dec.get_depth[0].weight, padding=1, tag="get_depth"))
     if dec.params.dataset == 'kitti':

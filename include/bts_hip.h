@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define BTS_HIP_ABI_VERSION 16
+#define BTS_HIP_ABI_VERSION 17
 
 #define BTS_ERR_INVALID      (-1)   /* bad argument (null pointer, non-positive dim, misalignment) */
 #define BTS_ERR_UNSUPPORTED  (-2)   /* valid in the reference but not built here (e.g. odd upratio)  */
@@ -106,6 +106,38 @@ int bts_reduc_fwd_f32(const float* x, long x_pix_stride, long npix, int c_in, in
 int bts_reduc_lpg_fwd_f32(const float* x, long x_pix_stride, int B, int h, int w, int c_in, int c_first_out,
                           const float* w_frag, long w_frag_floats, float max_depth, int upratio,
                           float* plane4, float* depth_scaled, float* ds_out, float* abs_min, bts_stream_t stream);
+
+/* Backward-data of one reduction_1x1 scale for training callers: the gradient that autograd through
+ * pytorch/bts.py:124-136 + F.normalize + local_planar_guidance + /max_depth (bts.py:249-256, 263-270, 277-283) hands to the
+ * chain's input, plus the two row buffers from which bts_conv_wgrad_f32 computes every layer's weight gradient.
+ *   x, B, h, w   : as bts_reduc_lpg_fwd_f32 (final chain: the map itself, npix = B*h*w)
+ *   (c_in, c_first_out, upratio) : (128,128,8), (128,64,4), (64,32,2), or the final chain (32,16) with upratio 0;
+ *                  anything else returns BTS_ERR_UNSUPPORTED
+ *   w_frag       : the chain's weights in the 32x32x2 fragment order for EVERY chain (ops.pack_reduc_weights(..., wide=True);
+ *                  the forward entry points take the narrow chains in the 16x16x4 order instead)
+ *   wt_frag      : the transposed weights W_l^T in reverse layer order, the last layer's 3 (1) outputs zero-padded to 8
+ *                  columns, in the same fragment order (ops.pack_reduc_weights_bwd)
+ *   grad_out     : upratio > 0: gradient of depth_scaled, contiguous [B,1,h*k,w*k]; final: gradient of the sigmoid output [B,1,h,w]
+ *   dx           : optional [npix, c_in] rows at dx_pix_stride (a multiple of 4, >= c_in); columns >= c_in are not written
+ *   Y            : [npix, YC] packed rows, the hidden layers' post-ELU activations (recomputed), layer l at the columns below
+ *   G            : optional [npix, YC + 4] packed rows, the gradient w.r.t. every layer's pre-activation; the last layer's
+ *                  3 (1) values sit in the last 4 columns, zero-padded
+ *   column tables (layer: first column, width), YC = width of Y:
+ *     (128,128): 128->128: 0,128   128->64: 128,64   64->32: 192,32   32->16: 224,16   16->8: 240,8   [G: 8->3: 248,4]   YC 248
+ *     (128, 64): 128->64:  0,64    64->32:  64,32    32->16: 96,16    16->8:  112,8    [G: 8->3: 120,4]                   YC 120
+ *     ( 64, 32): 64->32:   0,32    32->16:  32,16    16->8:  48,8     [G: 8->3: 56,4]                                     YC 56
+ *     ( 32, 16): 32->16:   0,16    16->8:   16,8     [G: 8->1: 24,4]                                                      YC 24
+ *   Layer l's weight gradient is bts_conv_wgrad_f32 (ksize 1) with dy = G's columns of layer l and x = Y's columns of
+ *   layer l-1 (the chain's input for the first layer).  No atomics: dx, G and Y are bit-reproducible.  All pointers 16-byte aligned.
+ */
+int bts_reduc_bwd_f32(const float* x, long x_pix_stride, int B, int h, int w, int c_in, int c_first_out,
+                      const float* w_frag, long w_frag_floats, const float* wt_frag, long wt_frag_floats,
+                      float max_depth, int upratio, const float* grad_out, float* dx, long dx_pix_stride,
+                      float* G, float* Y, bts_stream_t stream);
+
+/* The most waves bts_reduc_bwd_f32 launches for a chain (its grid cap x 8 waves; each wave walks 32-pixel tiles in a
+ * grid-stride loop), or BTS_ERR_UNSUPPORTED.  Host arithmetic only. */
+long bts_reduc_bwd_max_waves(int c_in, int c_first_out, int upratio);
 
 /* ------------------------------------------------------------------------------------------
  * NHWC implicit-GEMM convolution on fp32-input MFMA (v_mfma_f32_32x32x2_f32), with fused

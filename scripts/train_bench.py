@@ -33,6 +33,8 @@ def main():
     ap.add_argument("--decoder-only", action="store_true")
     ap.add_argument("--no-freeze", action="store_true", help="train every encoder parameter (the reference freezes some)")
     ap.add_argument("--native-loss", action="store_true", help="silog on the HIP loss kernels (no host sync) instead of torch")
+    ap.add_argument("--fused-reduc", action="store_true",
+                    help="reduction_1x1 -> LPG scales and reduc1x1 as single autograd nodes on the fused kernels (fused_reduction_train)")
     a = ap.parse_args()
     # BASELINE config 5 (B=32 over 8 GPUs = 4 per GPU, DDP): launch with
     #   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 scripts/train_bench.py
@@ -53,6 +55,7 @@ def main():
     torch.manual_seed(0)
     params = Params(a.encoder, 512, 80.0, "kitti")
     model = M.BtsModel(params).train().to(dev)
+    model.fused_reduction_train = a.fused_reduc
     loss_fn = M.silog_loss(0.85, native=a.native_loss)
     if not a.no_freeze:
         trainer.set_misc(model, a.encoder)          # the reference freezes the stem conv and the encoder norm affines
@@ -99,7 +102,8 @@ def main():
     res = dict(metric="training step ms (fwd+loss+bwd+AdamW)", ms_per_step=ms, frames_per_s=world * B / ms * 1e3,
                n_gpus=world, ddp=use_dist,
                loss="silog native (HIP)" if a.native_loss else "silog torch",
-               config=dict(encoder=a.encoder, batch_per_gpu=B, height=H, width=W, decoder_only=a.decoder_only),
+               config=dict(encoder=a.encoder, batch_per_gpu=B, height=H, width=W, decoder_only=a.decoder_only,
+                           fused_reduc=a.fused_reduc),
                peak_mem_gb=torch.cuda.max_memory_allocated() / 2**30)
     if a.trace:
         tr = ops.KernelTrace()
@@ -118,6 +122,9 @@ def main():
         for k, r in rows.items():
             r["tflops"] = r["flops"] / max(r["ms"], 1e-9) / 1e9
         res["kernels"] = rows
+        # the reduction scales on their own (library launches only: the torch elementwise kernels between them are not traced)
+        res["reduction_launches"] = {"%s %s" % (kern, tag): dict(ms=v["ms"], launches=v["launches"])
+                                     for kern, d in summ.items() for tag, v in d["tags"].items() if tag.startswith("reduc")}
         top = []
         for kern, d in summ.items():
             for tag, v in d["tags"].items():
