@@ -21,6 +21,7 @@ SYMBOLS = (
     "bts_reduc_lpg_fwd_f32", "bts_plan_run", "bts_upconv_combine_f32",
     "bts_depth_loss_ws_doubles", "bts_depth_loss_fwd_f32", "bts_depth_loss_bwd_f32",
     "bts_reduc_bwd_f32", "bts_reduc_bwd_max_waves",
+    "bts_conv_wgrad_batch_table_bytes", "bts_conv_wgrad_batch_plan_f32", "bts_conv_wgrad_batch_f32",
 )
 
 ABI_VERSION = 17
@@ -54,6 +55,11 @@ class ConvWgradDesc(C.Structure):
         ("dw", C.c_void_p), ("ws", C.c_void_p), ("ws_floats", C.c_long), ("n_bundles", C.c_int),
         ("pre_scale", C.c_void_p), ("pre_shift", C.c_void_p), ("pre_relu", C.c_int),
     ]
+
+
+class ConvWgradBatchItem(C.Structure):
+    """struct bts_conv_wgrad_batch_item (include/bts_hip.h)."""
+    _fields_ = [("bm", C.c_int), ("bn", C.c_int), ("split", C.c_long), ("pix_per_split", C.c_long), ("ws_offset", C.c_long)]
 
 
 class BtsHipError(RuntimeError):
@@ -146,6 +152,13 @@ def load_real():
     lib.bts_conv_wgrad_plan_f32.restype = i
     lib.bts_conv_wgrad_plan_f32.argtypes = [C.POINTER(ConvWgradDesc), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_long),
                                             C.POINTER(C.c_long)]
+    lib.bts_conv_wgrad_batch_table_bytes.restype = l
+    lib.bts_conv_wgrad_batch_table_bytes.argtypes = [i]
+    lib.bts_conv_wgrad_batch_plan_f32.restype = i
+    lib.bts_conv_wgrad_batch_plan_f32.argtypes = [C.POINTER(ConvWgradDesc), i, C.POINTER(vp), C.POINTER(l), i, l, vp,
+                                                  C.POINTER(ConvWgradBatchItem)]
+    lib.bts_conv_wgrad_batch_f32.restype = i
+    lib.bts_conv_wgrad_batch_f32.argtypes = [vp, vp, i, C.POINTER(vp), i, vp, vp]
     lib.bts_bn_train_ws_floats.restype = l
     lib.bts_bn_train_ws_floats.argtypes = [l, i]
     lib.bts_bn_train_stats_f32.restype = i

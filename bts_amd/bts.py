@@ -371,6 +371,8 @@ class bts(nn.Module):
         self.fused_reduction_train = False              # train() mode: True runs each reduction_1x1 -> LPG scale and reduc1x1 as one
                                                         # autograd node on the fused kernels (train.fused_lpg_scale);
                                                         # chains the library does not build (bts_size 256) keep the layer graph
+        self.batched_wgrad = False                      # train() mode, with fused_reduction_train: True computes the weight
+                                                        # gradients of one scale's layers in one batched launch (ops.WgradBatch)
 
     # ------------------------------------------------------------------ weight packing (lazy)
     _OWN = ("bn5", "conv5", "bn4", "conv4", "bn4_2", "daspp_conv", "bn3", "conv3", "bn2", "conv2", "conv1", "get_depth")
@@ -600,6 +602,8 @@ class encoder(nn.Module):
         self.base_model = build_base_model(params.encoder)
         names, channels = self.TAPS.get(params.encoder, self.RESNET_TAPS)
         self.feat_names, self.feat_out_channels = list(names), list(channels)
+        self.batched_wgrad = False          # train() mode: True defers the weight gradients of a DenseNet block to the end
+                                            # of its backward walk and computes them in one batched launch (train._DenseBlockFn)
 
     def forward(self, x):
         """[x, tap@1/2, tap@1/4, tap@1/8, tap@1/16, tap@1/32]: run the backbone's children in order and keep the outputs
@@ -659,6 +663,16 @@ class BtsModel(nn.Module):
     @fused_reduction_train.setter
     def fused_reduction_train(self, on: bool):
         self.decoder.fused_reduction_train = bool(on)
+
+    @property
+    def batched_wgrad(self) -> bool:
+        """One multi-problem weight-gradient launch per DenseNet block and per fused reduction scale instead of one
+        launch per layer (encoder.batched_wgrad and bts.batched_wgrad, set together), default False."""
+        return self.encoder.batched_wgrad and self.decoder.batched_wgrad
+
+    @batched_wgrad.setter
+    def batched_wgrad(self, on: bool):
+        self.encoder.batched_wgrad = self.decoder.batched_wgrad = bool(on)
 
     def _native_ok(self, x):
         return (self.native_encoder and not self.training and isinstance(x, torch.Tensor) and x.is_cuda

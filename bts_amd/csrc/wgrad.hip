@@ -10,6 +10,33 @@
 // K is the long axis (B*H*W up to 6.8 M pixels) and the output is small, so the launch splits K over gridDim.y;
 // partials go to a workspace and are summed in a fixed order (deterministic, no atomics); plan_wgrad picks the tile
 // (128x128 / 64x128 / 32x128 / 64x64) and the split together.
+//
+// bts_conv_wgrad_batch_f32 runs many such problems (a DenseNet block's 2*L weight gradients) in one launch per tile
+// shape plus one reduction launch; its planner sees the whole batch.
+// Batch planner, the rule kept:
+//   tile   per problem, by the single planner's shape terms alone: useful fraction of the padded tile grid x per-tile
+//          efficiency.  Its chip-fill and partial-traffic terms are properties of the whole batch here, not of a tile.
+//   split  one pixel quantum q (a multiple of 32 pixels, at least 4 K-steps) for the whole batch: split_i =
+//          ceil(M_i / q), within the single planner's limits (>= 4 K-steps per split unless M is smaller, <= 1024), then
+//          settled as there (pix_per_split rounded up to 32, no empty split).  q is the LARGEST quantum at which the batch
+//          still has >= max(768, T / 128) workgroups, T = sum of tiles_i x K-steps_i: 768 is the single planner's target
+//          (three per CU, two resident); T / 128 asks for workgroups of about 128 K-steps (4096 pixels) once the batch
+//          has work for more than 768 of them.  A batch that has that many workgroups unsplit is not split at all.  One
+//          quantum rather than one split count makes every workgroup of the batch walk about the same number of pixels
+//          whatever its problem's M; the largest such q is the least partial traffic that fills the chip.  Why not a
+//          flat 768: all workgroups of a batch take about equally long, so the grid runs in rounds of the 512 resident
+//          ones and a batch of 800 pays for two rounds.  Measured so (MI355X, DenseNet161 at 4x352x704): block 1 as 810
+//          workgroups of 323 K-steps and block 2 as 990 of 162 ran at 0.76x / 0.79x the speed of their single launches;
+//          at ~128 K-steps a long batch runs several rounds and the last, partly filled one costs less (0.97x / 0.93x), while
+//          blocks 3 and 4 (121 / 31 K-steps unsplit, 3078 / 2484 tiles) stay unsplit (DESIGN.md 3a has the tables).
+//   ws     if the partials at that q exceed the workspace, q grows to the smallest quantum whose partials fit (none
+//          at all in the limit): lack of workspace lowers splits, it never fails.
+//   order  inside a tile shape's grid, problems whose workgroups walk the most K-steps come first (dispatched first);
+//          ties are broken by shape, then by position.  Tile, split and pix_per_split of a problem therefore do not depend
+//          on the batch order at all; ws_offset is handed out in that order, so among problems of EQUAL shape it goes by
+//          position: permuting a batch permutes the offsets of equal-shape problems among themselves, and the set of
+//          workspace regions stays the same.
+// Everything above reads shapes and ws_floats only.
 #include "common.h"
 #include <stdint.h>
 
@@ -33,9 +60,12 @@ struct WgradArgs {
                                  // [j*c_in, ..), gradient channels [j*c_out, ..) and writes dense block j of [c_out][N]
 };
 
-// One workgroup = 4 waves arranged WM x WN over a BM x BN tile of dw; each wave owns (BM/WM) x (BN/WN).
+// One workgroup = 4 waves arranged WM x WN over a BM x BN tile of dw; each wave owns (BM/WM) x (BN/WN).  The body is
+// shared by the single-problem launch (tile / split / bundle = blockIdx.x / .y / .z) and the batched launch (all three
+// derived from the workgroup's rank inside its problem).
 template <int BM, int BN, int WM, int WN>
-__global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const WgradArgs a) {
+__device__ __forceinline__ void wgrad_tile(const WgradArgs& a, const unsigned tile, const unsigned split_idx,
+                                           const unsigned bundle) {
     static_assert(WM * WN == 4, "4 waves");
     constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
     static_assert(TM >= 1 && TN >= 1, "wave tile must be at least 32x32");
@@ -51,10 +81,10 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const WgradArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm0 = (wave / WN) * (BM / WM), wn0 = (wave % WN) * (BN / WN);
     const int l31 = lane & 31, khalf = lane >> 5;
-    const int tile_n = blockIdx.x % a.n_ntiles, tile_m = blockIdx.x / a.n_ntiles;
+    const int tile_n = tile % a.n_ntiles, tile_m = tile / a.n_ntiles;
     const int m0 = tile_m * BM, n0 = tile_n * BN;
-    const float* __restrict__ xg = a.x + (size_t)blockIdx.z * a.c_in;      // this bundle's channel slice
-    const float* __restrict__ dyg = a.dy + (size_t)blockIdx.z * a.c_out;
+    const float* __restrict__ xg = a.x + (size_t)bundle * a.c_in;      // this bundle's channel slice
+    const float* __restrict__ dyg = a.dy + (size_t)bundle * a.c_out;
 
     // ---- loader roles (fixed for the whole K walk) ----
     const int a_col = (tid % ACOLS) * 4, a_row = tid / ACOLS;
@@ -68,7 +98,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const WgradArgs a) {
     const int ky = tap / a.ksize, kx = tap - ky * a.ksize;
     const int off_y = ky * a.dil - a.pad, off_x = kx * a.dil - a.pad;
 
-    const unsigned k_begin = blockIdx.y * a.pix_per_split;
+    const unsigned k_begin = split_idx * a.pix_per_split;
     const unsigned k_end = min(a.M, k_begin + a.pix_per_split);
     const int n_it = k_begin < k_end ? (int)((k_end - k_begin + WBK - 1) / WBK) : 0;
     const unsigned HW = (unsigned)a.H * (unsigned)a.W;
@@ -79,7 +109,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const WgradArgs a) {
     f32x4 psc = {1.f, 1.f, 1.f, 1.f}, psh = {0.f, 0.f, 0.f, 0.f};          // this thread's four input channels never change
     const bool has_pre = a.pre_scale != nullptr;
     if (has_pre) {
-        const int cpre = blockIdx.z * a.c_in + ci;
+        const int cpre = bundle * a.c_in + ci;
         psc = *reinterpret_cast<const f32x4*>(a.pre_scale + cpre);
         psh = *reinterpret_cast<const f32x4*>(a.pre_shift + cpre);
     }
@@ -174,7 +204,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const WgradArgs a) {
     }
 
     // ---- store: D register r of lane l is row (r&3) + 8*(r>>2) + 4*(l>>5), column l&31 ----
-    float* out = a.out + ((size_t)blockIdx.y * a.n_bundles + blockIdx.z) * a.c_out * a.N;
+    float* out = a.out + ((size_t)split_idx * a.n_bundles + bundle) * a.c_out * a.N;
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -186,6 +216,11 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const WgradArgs a) {
                 if (m < a.c_out && n < a.N) out[(size_t)m * a.N + n] = acc[i][j][r];
             }
         }
+}
+
+template <int BM, int BN, int WM, int WN>
+__global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const WgradArgs a) {
+    wgrad_tile<BM, BN, WM, WN>(a, blockIdx.x, blockIdx.y, blockIdx.z);
 }
 
 // Sum the ksplit partial tiles in a fixed order.  The output is small and the split count can be in the hundreds, so
@@ -341,6 +376,359 @@ extern "C" int bts_conv_wgrad_plan_f32(const bts_conv_wgrad_desc* d, int* bm, in
     if (bn) *bn = WGRAD_BN[p.variant];
     if (split) *split = p.split;
     if (pix_per_split) *pix_per_split = (long)a.pix_per_split;
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Many problems in one launch (bts_conv_wgrad_batch_*, include/bts_hip.h).  One grid per tile shape covers every problem
+// of the batch that uses that tile; a workgroup finds its problem by binary search over a prefix sum of workgroups in a
+// device table (the way pack_weights_kernel finds its entry), derives (tile, split, bundle) from its rank inside the
+// problem and runs wgrad_tile.  The table stores (base index, byte offset) for every pointer, the launch receives the
+// base pointers by value: one upload per geometry serves every later step.
+//
+// The batch planner's rule is in this file's header comment.
+namespace {
+
+struct WgradBatchEntry {
+    long x_off, dy_off, dw_off, sc_off, sh_off;   // byte offsets into their base ranges
+    long ws_off;                                   // floats into the batch workspace (split > 1)
+    long x_pix_stride, dy_pix_stride;
+    long first_wg;                                 // prefix sum of workgroups over the entries of this tile shape
+    long first_red;                                // prefix sum of reduction blocks over the whole table
+    int x_base, dy_base, dw_base, sc_base, sh_base;   // sc_base < 0: no prologue
+    int c_in, c_out, N, B, h_in, w_in, Hs, Ws, ups, H, W, ksize, dil, stride, pad;
+    unsigned M, pix_per_split;
+    int n_ntiles, tiles, split, n_bundles, pre_relu, variant;
+};
+
+constexpr long WGRAD_BATCH_MAGIC = 0x4254535747424131L;
+constexpr int WGRAD_MAX_BASES = 8;
+
+struct WgradBatchHeader {
+    long magic;
+    int n, n_bases;
+    int first[5];          // entries [first[v], first[v+1]) use tile shape v
+    int reserved;
+    long wgs[4];           // workgroups of each tile shape's grid
+    long red_blocks;       // blocks of the reduction launch (0: no problem is split)
+    long ws_used;          // floats of the workspace the launch writes
+    long reserved2;
+};
+static_assert(sizeof(WgradBatchHeader) % 16 == 0 && sizeof(WgradBatchEntry) % 8 == 0, "table layout");
+
+struct WgradBases { const char* p[WGRAD_MAX_BASES]; };
+
+__device__ __forceinline__ const char* wgrad_base(const WgradBases& b, int i) {   // uniform selects, no indexed kernarg
+    const char* p = b.p[0];
+#pragma unroll
+    for (int j = 1; j < WGRAD_MAX_BASES; ++j) p = i == j ? b.p[j] : p;
+    return p;
+}
+
+template <int BM, int BN, int WM, int WN>
+__global__ __launch_bounds__(256, 2) void conv_wgrad_batch_kernel(const WgradBatchEntry* __restrict__ table, int n,
+                                                                  const WgradBases bases, float* __restrict__ ws) {
+    int lo = 0, hi = n - 1;                       // the entry whose workgroup range holds blockIdx.x
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (table[mid].first_wg <= (long)blockIdx.x) lo = mid; else hi = mid - 1;
+    }
+    const WgradBatchEntry& e = table[lo];         // uniform: read once, into scalar registers
+    WgradArgs a;
+    a.x = reinterpret_cast<const float*>(wgrad_base(bases, e.x_base) + e.x_off);
+    a.dy = reinterpret_cast<const float*>(wgrad_base(bases, e.dy_base) + e.dy_off);
+    a.out = e.split > 1 ? ws + e.ws_off
+                        : reinterpret_cast<float*>(const_cast<char*>(wgrad_base(bases, e.dw_base)) + e.dw_off);
+    a.x_pix_stride = e.x_pix_stride; a.dy_pix_stride = e.dy_pix_stride;
+    a.c_in = e.c_in; a.c_out = e.c_out; a.N = e.N;
+    a.B = e.B; a.h_in = e.h_in; a.w_in = e.w_in; a.Hs = e.Hs; a.Ws = e.Ws; a.ups = e.ups; a.H = e.H; a.W = e.W;
+    a.ksize = e.ksize; a.dil = e.dil; a.stride = e.stride; a.pad = e.pad;
+    a.M = e.M; a.pix_per_split = e.pix_per_split; a.n_ntiles = e.n_ntiles;
+    const bool has_pre = e.sc_base >= 0;
+    a.pre_scale = has_pre ? reinterpret_cast<const float*>(wgrad_base(bases, e.sc_base) + e.sc_off) : nullptr;
+    a.pre_shift = has_pre ? reinterpret_cast<const float*>(wgrad_base(bases, e.sh_base) + e.sh_off) : nullptr;
+    a.pre_relu = e.pre_relu;
+    a.n_bundles = e.n_bundles;
+    const unsigned rank = (unsigned)((long)blockIdx.x - e.first_wg);      // < tiles * split * n_bundles
+    const unsigned tile = rank % (unsigned)e.tiles, rest = rank / (unsigned)e.tiles;
+    wgrad_tile<BM, BN, WM, WN>(a, tile, rest % (unsigned)e.split, rest / (unsigned)e.split);
+}
+
+// wgrad_reduce_kernel for every split problem of a batch in one launch: the block finds its problem in the table, then
+// sums exactly as wgrad_reduce_kernel does (lane j adds splits j, j+16, ..., then the 16 lane sums in order).
+__global__ __launch_bounds__(256) void wgrad_reduce_batch_kernel(const WgradBatchEntry* __restrict__ table, int n,
+                                                                 const WgradBases bases, const float* __restrict__ ws_all) {
+    int lo = 0, hi = n - 1;      // unsplit problems own no blocks: the last entry at or below blockIdx.x is never one
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (table[mid].first_red <= (long)blockIdx.x) lo = mid; else hi = mid - 1;
+    }
+    const WgradBatchEntry& e = table[lo];
+    const long count4 = (long)e.c_out * e.N * e.n_bundles / 4;
+    const int ksplit = e.split;
+    const float* ws = ws_all + e.ws_off;
+    float* dw = reinterpret_cast<float*>(const_cast<char*>(wgrad_base(bases, e.dw_base)) + e.dw_off);
+    const int el = threadIdx.x & 15, lane = threadIdx.x >> 4;
+    const long t = ((long)blockIdx.x - e.first_red) * 16 + el;
+    const long tt = t < count4 ? t : count4 - 1;
+    const f32x4* p = reinterpret_cast<const f32x4*>(ws) + tt;
+    f32x4 v = (f32x4)(0.f);
+    int s = lane;
+    for (; s + 48 < ksplit; s += 64) {
+        const f32x4 a0 = p[(size_t)s * count4], a1 = p[(size_t)(s + 16) * count4];
+        const f32x4 a2 = p[(size_t)(s + 32) * count4], a3 = p[(size_t)(s + 48) * count4];
+        v += (a0 + a1) + (a2 + a3);
+    }
+    for (; s < ksplit; s += 16) v += p[(size_t)s * count4];
+    __shared__ f32x4 red[16][16];
+    red[lane][el] = v;
+    __syncthreads();
+    if (lane == 0 && t < count4) {
+        f32x4 r = red[0][el];
+#pragma unroll
+        for (int j = 1; j < 16; ++j) r += red[j][el];
+        reinterpret_cast<f32x4*>(dw)[t] = r;
+    }
+}
+
+template <int BM, int BN, int WM, int WN>
+int launch_wgrad_batch(const WgradBatchEntry* entries, int n, long wgs, const WgradBases& bases, float* ws, hipStream_t s) {
+    const size_t lds_bytes = (size_t)2 * WBK * (BM + BN) * sizeof(float);
+    auto kern = conv_wgrad_batch_kernel<BM, BN, WM, WN>;
+    static std::atomic<unsigned long long> lds_set{0};     // per instantiation: one bit per device (common.h)
+    if (hipError_t e = bts_ensure_dynamic_lds((const void*)kern, lds_bytes, lds_set); e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(kern, dim3((unsigned)wgs), dim3(256), lds_bytes, s, entries, n, bases, ws);
+    return (int)hipGetLastError();
+}
+
+// The tile of one problem inside a batch: the single planner's shape terms (see the rule above).
+inline int wgrad_batch_variant(int c_out, int N) {
+    static const double eff[4] = {1.0, 0.9, 0.75, 0.8};
+    int best = 0;
+    double best_score = -1.0;
+    for (int v = 0; v < 4; ++v) {
+        const long mt = (c_out + WGRAD_BM[v] - 1) / WGRAD_BM[v], nt = (N + WGRAD_BN[v] - 1) / WGRAD_BN[v];
+        const double useful = (double)c_out * N / ((double)mt * WGRAD_BM[v] * nt * WGRAD_BN[v]);
+        const double score = useful * eff[v];
+        if (score > best_score * 1.0001) { best_score = score; best = v; }
+    }
+    return best;
+}
+
+// Split of an M-pixel problem at a quantum of qs K-steps, settled as prepare_wgrad settles it.
+inline void wgrad_batch_split(long M, long qs, long& split, long& pps) {
+    long max_split = M / (4 * WBK);
+    if (max_split > 1024) max_split = 1024;
+    if (max_split < 1) max_split = 1;
+    split = (M + qs * WBK - 1) / (qs * WBK);
+    if (split > max_split) split = max_split;
+    pps = ((M + split - 1) / split + WBK - 1) / WBK * WBK;
+    split = (M + pps - 1) / pps;
+}
+
+// Byte range [p, p + bytes) inside one of the declared bases: its index and offset.
+inline bool wgrad_resolve(const void* p, double bytes, const void* const* bases, const long* base_bytes, int n_bases, int& idx,
+                          long& off) {
+    const uintptr_t u = (uintptr_t)p;
+    for (int j = 0; j < n_bases; ++j) {
+        const uintptr_t b = (uintptr_t)bases[j];
+        if (u >= b && (double)(u - b) + bytes <= (double)base_bytes[j]) { idx = j; off = (long)(u - b); return true; }
+    }
+    return false;
+}
+
+}  // namespace
+
+extern "C" long bts_conv_wgrad_batch_table_bytes(int n) {
+    if (n < 0) return -1;
+    return (long)sizeof(WgradBatchHeader) + (long)n * (long)sizeof(WgradBatchEntry);
+}
+
+extern "C" int bts_conv_wgrad_batch_plan_f32(const bts_conv_wgrad_desc* descs, int n, const void* const* bases,
+                                             const long* base_bytes, int n_bases, long ws_floats, void* table_host,
+                                             bts_conv_wgrad_batch_item* plan) {
+    if (n < 0 || n_bases < 0 || n_bases > WGRAD_MAX_BASES || ws_floats < 0 || !table_host) return BTS_ERR_INVALID;
+    if (n > 0 && (!descs || n_bases == 0)) return BTS_ERR_INVALID;
+    if (n_bases > 0 && (!bases || !base_bytes)) return BTS_ERR_INVALID;
+    for (int j = 0; j < n_bases; ++j)
+        if (!bases[j] || ((uintptr_t)bases[j] & 15) || base_bytes[j] <= 0) return BTS_ERR_INVALID;
+    WgradBatchHeader* hdr = (WgradBatchHeader*)table_host;
+    WgradBatchEntry* out = (WgradBatchEntry*)(hdr + 1);
+    long target = 768;                                     // workgroups the batch aims for: plan_wgrad's own target, or
+    double tile_ksteps = 0.0;                              // workgroups of ~128 K-steps if the batch has work for more
+
+    struct Item { WgradBatchEntry e; int src; long n_it; };
+    Item* items = n > 0 ? new Item[n] : nullptr;
+    struct Free { Item* p; ~Free() { delete[] p; } } free_items{items};
+    long max_m = 1;
+    for (int i = 0; i < n; ++i) {
+        const bts_conv_wgrad_desc* d = descs + i;
+        WgradArgs a;
+        WgradPlan p;
+        if (const int rc = prepare_wgrad(d, a, p); rc != 0) return rc;
+        if (d->ws || d->ws_floats) return BTS_ERR_INVALID;       // the batch has one workspace
+        WgradBatchEntry& e = items[i].e;
+        items[i].src = i;
+        const double nbx = 4.0 * a.n_bundles * a.c_in, nby = 4.0 * a.n_bundles * a.c_out;
+        const double x_bytes = 4.0 * ((double)a.B * a.h_in * a.w_in - 1.0) * (double)a.x_pix_stride + nbx;
+        const double dy_bytes = 4.0 * ((double)a.M - 1.0) * (double)a.dy_pix_stride + nby;
+        const double dw_bytes = 4.0 * (double)a.c_out * a.N * a.n_bundles;
+        if (!wgrad_resolve(d->x, x_bytes, bases, base_bytes, n_bases, e.x_base, e.x_off)) return BTS_ERR_INVALID;
+        if (!wgrad_resolve(d->dy, dy_bytes, bases, base_bytes, n_bases, e.dy_base, e.dy_off)) return BTS_ERR_INVALID;
+        if (!wgrad_resolve(d->dw, dw_bytes, bases, base_bytes, n_bases, e.dw_base, e.dw_off)) return BTS_ERR_INVALID;
+        e.sc_base = e.sh_base = -1; e.sc_off = e.sh_off = 0;
+        if (d->pre_scale) {
+            if (!wgrad_resolve(d->pre_scale, nbx, bases, base_bytes, n_bases, e.sc_base, e.sc_off)) return BTS_ERR_INVALID;
+            if (!wgrad_resolve(d->pre_shift, nbx, bases, base_bytes, n_bases, e.sh_base, e.sh_off)) return BTS_ERR_INVALID;
+        }
+        e.ws_off = 0; e.first_wg = 0; e.first_red = 0;
+        e.x_pix_stride = a.x_pix_stride; e.dy_pix_stride = a.dy_pix_stride;
+        e.c_in = a.c_in; e.c_out = a.c_out; e.N = a.N; e.B = a.B; e.h_in = a.h_in; e.w_in = a.w_in; e.Hs = a.Hs; e.Ws = a.Ws;
+        e.ups = a.ups; e.H = a.H; e.W = a.W; e.ksize = a.ksize; e.dil = a.dil; e.stride = a.stride; e.pad = a.pad;
+        e.M = a.M; e.n_bundles = a.n_bundles; e.pre_relu = d->pre_scale ? a.pre_relu : 0;
+        e.variant = wgrad_batch_variant(a.c_out, a.N);
+        e.n_ntiles = (a.N + WGRAD_BN[e.variant] - 1) / WGRAD_BN[e.variant];
+        const long tiles = (long)((a.c_out + WGRAD_BM[e.variant] - 1) / WGRAD_BM[e.variant]) * e.n_ntiles;
+        if (tiles > 2147483647L) return BTS_ERR_UNSUPPORTED;
+        e.tiles = (int)tiles;
+        if ((long)a.M > max_m) max_m = (long)a.M;
+        tile_ksteps += (double)tiles * a.n_bundles * (double)(((long)a.M + WBK - 1) / WBK);
+    }
+    if (tile_ksteps / 128.0 > (double)target) target = tile_ksteps / 128.0 < 2147483647.0 ? (long)(tile_ksteps / 128.0) : 2147483647L;
+
+    // ---- the quantum: workgroups and partial floats of the batch are both non-increasing in qs ----
+    auto totals = [&](long qs, long& wgs, double& part) {
+        wgs = 0; part = 0.0;
+        for (int i = 0; i < n; ++i) {
+            const WgradBatchEntry& e = items[i].e;
+            long split, pps;
+            wgrad_batch_split((long)e.M, qs, split, pps);
+            wgs += (long)e.tiles * e.n_bundles * split;
+            if (split > 1) part += (double)split * e.c_out * e.N * e.n_bundles;
+        }
+    };
+    const long q_all = (max_m + WBK - 1) / WBK < 4 ? 4 : (max_m + WBK - 1) / WBK;      // every split is 1 from here on
+    long wgs; double part;
+    long qs = q_all;
+    totals(q_all, wgs, part);
+    if (wgs < target) {                                  // the largest quantum that still reaches the target, or 4
+        long lo = 4, hi = q_all;                         // invariant: answer in [lo, hi)
+        totals(lo, wgs, part);
+        if (wgs < target) qs = 4;
+        else {
+            while (hi - lo > 1) {
+                const long mid = lo + (hi - lo) / 2;
+                totals(mid, wgs, part);
+                if (wgs >= target) lo = mid; else hi = mid;
+            }
+            qs = lo;
+        }
+    }
+    totals(qs, wgs, part);
+    if (part > (double)ws_floats) {                      // the smallest quantum whose partials fit (q_all: none)
+        long lo = qs, hi = q_all;                        // part(lo) too large, part(hi) = 0
+        while (hi - lo > 1) {
+            const long mid = lo + (hi - lo) / 2;
+            totals(mid, wgs, part);
+            if (part > (double)ws_floats) lo = mid; else hi = mid;
+        }
+        qs = hi;
+    }
+
+    for (int i = 0; i < n; ++i) {
+        WgradBatchEntry& e = items[i].e;
+        long split, pps;
+        wgrad_batch_split((long)e.M, qs, split, pps);
+        e.split = (int)split; e.pix_per_split = (unsigned)pps;
+        const long own = (long)e.M < pps ? (long)e.M : pps;
+        items[i].n_it = (own + WBK - 1) / WBK;
+    }
+    // tile shape, then longest workgroups first, then shape, then position (stable: std::sort is not needed for n this small)
+    auto before = [](const Item& p, const Item& q) {
+        const WgradBatchEntry &a = p.e, &b = q.e;
+        if (a.variant != b.variant) return a.variant < b.variant;
+        if (p.n_it != q.n_it) return p.n_it > q.n_it;
+        if (a.M != b.M) return a.M > b.M;
+        if (a.N != b.N) return a.N > b.N;
+        if (a.c_out != b.c_out) return a.c_out > b.c_out;
+        if (a.n_bundles != b.n_bundles) return a.n_bundles > b.n_bundles;
+        return p.src < q.src;
+    };
+    int* order = n > 0 ? new int[n] : nullptr;
+    struct FreeI { int* p; ~FreeI() { delete[] p; } } free_order{order};
+    for (int i = 0; i < n; ++i) order[i] = i;
+    for (int i = 1; i < n; ++i) {                        // insertion sort
+        const int k = order[i];
+        int j = i - 1;
+        while (j >= 0 && before(items[k], items[order[j]])) { order[j + 1] = order[j]; --j; }
+        order[j + 1] = k;
+    }
+
+    hdr->magic = WGRAD_BATCH_MAGIC; hdr->n = n; hdr->n_bases = n_bases; hdr->reserved = 0; hdr->reserved2 = 0;
+    for (int v = 0; v < 5; ++v) hdr->first[v] = n;
+    for (int v = 0; v < 4; ++v) hdr->wgs[v] = 0;
+    long red = 0, ws_used = 0;
+    for (int r = 0; r < n; ++r) {
+        WgradBatchEntry& e = items[order[r]].e;
+        if (r < hdr->first[e.variant]) hdr->first[e.variant] = r;
+        const long per = (long)e.c_out * e.N * e.n_bundles;
+        e.first_wg = hdr->wgs[e.variant];
+        hdr->wgs[e.variant] += (long)e.tiles * e.n_bundles * e.split;
+        e.first_red = red;
+        if (e.split > 1) {
+            e.ws_off = ws_used;
+            ws_used += per * e.split;
+            red += (per / 4 + 15) / 16;
+        }
+        out[r] = e;
+        if (plan) {
+            bts_conv_wgrad_batch_item& it = plan[order[r]];
+            it.bm = WGRAD_BM[e.variant]; it.bn = WGRAD_BN[e.variant];
+            it.split = e.split; it.pix_per_split = (long)e.pix_per_split;
+            it.ws_offset = e.split > 1 ? e.ws_off : -1;
+        }
+    }
+    for (int v = 3; v >= 0; --v)                          // a shape with no entries starts where the next one does
+        if (hdr->first[v] > hdr->first[v + 1]) hdr->first[v] = hdr->first[v + 1];
+    hdr->red_blocks = red; hdr->ws_used = ws_used;
+    for (int v = 0; v < 4; ++v)
+        if (hdr->wgs[v] > 2147483647L) return BTS_ERR_UNSUPPORTED;
+    if (red > 2147483647L || ws_used > ws_floats) return BTS_ERR_UNSUPPORTED;
+    return 0;
+}
+
+extern "C" int bts_conv_wgrad_batch_f32(const void* table_host, const void* table_dev, int n, const void* const* bases,
+                                        int n_bases, float* ws, bts_stream_t stream) {
+    const WgradBatchHeader* hdr = (const WgradBatchHeader*)table_host;
+    if (!hdr || hdr->magic != WGRAD_BATCH_MAGIC || hdr->n != n || hdr->n_bases != n_bases || n < 0) return BTS_ERR_INVALID;
+    if (n == 0) return 0;
+    if (!table_dev || ((uintptr_t)table_dev & 15) || !bases) return BTS_ERR_INVALID;
+    if (hdr->ws_used > 0 && (!ws || ((uintptr_t)ws & 15))) return BTS_ERR_INVALID;
+    WgradBases b;
+    for (int j = 0; j < WGRAD_MAX_BASES; ++j) {
+        b.p[j] = j < n_bases ? (const char*)bases[j] : nullptr;
+        if (j < n_bases && (!bases[j] || ((uintptr_t)bases[j] & 15))) return BTS_ERR_INVALID;
+    }
+    const WgradBatchEntry* entries = (const WgradBatchEntry*)((const char*)table_dev + sizeof(WgradBatchHeader));
+    hipStream_t s = (hipStream_t)stream;
+    for (int v = 0; v < 4; ++v) {
+        const int cnt = hdr->first[v + 1] - hdr->first[v];
+        if (cnt <= 0 || hdr->wgs[v] <= 0) continue;
+        const WgradBatchEntry* ev = entries + hdr->first[v];
+        int rc;
+        switch (v) {
+            case 0: rc = launch_wgrad_batch<128, 128, 2, 2>(ev, cnt, hdr->wgs[v], b, ws, s); break;
+            case 1: rc = launch_wgrad_batch<64, 128, 1, 4>(ev, cnt, hdr->wgs[v], b, ws, s); break;
+            case 2: rc = launch_wgrad_batch<32, 128, 1, 4>(ev, cnt, hdr->wgs[v], b, ws, s); break;
+            default: rc = launch_wgrad_batch<64, 64, 2, 2>(ev, cnt, hdr->wgs[v], b, ws, s); break;
+        }
+        if (rc != 0) return rc;
+    }
+    if (hdr->red_blocks > 0) {
+        hipLaunchKernelGGL(wgrad_reduce_batch_kernel, dim3((unsigned)hdr->red_blocks), dim3(256), 0, s, entries, n, b,
+                           (const float*)ws);
+        return (int)hipGetLastError();
+    }
     return 0;
 }
 

@@ -14,7 +14,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib, conv_plan
-from ._lib import BtsHipError, ConvDesc, ConvWgradDesc
+from ._lib import BtsHipError, ConvDesc, ConvWgradBatchItem, ConvWgradDesc
 from .conv_plan import conv_out_hw, round_up
 
 ACT_NONE, ACT_RELU, ACT_ELU, ACT_SIGMOID = 0, 1, 2, 3
@@ -601,11 +601,68 @@ def reduc_backward(x2d: torch.Tensor, B: int, h: int, w: int, c_in: int, c_first
     _lib.check(rc, "bts_reduc_bwd_f32")
 
 
+class BatchCache:
+    """A small least-recently-used map from a batch's key to its WgradBatch (plan, host table, device table): bounded,
+    so that a run which keeps changing shapes or freeze masks does not accumulate tables."""
+
+    def __init__(self, max_entries: int):
+        import collections
+        self.max_entries, self._d = max_entries, collections.OrderedDict()
+
+    def __len__(self):
+        return len(self._d)
+
+    def get(self, key):
+        v = self._d.get(key)
+        if v is not None:
+            self._d.move_to_end(key)
+        return v
+
+    def put(self, key, value):
+        self._d[key] = value
+        while len(self._d) > self.max_entries:
+            self._d.popitem(last=False)
+        return value
+
+
+# (device, x pixel stride, x channels, B, h, w, chain, need mask, workspace floats) -> WgradBatch; the plan depends on the
+# workspace size, so it is part of the key
+_REDUC_WGRAD_BATCHES = BatchCache(32)
+
+
+def _reduc_wgrad_batch(x2d, Y, G, B, h, w, weights, cols, need_dw, ws):
+    """The weight gradients of one scale's layers as ONE batched launch: bases x2d's storage rows, Y, G and a flat DW.
+    The batch (plan + device table) is built once per geometry and need mask; later steps only launch."""
+    dev = x2d.device
+    widths = [width * wt.shape[1] for wt, (_, width) in zip(weights, cols)]
+    total = sum(wd for wd, nd in zip(widths, need_dw) if nd)
+    DW = torch.empty(total, dtype=torch.float32, device=dev)
+    xs = x2d.stride(0)
+    xbase = x2d.as_strided(((x2d.shape[0] - 1) * xs + x2d.shape[1],), (1,))     # the storage span the view covers, flat
+    ws_floats = 0 if ws is None else ws.numel()
+    key = (str(dev), xs, x2d.shape[1], B, h, w, tuple(tuple(wt.shape[:2]) for wt in weights), tuple(bool(nd) for nd in need_dw), ws_floats)
+    batch = _REDUC_WGRAD_BATCHES.get(key)
+    if batch is None:
+        problems, at = [], 0
+        for l, (wt, (c0, width)) in enumerate(zip(weights, cols)):
+            if not need_dw[l]:
+                continue
+            cin_l = wt.shape[1]
+            src = x2d[:, :cin_l] if l == 0 else Y[:, cols[l - 1][0]:cols[l - 1][0] + cin_l]
+            problems.append(dict(x=src, dy=G[:, c0:c0 + width], dw=DW[at:at + widths[l]], B=B, h_in=h, w_in=w, c_in=cin_l,
+                                 c_out=width, ksize=1))
+            at += widths[l]
+        batch = _REDUC_WGRAD_BATCHES.put(key, WgradBatch(problems, [xbase, Y, G, DW], ws_floats, tag="reduc.wgrad"))
+    got = iter(batch.run([xbase, Y, G, DW], ws))
+    return [next(got)[:wt.shape[0]].reshape(wt.shape[0], wt.shape[1], 1, 1) if nd else None for wt, nd in zip(weights, need_dw)]
+
+
 def reduc_train_backward(x2d: torch.Tensor, B: int, h: int, w: int, weights: Sequence[torch.Tensor], packs, max_depth: float,
                          upratio: int, grad_out: torch.Tensor, need_dx: bool, need_dw: Sequence[bool],
-                         ws: Optional[torch.Tensor] = None):
+                         ws: Optional[torch.Tensor] = None, batched_wgrad: bool = False):
     """All gradients of one scale: one bts_reduc_bwd_f32 launch, then one bts_conv_wgrad_f32 (ksize 1) per layer whose
-    weight wants a gradient, on column slices of the row buffers.  Returns (dx [B,h,w,c_in] or None, [dW or None])."""
+    weight wants a gradient, on column slices of the row buffers -- or, with ``batched_wgrad``, one
+    bts_conv_wgrad_batch_f32 for all of them.  Returns (dx [B,h,w,c_in] or None, [dW or None])."""
     c_in, c_first = weights[0].shape[1], weights[0].shape[0]
     npix = B * h * w
     cols, yc = reduc_train_cols(c_in, c_first)
@@ -616,6 +673,8 @@ def reduc_train_backward(x2d: torch.Tensor, B: int, h: int, w: int, weights: Seq
     dx = torch.empty((B, h, w, c_in), dtype=torch.float32, device=dev) if need_dx else None
     reduc_backward(x2d, B, h, w, c_in, c_first, packs[1], packs[2], max_depth, upratio, grad_out.contiguous(), Y, G,
                    None if dx is None else dx.view(npix, c_in))
+    if batched_wgrad:
+        return dx, (_reduc_wgrad_batch(x2d, Y, G, B, h, w, weights, cols, need_dw, ws) if any_dw else [None] * len(weights))
     dws = []
     for l, (wt, (c0, width)) in enumerate(zip(weights, cols)):
         if not need_dw[l]:
@@ -662,11 +721,25 @@ class ReducLpgFunction(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out):
+        return ReducLpgFunction.backward_impl(ctx, grad_out, False)
+
+    @staticmethod
+    def backward_impl(ctx, grad_out, batched_wgrad):
         x2d, *weights = ctx.saved_tensors
         B, h, w, md, k, packs, ws = ctx.cfg
         dx, dws = reduc_train_backward(x2d, B, h, w, weights, packs, md, k, grad_out, ctx.needs_input_grad[0],
-                                       ctx.needs_input_grad[6:], ws)
+                                       ctx.needs_input_grad[6:], ws, batched_wgrad=batched_wgrad)
         return (None if dx is None else dx.permute(0, 3, 1, 2), None, None, None, None, None) + tuple(dws)
+
+
+class ReducLpgBatchedFunction(torch.autograd.Function):
+    """ReducLpgFunction whose backward computes the layers' weight gradients in one batched launch."""
+    forward = staticmethod(ReducLpgFunction.forward)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        return ReducLpgFunction.backward_impl(ctx, grad_out, True)
 
 
 class ReducFinalFunction(torch.autograd.Function):
@@ -690,11 +763,25 @@ class ReducFinalFunction(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out):
+        return ReducFinalFunction.backward_impl(ctx, grad_out, False)
+
+    @staticmethod
+    def backward_impl(ctx, grad_out, batched_wgrad):
         x2d, *weights = ctx.saved_tensors
         B, h, w, md, packs, ws = ctx.cfg
         dx, dws = reduc_train_backward(x2d, B, h, w, weights, packs, md, 0, grad_out, ctx.needs_input_grad[0],
-                                       ctx.needs_input_grad[4:], ws)
+                                       ctx.needs_input_grad[4:], ws, batched_wgrad=batched_wgrad)
         return (None if dx is None else dx.permute(0, 3, 1, 2), None, None, None) + tuple(dws)
+
+
+class ReducFinalBatchedFunction(torch.autograd.Function):
+    """ReducFinalFunction whose backward computes the layers' weight gradients in one batched launch."""
+    forward = staticmethod(ReducFinalFunction.forward)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        return ReducFinalFunction.backward_impl(ctx, grad_out, True)
 
 
 # ---------------------------------------------------------------------------- layout
@@ -1296,19 +1383,150 @@ def conv_wgrad(x2d: torch.Tensor, B: int, h_in: int, w_in: int, c_in: int, dy2d:
     return dw
 
 
+# ---- many weight gradients in one launch (bts_conv_wgrad_batch_*, include/bts_hip.h)
+def conv_wgrad_batch_plan_descs(descs: Sequence[ConvWgradDesc], bases: Sequence[Tuple[int, int]], ws_floats: int,
+                                with_table: bool = False):
+    """bts_conv_wgrad_batch_plan_f32 on filled descriptors.  ``bases``: (address, bytes) of the ranges every pointer of
+    every descriptor must lie in.  Returns one (bm, bn, split, pix_per_split, ws_offset) per problem, in the order
+    given (ws_offset -1: unsplit); with ``with_table`` also the host table.  Host arithmetic only."""
+    lib = _lib.load()
+    n, nb = len(descs), len(bases)
+    arr = (ConvWgradDesc * max(n, 1))(*descs)
+    bp = (C.c_void_p * max(nb, 1))(*[int(a) for a, _ in bases])
+    bb = (C.c_long * max(nb, 1))(*[int(b) for _, b in bases])
+    table = C.create_string_buffer(int(lib.bts_conv_wgrad_batch_table_bytes(n)))
+    items = (ConvWgradBatchItem * max(n, 1))()
+    _lib.check(lib.bts_conv_wgrad_batch_plan_f32(arr, n, bp, bb, nb, int(ws_floats), table, items), "bts_conv_wgrad_batch_plan_f32")
+    plan = [(it.bm, it.bn, it.split, it.pix_per_split, it.ws_offset) for it in items[:n]]
+    return (plan, table) if with_table else plan
+
+
+def conv_wgrad_batch_plan(problems: Sequence[dict], ws_floats: int) -> List[Tuple[int, int, int, int, int]]:
+    """Tiles and pixel splits one batched launch will run for these geometries under a workspace of ``ws_floats`` floats:
+    one (bm, bn, split, pix_per_split, ws_offset) per problem, from the library's own batch planner.  No tensors and no
+    GPU.  Each problem is a dict of conv_wgrad_plan's arguments (B, h_in, w_in, c_in, c_out, ksize and optionally dil,
+    stride, pad, up, n_bundles, pre, pre_relu, x_pix_stride, dy_pix_stride)."""
+    descs = []
+    for pr in problems:
+        pr = dict(pr)
+        ksize, dil = pr["ksize"], pr.get("dil", 1)
+        pad = pr.get("pad")
+        nbun = pr.get("n_bundles", 1)
+        nb = max(nbun, 1)
+        xs, ds = pr.get("x_pix_stride"), pr.get("dy_pix_stride")
+        d = _wgrad_desc(pr["B"], pr["h_in"], pr["w_in"], pr["c_in"], pr["c_out"], ksize, dil, pr.get("stride", 1),
+                        dil * (ksize // 2) if pad is None else pad, pr.get("up", 1), nbun,
+                        nb * pr["c_in"] if xs is None else xs, nb * pr["c_out"] if ds is None else ds)
+        d.x = d.dy = d.dw = _PLAN_DUMMY_PTR
+        if pr.get("pre", False):
+            d.pre_scale = d.pre_shift = _PLAN_DUMMY_PTR
+            d.pre_relu = int(bool(pr.get("pre_relu", False)))
+        descs.append(d)
+    return conv_wgrad_batch_plan_descs(descs, [(_PLAN_DUMMY_PTR, 1 << 60)], ws_floats)
+
+
+class WgradBatch:
+    """The weight gradients of many convolutions as one batched launch (bts_conv_wgrad_batch_f32).
+
+    ``problems``: one dict per convolution -- ``x`` / ``dy`` ([npix, >=c] NHWC views), ``dw`` (contiguous view of
+    n_bundles*c_out*ksize^2*c_in floats that receives the OHWI gradient), optional ``pre`` = (scale, shift) views and
+    ``pre_relu``, and conv_wgrad's geometry (B, h_in, w_in, c_in, c_out, ksize, dil, stride, pad, up, n_bundles).  Every
+    view must lie inside one of ``bases`` (at most 8 contiguous fp32 tensors).  Construction plans the batch and uploads
+    its table once; ``run(bases, ws)`` then launches with any buffers of the same sizes -- the table stores offsets, not
+    addresses -- uploading nothing and synchronising nothing, and returns the dw views of the bases it was given.
+    dw views that overlap are a caller error."""
+
+    def __init__(self, problems: Sequence[dict], bases: Sequence[torch.Tensor], ws_floats: int, tag: str = "wgrad.batch"):
+        self.tag, self.n, self.ws_floats = tag, len(problems), int(ws_floats)
+        for b in bases:
+            _need(b, "WgradBatch")
+            if not b.is_contiguous():
+                raise BtsHipError("WgradBatch: bases must be contiguous")
+        self.base_numel = [b.numel() for b in bases]
+        self.device = bases[0].device if bases else None
+        ranges = [(b.data_ptr(), 4 * b.numel()) for b in bases]
+        descs, self._dw, self.flops, self.nbytes = [], [], 0.0, 0.0
+        for pr in problems:
+            x2d, dy2d, dw = pr["x"], pr["dy"], pr["dw"]
+            B, h_in, w_in, c_in, c_out, ksize = (pr[k] for k in ("B", "h_in", "w_in", "c_in", "c_out", "ksize"))
+            dil, stride, up, nbun = pr.get("dil", 1), pr.get("stride", 1), pr.get("up", 1), pr.get("n_bundles", 1)
+            pad = pr.get("pad")
+            pad = dil * (ksize // 2) if pad is None else pad
+            nb = max(nbun, 1)
+            xs, xc = _rows2d(x2d, "WgradBatch")
+            ds, dc = _rows2d(dy2d, "WgradBatch")
+            _need(dw, "WgradBatch")
+            H, W = conv_out_hw(h_in, w_in, ksize, dil, stride, pad, up)
+            if c_in % 4 or c_out % 4 or c_in * nb > xc or c_out * nb > dc:
+                raise BtsHipError("WgradBatch: c_in/c_out must be multiples of 4 within the views (%d/%d, %d/%d)" % (c_in, xc, c_out, dc))
+            if x2d.shape[0] != B * h_in * w_in or dy2d.shape[0] != B * H * W:
+                raise BtsHipError("WgradBatch: views %s / %s do not match B=%d %dx%d -> %dx%d"
+                                  % (tuple(x2d.shape), tuple(dy2d.shape), B, h_in, w_in, H, W))
+            taps = ksize * ksize
+            shape = (c_out, taps, c_in) if nbun <= 1 else (nbun, c_out, taps, c_in)
+            if not dw.is_contiguous() or dw.numel() != nb * c_out * taps * c_in:
+                raise BtsHipError("WgradBatch: dw must be a contiguous view of %d floats" % (nb * c_out * taps * c_in))
+            d = _wgrad_desc(B, h_in, w_in, c_in, c_out, ksize, dil, stride, pad, up, nbun, xs, ds)
+            pre = pr.get("pre")
+            if pre is not None:
+                if pre[0].numel() != c_in * nb or pre[1].numel() != pre[0].numel():
+                    raise BtsHipError("WgradBatch: pre vectors must have c_in entries")
+                d.pre_scale, d.pre_shift, d.pre_relu = pre[0].data_ptr(), pre[1].data_ptr(), int(bool(pr.get("pre_relu", False)))
+            d.x, d.dy, d.dw = x2d.data_ptr(), dy2d.data_ptr(), dw.data_ptr()
+            descs.append(d)
+            where = [(j, (dw.data_ptr() - a) // 4) for j, (a, nbytes) in enumerate(ranges) if a <= dw.data_ptr() < a + nbytes]
+            if not where:
+                raise BtsHipError("WgradBatch: a dw view lies outside every base")
+            self._dw.append((where[0][0], where[0][1], shape))
+            self.flops += 2.0 * B * H * W * c_out * c_in * taps * nb
+            self.nbytes += 4.0 * (B * h_in * w_in * c_in + B * H * W * c_out + taps * c_out * c_in) * nb
+        self.plan, self._table = conv_wgrad_batch_plan_descs(descs, ranges, self.ws_floats, with_table=True)
+        self.ws_used = sum(p[2] * int(torch.Size(sh).numel()) for p, (_, _, sh) in zip(self.plan, self._dw) if p[2] > 1)
+        self._table_dev = None
+        if self.n:
+            self._table_dev = torch.frombuffer(self._table, dtype=torch.uint8).to(self.device)      # the one upload
+
+    def run(self, bases: Sequence[torch.Tensor], ws: Optional[torch.Tensor]) -> List[torch.Tensor]:
+        if len(bases) != len(self.base_numel):
+            raise BtsHipError("WgradBatch.run: %d bases, planned with %d" % (len(bases), len(self.base_numel)))
+        if self.n == 0:
+            return []
+        for b, numel in zip(bases, self.base_numel):
+            _need(b, "WgradBatch.run")
+            if b.numel() < numel or not b.is_contiguous() or b.device != self.device:
+                raise BtsHipError("WgradBatch.run: a base is smaller than the one the batch was planned with, not contiguous or on another device")
+        if self.ws_used:
+            _need(ws, "WgradBatch.run")
+            if ws.numel() < self.ws_used or not ws.is_contiguous() or ws.device != self.device:
+                raise BtsHipError("WgradBatch.run: the workspace must hold %d floats" % self.ws_used)
+        bp = (C.c_void_p * len(bases))(*[b.data_ptr() for b in bases])
+        with torch.cuda.device(self.device):
+            rc = _launch("conv_wgrad_batch_kernel", self.tag, self.flops, self.nbytes,
+                         lambda: _lib.load().bts_conv_wgrad_batch_f32(self._table, self._table_dev.data_ptr(), self.n, bp, len(bases),
+                                                                      _ptr(ws), _stream(bases[0])))
+        _lib.check(rc, "bts_conv_wgrad_batch_f32")
+        return [bases[j].view(-1)[off:off + int(torch.Size(sh).numel())].view(sh) for j, off, sh in self._dw]
+
+
 # ------------------------------------------------------------------------------ train-mode BN
 def bn_train_ws_floats(npix: int, C: int) -> int:
     return int(_lib.load().bts_bn_train_ws_floats(npix, C))
 
 
 def bn_train_stats(x2d: torch.Tensor, C: int, gamma, beta, eps: float, momentum: float, running_mean, running_var,
-                   ws: torch.Tensor):
+                   ws: torch.Tensor, out: Optional[torch.Tensor] = None):
     """Batch statistics of NHWC rows (bts_bn_train_stats_f32): returns (mean, invstd, scale, shift), each [C];
-    running_mean / running_var (or None) are updated in place."""
+    running_mean / running_var (or None) are updated in place.  ``out``: optional [4, C] view (unit channel stride, rows
+    16-byte aligned) that receives the four vectors instead of a fresh tensor."""
     xs, xc = _rows2d(x2d, "bn_train_stats")
     if C % 4 or C > xc:
         raise BtsHipError("bn_train_stats: C must be a multiple of 4 within the view (%d/%d)" % (C, xc))
-    out = torch.empty((4, C), dtype=torch.float32, device=x2d.device)
+    if out is None:
+        out = torch.empty((4, C), dtype=torch.float32, device=x2d.device)
+    else:
+        _need(out, "bn_train_stats")
+        if tuple(out.shape) != (4, C) or out.stride(1) != 1 or out.stride(0) % 4 or out.data_ptr() % 16:
+            raise BtsHipError("bn_train_stats: out must be a [4, %d] view with unit channel stride and 16-byte aligned rows" % C)
     _need(ws, "bn_train_stats")
     npix = x2d.shape[0]
     with torch.cuda.device(x2d.device):

@@ -454,20 +454,23 @@ def fused_reduction_available(m, upratio: int) -> bool:
     return bool(m.is_final) == (upratio == 0) and ops.reduc_train_supported(m.c_in, m.c_first_out, upratio)
 
 
-def fused_lpg_scale(reduc_mod, lpg_mod, feat):
-    """reduction_1x1 -> F.normalize -> LPG -> /max_depth of one scale (bts.py:249-256) as one autograd node."""
+def fused_lpg_scale(reduc_mod, lpg_mod, feat, batched_wgrad=False):
+    """reduction_1x1 -> F.normalize -> LPG -> /max_depth of one scale (bts.py:249-256) as one autograd node.
+    ``batched_wgrad``: the layers' weight gradients in one batched launch (decoder.batched_wgrad)."""
     refuse_bf16("train.fused_lpg_scale")
     am = torch.empty((), dtype=torch.float32, device=feat.device)
-    depth = ops.ReducLpgFunction.apply(feat, reduc_mod.max_depth, int(lpg_mod.upratio), reduc_mod.packed_train(), am,
+    fn = ops.ReducLpgBatchedFunction if batched_wgrad else ops.ReducLpgFunction
+    depth = fn.apply(feat, reduc_mod.max_depth, int(lpg_mod.upratio), reduc_mod.packed_train(), am,
                                        _workspace(feat.device), *_reduc_weights(reduc_mod))
     lpg_mod.abs_min = am
     return depth
 
 
-def fused_reduction_final(reduc_mod, feat):
+def fused_reduction_final(reduc_mod, feat, batched_wgrad=False):
     """reduc1x1 (bts.py:285): the final chain and its sigmoid as one autograd node."""
     refuse_bf16("train.fused_reduction_final")
-    return ops.ReducFinalFunction.apply(feat, reduc_mod.max_depth, reduc_mod.packed_train(), _workspace(feat.device),
+    fn = ops.ReducFinalBatchedFunction if batched_wgrad else ops.ReducFinalFunction
+    return fn.apply(feat, reduc_mod.max_depth, reduc_mod.packed_train(), _workspace(feat.device),
                                         *_reduc_weights(reduc_mod))
 
 
@@ -502,10 +505,11 @@ def _decoder_forward(dec, features, focal):
     daspp_feat = _conv_elu(dec.daspp_conv, torch.cat([iconv4] + branches, 1), "daspp_conv")
 
     fused = bool(getattr(dec, "fused_reduction_train", False))
+    batched = bool(getattr(dec, "batched_wgrad", False))
 
     def lpg_scale(reduc_mod, lpg_mod, feat):
         if fused and fused_reduction_available(reduc_mod, int(lpg_mod.upratio)):
-            return fused_lpg_scale(reduc_mod, lpg_mod, feat)
+            return fused_lpg_scale(reduc_mod, lpg_mod, feat, batched)
         r = reduction_forward(reduc_mod, feat)
         plane_eq = torch.cat([F.normalize(r[:, :3], 2, 1), r[:, 3:4]], 1).contiguous()
         return lpg_mod(plane_eq, focal).unsqueeze(1) / md
@@ -519,7 +523,7 @@ def _decoder_forward(dec, features, focal):
     depth_2x2 = lpg_scale(dec.reduc2x2, dec.lpg2x2, iconv2)
     upconv1 = upconv_forward(dec.upconv1, iconv2)
     if fused and fused_reduction_available(dec.reduc1x1, 0):
-        reduc1x1 = fused_reduction_final(dec.reduc1x1, upconv1)
+        reduc1x1 = fused_reduction_final(dec.reduc1x1, upconv1, batched)
     else:
         reduc1x1 = reduction_forward(dec.reduc1x1, upconv1)
     iconv1 = _conv_elu(dec.conv1, torch.cat([upconv1, reduc1x1, depth_2x2, depth_4x4, depth_8x8], 1), "conv1")
@@ -542,7 +546,7 @@ class _DenseBlockFn(torch.autograd.Function):
     norm + ReLU ride in the prologue of the forward convolutions and of the weight-gradient gather."""
 
     @staticmethod
-    def forward(ctx, x, block, *params):
+    def forward(ctx, x, block, batched, *params):
         refuse_bf16("train.densenet_block")
         B, C0, H, W = x.shape
         layers = list(block.values())
@@ -556,25 +560,34 @@ class _DenseBlockFn(torch.autograd.Function):
         saved = []
         ws = _bn_workspace(dev, ops.bn_train_ws_floats(npix, Ct))
         sk = _splitk_workspace(dev)
+        if batched:      # one slab per kind, so that the deferred weight gradients of all layers address six buffers
+            T1 = torch.empty((len(layers), npix, mid), dtype=torch.float32, device=dev)
+            stats = torch.empty((len(layers), 8, max(Ct, mid)), dtype=torch.float32, device=dev)   # rows 0-3 norm1, 4-7 norm2
         for i, L in enumerate(layers):
             Ci = C0 + i * g
             s1 = ops.bn_train_stats(buf[:, :Ci], Ci, L.norm1.weight.detach(), L.norm1.bias.detach(), L.norm1.eps,
-                                    L.norm1.momentum, L.norm1.running_mean, L.norm1.running_var, ws)
+                                    L.norm1.momentum, L.norm1.running_mean, L.norm1.running_var, ws,
+                                    out=stats[i, 0:4, :Ci] if batched else None)
             # norm + ReLU ride in the convolutions' prologue (applied on the way to LDS): the normalised tensors are
             # never written in the forward pass
-            t1 = torch.empty((npix, mid), dtype=torch.float32, device=dev)
+            t1 = T1[i] if batched else torch.empty((npix, mid), dtype=torch.float32, device=dev)
             ops.conv_forward(buf[:, :Ci], B, H, W, _PACKER.get(L.conv1.weight, Ci, WeightPacker.FWD), mid, 1, c_in_ld=Ci,
                              pre=(s1[2], s1[3]), pre_relu=True, y2d=t1, tag="enc.fwd", splitk_ws=sk)
             s2 = ops.bn_train_stats(t1, mid, L.norm2.weight.detach(), L.norm2.bias.detach(), L.norm2.eps,
-                                    L.norm2.momentum, L.norm2.running_mean, L.norm2.running_var, ws)
+                                    L.norm2.momentum, L.norm2.running_mean, L.norm2.running_var, ws,
+                                    out=stats[i, 4:8, :mid] if batched else None)
             ops.conv_forward(t1, B, H, W, _PACKER.get(L.conv2.weight, mid, WeightPacker.FWD), g, 3, c_in_ld=mid,
                              pre=(s2[2], s2[3]), pre_relu=True, y2d=buf[:, Ci:Ci + g], tag="enc.fwd", splitk_ws=sk)
             for bn in (L.norm1, L.norm2):
                 if bn.num_batches_tracked is not None:
                     _count_batch(bn)
-            saved += [t1, torch.stack(s1), torch.stack(s2)]
+            if not batched:
+                saved += [t1, torch.stack(s1), torch.stack(s2)]
+        if batched:
+            saved = [T1, stats]
         ctx.save_for_backward(buf, *saved)
         ctx.block = block
+        ctx.batched_wgrad = batched
         ctx.geom = (B, C0, H, W, g, mid, Ct)
         return buf.view(B, H, W, Ct).permute(0, 3, 1, 2)
 
@@ -588,7 +601,12 @@ class _DenseBlockFn(torch.autograd.Function):
         G = torch.empty((npix, Ct), dtype=torch.float32, device=dev)     # private copy: the walk below accumulates into it
         G.view(B, H, W, Ct).copy_(grad_out.permute(0, 2, 3, 1))
         d_a2 = torch.empty((npix, mid), dtype=torch.float32, device=dev)
-        d_t1 = torch.empty((npix, mid), dtype=torch.float32, device=dev)
+        batched = ctx.batched_wgrad
+        if batched:      # the weight gradients wait for the end of the walk: every layer keeps its d_t1
+            T1, stats = saved
+            D_T1 = torch.empty((len(layers), npix, mid), dtype=torch.float32, device=dev)
+        else:
+            d_t1 = torch.empty((npix, mid), dtype=torch.float32, device=dev)
         d_a1 = torch.empty((npix, Ct), dtype=torch.float32, device=dev)
         dpre = torch.empty((npix, Ct), dtype=torch.float32, device=dev)
         ws = _bn_workspace(dev, ops.bn_train_ws_floats(npix, Ct))
@@ -599,37 +617,87 @@ class _DenseBlockFn(torch.autograd.Function):
         for i in range(len(layers) - 1, -1, -1):
             L = layers[i]
             Ci = C0 + i * g
-            t1, s1, s2 = saved[3 * i], saved[3 * i + 1], saved[3 * i + 2]
+            if batched:
+                t1, s1, s2, d_t1 = T1[i], stats[i, 0:4, :Ci], stats[i, 4:8, :mid], D_T1[i]
+            else:
+                t1, s1, s2 = saved[3 * i], saved[3 * i + 1], saved[3 * i + 2]
             gy = G[:, Ci:Ci + g]                                               # this layer's output gradient, in place
             ops.conv_forward(gy, B, H, W, _PACKER.get(L.conv2.weight, g, WeightPacker.DGRAD), mid, 3, c_in_ld=g, y2d=d_a2,
                              pad=1, tag="enc.dgrad", splitk_ws=sk)
-            if need[2 + 6 * i + 5]:                # the weight-gradient gather re-applies norm2 + ReLU to t1 on the fly
+            if need[3 + 6 * i + 5] and not batched:   # the weight-gradient gather re-applies norm2 + ReLU to t1 on the fly
                 w2 = ops.conv_wgrad(t1, B, H, W, mid, gy, g, 3, ws=wws, tag="enc.wgrad", pre=(s2[2], s2[3]), pre_relu=True)
                 grads[6 * i + 5] = w2.reshape(g, 3, 3, mid).permute(0, 3, 1, 2).contiguous()
             dg2, db2 = ops.bn_train_backward(t1, d_a2, mid, s2[0], s2[1], s2[2], s2[3], True, ws, d_t1)
-            if need[2 + 6 * i + 3]:
+            if need[3 + 6 * i + 3]:
                 grads[6 * i + 3] = dg2
-            if need[2 + 6 * i + 4]:
+            if need[3 + 6 * i + 4]:
                 grads[6 * i + 4] = db2
             ops.conv_forward(d_t1, B, H, W, _PACKER.get(L.conv1.weight, mid, WeightPacker.DGRAD), Ci, 1, c_in_ld=mid,
                              y2d=d_a1[:, :Ci], pad=0, tag="enc.dgrad", splitk_ws=sk)
-            if need[2 + 6 * i + 2]:
+            if need[3 + 6 * i + 2] and not batched:
                 w1 = ops.conv_wgrad(buf[:, :Ci], B, H, W, Ci, d_t1, mid, 1, ws=wws, tag="enc.wgrad", pre=(s1[2], s1[3]),
                                     pre_relu=True)
                 grads[6 * i + 2] = w1.reshape(mid, Ci, 1, 1)
             dg1, db1 = ops.bn_train_backward(buf[:, :Ci], d_a1[:, :Ci], Ci, s1[0], s1[1], s1[2], s1[3], True, ws, dpre[:, :Ci])
-            if need[2 + 6 * i + 0]:
+            if need[3 + 6 * i + 0]:
                 grads[6 * i + 0] = dg1
-            if need[2 + 6 * i + 1]:
+            if need[3 + 6 * i + 1]:
                 grads[6 * i + 1] = db1
             G[:, :Ci] += dpre[:, :Ci]                                          # the prefix receives this layer's input gradient
+        if batched:
+            # Deferring is safe: buf, T1 and the norm vectors are read-only in backward, D_T1[i] is written once, and layer
+            # i's columns of G are final when layer i is processed (layers below only add onto columns < C_i).
+            mask = tuple((bool(need[3 + 6 * i + 2]), bool(need[3 + 6 * i + 5])) for i in range(len(layers)))
+            dws = iter(_dense_wgrad_batch(ctx.geom, mask, buf, G, T1, D_T1, stats, wws))
+            for i, (n1, n2) in enumerate(mask):
+                if n1:
+                    grads[6 * i + 2] = next(dws).reshape(mid, C0 + i * g, 1, 1)
+                if n2:
+                    grads[6 * i + 5] = next(dws).reshape(g, 3, 3, mid).permute(0, 3, 1, 2).contiguous()
         dx = G[:, :C0].reshape(B, H, W, C0).permute(0, 3, 1, 2) if need[0] else None
-        return (dx, None) + tuple(grads)
+        return (dx, None, None) + tuple(grads)
 
 
-def _dense_block(block, x):
+# (device, block geometry, need mask, workspace floats) -> ops.WgradBatch; the plan depends on the workspace size, so it
+# is part of the key.  Bounded: a run that keeps changing crop size or freeze mask evicts the least recently used table
+_DENSE_WGRAD_BATCHES = ops.BatchCache(64)
+
+
+def _dense_wgrad_batch(geom, mask, buf, G, T1, D_T1, stats, wws):
+    """Every wanted weight gradient of one dense block in ONE batched launch over the bases buf, G, T1, D_T1, stats and
+    a flat DW (the return value's views, in layer order: 1x1 then 3x3).  The batch -- plan and device table -- is built
+    on the first step of a (geometry, need mask) and only launched afterwards; frozen layers are not in it, and a block
+    with nothing to compute launches nothing."""
+    B, C0, H, W, g, mid, Ct = geom
+    sizes = []
+    for i, (n1, n2) in enumerate(mask):
+        sizes += [mid * (C0 + i * g)] * n1 + [g * 9 * mid] * n2
+    if not sizes:
+        return []
+    DW = torch.empty(sum(sizes), dtype=torch.float32, device=buf.device)
+    bases = [buf, G, T1, D_T1, stats, DW]
+    key = (str(buf.device), geom, mask, wws.numel())
+    batch = _DENSE_WGRAD_BATCHES.get(key)
+    if batch is None:
+        problems, at = [], 0
+        for i, (n1, n2) in enumerate(mask):
+            Ci = C0 + i * g
+            if n1:
+                problems.append(dict(x=buf[:, :Ci], dy=D_T1[i], dw=DW[at:at + mid * Ci], B=B, h_in=H, w_in=W, c_in=Ci, c_out=mid,
+                                     ksize=1, pre=(stats[i, 2, :Ci], stats[i, 3, :Ci]), pre_relu=True))
+                at += mid * Ci
+            if n2:
+                problems.append(dict(x=T1[i], dy=G[:, Ci:Ci + g], dw=DW[at:at + g * 9 * mid], B=B, h_in=H, w_in=W, c_in=mid,
+                                     c_out=g, ksize=3, pre=(stats[i, 6, :mid], stats[i, 7, :mid]), pre_relu=True))
+                at += g * 9 * mid
+        batch = _DENSE_WGRAD_BATCHES.put(key, ops.WgradBatch(problems, bases, wws.numel(), tag="enc.wgrad"))
+    return batch.run(bases, wws)
+
+
+def _dense_block(block, x, batched_wgrad=False):
     """Fused in-place dense block when every norm layer is an ordinary train()-mode BatchNorm2d with affine parameters
-    and channel counts the kernels take (multiples of 4); otherwise the generic layer-by-layer graph."""
+    and channel counts the kernels take (multiples of 4); otherwise the generic layer-by-layer graph.
+    ``batched_wgrad``: the block's weight gradients in one batched launch at the end of its backward walk."""
     nn = torch.nn
     layers = list(block.values())
     ok = x.is_cuda and x.dtype == torch.float32 and x.shape[1] % 4 == 0
@@ -645,10 +713,10 @@ def _dense_block(block, x):
     params = []
     for L in layers:
         params += [L.norm1.weight, L.norm1.bias, L.conv1.weight, L.norm2.weight, L.norm2.bias, L.conv2.weight]
-    return _DenseBlockFn.apply(x, block, *params)
+    return _DenseBlockFn.apply(x, block, bool(batched_wgrad), *params)
 
 
-def _run_children(children, x, tapped=None, taps=None):
+def _run_children(children, x, tapped=None, taps=None, batched_wgrad=False):
     """Run (name, module) pairs in order on the HIP kernels: bias-free ungrouped convolutions, batch-statistic BN
     with the ReLU that follows it fused in; pools and stray activations are the modules themselves.
     ``tapped(name)``: children whose output joins ``taps`` (encoder.forward's skip list)."""
@@ -670,7 +738,7 @@ def _run_children(children, x, tapped=None, taps=None):
                 i += 1
                 last = children[i][0]
         elif isinstance(child, nn.ModuleDict):               # _DenseBlock
-            fused = _dense_block(child, x) if FUSED_DENSE_BLOCKS else None
+            fused = _dense_block(child, x, batched_wgrad) if FUSED_DENSE_BLOCKS else None
             if fused is not None:
                 x = fused                                    # one autograd node, one NHWC buffer, no torch.cat
             else:                                            # generic graph: each layer sees the concat of all earlier ones
@@ -680,7 +748,7 @@ def _run_children(children, x, tapped=None, taps=None):
                     feats.append(_run_children(list(layer.named_children()), y))   # norm1 relu1 conv1 norm2 relu2 conv2
                 x = torch.cat(feats, 1)
         elif isinstance(child, nn.Sequential):               # _Transition
-            x = _run_children(list(child.named_children()), x)
+            x = _run_children(list(child.named_children()), x, batched_wgrad=batched_wgrad)
         else:
             x = child(x)
         if tapped is not None and tapped(last):
@@ -698,7 +766,8 @@ def densenet_encoder_forward(enc, x):
     cur = x.float().contiguous(memory_format=torch.channels_last)
     with _deferred_batch_counts():
         _run_children(list(enc.base_model.named_children()), cur,
-                      tapped=lambda name: any(fragment in name for fragment in enc.feat_names), taps=taps)
+                      tapped=lambda name: any(fragment in name for fragment in enc.feat_names), taps=taps,
+                      batched_wgrad=bool(getattr(enc, "batched_wgrad", False)))
     return taps
 
 

@@ -332,6 +332,46 @@ int bts_conv_wgrad_f32(const bts_conv_wgrad_desc* desc, bts_stream_t stream);
  * checked (non-null, alignment), never dereferenced; any of the four outputs may be NULL. */
 int bts_conv_wgrad_plan_f32(const bts_conv_wgrad_desc* desc, int* bm, int* bn, long* split, long* pix_per_split);
 
+/* Many weight gradients in one launch (a DenseNet block's 2*L problems average tens of microseconds each when launched
+ * one at a time, and each is split over pixels far enough to fill the chip on its own; taken together they fill it with
+ * little or no split).  Three calls:
+ *
+ *   bts_conv_wgrad_batch_table_bytes(n)   bytes of the table for n problems (host and device copy have the same size)
+ *   bts_conv_wgrad_batch_plan_f32(...)    host only, no GPU work, no device needed: validates every descriptor with the
+ *                                         rules of bts_conv_wgrad_f32 (and rejects nothing else), plans tiles and splits
+ *                                         for the batch as a whole and fills `table_host`
+ *   bts_conv_wgrad_batch_f32(...)         at most one launch per tile shape present in the batch plus one launch that
+ *                                         sums the partials of every split problem in wgrad_reduce's fixed order
+ *
+ * The table is relocatable: every pointer of every descriptor (x, dy, dw, pre_scale, pre_shift) -- together with the
+ * whole extent the kernel reads or writes through it -- must lie inside one of n_bases <= 8 caller-declared ranges
+ * [bases[j], bases[j] + base_bytes[j]) (16-byte aligned), else BTS_ERR_INVALID; the table stores (base index, byte
+ * offset) and the launch receives the current base pointers by value.  The caller copies table_host to the device once
+ * per geometry (table_dev) and may then launch every step with that step's buffers, uploading nothing more.  The launch
+ * receives base pointers only, no sizes: that every range given at launch is at least as large as the one given to the
+ * plan is the caller's contract (as for every buffer of this header), not something the launch can check.  descs[i].ws / ws_floats must be NULL / 0: the
+ * partials of the whole batch live in the one workspace `ws` of `ws_floats` floats at disjoint offsets (plan[i].ws_offset,
+ * in floats; -1 for an unsplit problem).  The plan never fails for lack of workspace: it lowers the splits, down to 1.
+ * The launch writes plan[i].split * n_bundles * c_out * ksize^2 * c_in floats at plan[i].ws_offset for every problem with
+ * split > 1 and nothing else of `ws`.  The plan is a function of the problems' shapes and ws_floats only -- not of the
+ * pointers or of the device; tile, split and pix_per_split do not depend on the order of the batch either (items follow their
+ * problems), ws_offset goes by position among problems of equal shape.  dw regions of different
+ * problems that overlap are a caller error (not detected): each is written by its own workgroups in no defined order.
+ * Like everything here the launch allocates nothing, synchronises nothing and is hipGraph-capturable.  n = 0 is valid
+ * and launches nothing. */
+typedef struct bts_conv_wgrad_batch_item {
+    int  bm, bn;             /* the dw tile of one workgroup, as in bts_conv_wgrad_plan_f32       */
+    long split;              /* workgroups along the pixel axis                                   */
+    long pix_per_split;      /* multiple of 32; (split-1)*pix_per_split < B*H*W                   */
+    long ws_offset;          /* floats into `ws` where this problem's partials live; -1: split 1  */
+} bts_conv_wgrad_batch_item;
+
+long bts_conv_wgrad_batch_table_bytes(int n);
+int  bts_conv_wgrad_batch_plan_f32(const bts_conv_wgrad_desc* descs, int n, const void* const* bases, const long* base_bytes,
+                                   int n_bases, long ws_floats, void* table_host, bts_conv_wgrad_batch_item* plan /* [n] or NULL */);
+int  bts_conv_wgrad_batch_f32(const void* table_host, const void* table_dev, int n, const void* const* bases, int n_bases,
+                              float* ws, bts_stream_t stream);
+
 /* Batched weight re-packing for the training step (the optimiser rewrites the OIHW parameters every iteration,
  * bts_main.py:606): one launch lays every registered weight out as bts_conv_fwd_f32 wants it.
  * table: n_entries device records of 14 int64 each --

@@ -35,6 +35,9 @@ def main():
     ap.add_argument("--native-loss", action="store_true", help="silog on the HIP loss kernels (no host sync) instead of torch")
     ap.add_argument("--fused-reduc", action="store_true",
                     help="reduction_1x1 -> LPG scales and reduc1x1 as single autograd nodes on the fused kernels (fused_reduction_train)")
+    ap.add_argument("--batched-wgrad", action="store_true",
+                    help="one multi-problem weight-gradient launch per DenseNet block (and per fused reduction scale) instead "
+                         "of one launch per layer (BtsModel.batched_wgrad)")
     a = ap.parse_args()
     # BASELINE config 5 (B=32 over 8 GPUs = 4 per GPU, DDP): launch with
     #   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 scripts/train_bench.py
@@ -56,6 +59,7 @@ def main():
     params = Params(a.encoder, 512, 80.0, "kitti")
     model = M.BtsModel(params).train().to(dev)
     model.fused_reduction_train = a.fused_reduc
+    model.batched_wgrad = a.batched_wgrad
     loss_fn = M.silog_loss(0.85, native=a.native_loss)
     if not a.no_freeze:
         trainer.set_misc(model, a.encoder)          # the reference freezes the stem conv and the encoder norm affines
@@ -103,7 +107,7 @@ def main():
                n_gpus=world, ddp=use_dist,
                loss="silog native (HIP)" if a.native_loss else "silog torch",
                config=dict(encoder=a.encoder, batch_per_gpu=B, height=H, width=W, decoder_only=a.decoder_only,
-                           fused_reduc=a.fused_reduc),
+                           fused_reduc=a.fused_reduc, batched_wgrad=a.batched_wgrad),
                peak_mem_gb=torch.cuda.max_memory_allocated() / 2**30)
     if a.trace:
         tr = ops.KernelTrace()
@@ -122,6 +126,7 @@ def main():
         for k, r in rows.items():
             r["tflops"] = r["flops"] / max(r["ms"], 1e-9) / 1e9
         res["kernels"] = rows
+        res["library_launches_per_step"] = len(tr.records)
         # the reduction scales on their own (library launches only: the torch elementwise kernels between them are not traced)
         res["reduction_launches"] = {"%s %s" % (kern, tag): dict(ms=v["ms"], launches=v["launches"])
                                      for kern, d in summ.items() for tag, v in d["tags"].items() if tag.startswith("reduc")}

@@ -1,5 +1,7 @@
 #!/usr/bin/env python3
-"""Per-shape timing of bts_conv_wgrad_f32 on the training configuration's layers (B=4, 352x704, DenseNet161-BTS)."""
+"""Per-shape timing of bts_conv_wgrad_f32 on the training configuration's layers (B=4, 352x704, DenseNet161-BTS), then
+one line per DenseNet161 block: the block's 2*L weight gradients as single launches against one batched launch
+(bts_conv_wgrad_batch_f32) on the same buffers."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -17,6 +19,56 @@ SHAPES = [  # name, B, h, w, cin, cout, k, dil, up
     ("conv1", 4, 352, 704, 36, 32, 3, 1, 1), ("reduc 32->16", 4, 352, 704, 32, 16, 1, 1, 1),
     ("reduc 8->4", 4, 352, 704, 8, 4, 1, 1, 1), ("reduc 128->64", 4, 88, 176, 128, 64, 1, 1, 1),
 ]
+
+BLOCKS = [("block 1", 88, 176, 96, 6), ("block 2", 44, 88, 192, 12), ("block 3", 22, 44, 384, 36), ("block 4", 11, 22, 1056, 24)]
+
+
+def _time(fn, n=10):
+    for _ in range(2):
+        fn()
+    torch.cuda.synchronize()
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    s.record()
+    for _ in range(n):
+        fn()
+    e.record()
+    torch.cuda.synchronize()
+    return s.elapsed_time(e) / n * 1e3
+
+
+def blocks(dev, ws, B=4, g=48, mid=192):
+    """The problems train._DenseBlockFn hands the weight-gradient kernels, on buffers laid out as it lays them out."""
+    for name, H, W, C0, L in BLOCKS:
+        npix, Ct = B * H * W, C0 + L * g
+        buf, G = torch.randn(npix, Ct, device=dev), torch.randn(npix, Ct, device=dev)
+        T1, D_T1 = torch.randn(L, npix, mid, device=dev), torch.randn(L, npix, mid, device=dev)
+        stats = torch.rand(L, 8, Ct, device=dev) + 0.5
+        DW = torch.empty(sum(mid * (C0 + i * g) + g * 9 * mid for i in range(L)), device=dev)
+        problems, at = [], 0
+        for i in range(L):
+            Ci = C0 + i * g
+            problems.append(dict(x=buf[:, :Ci], dy=D_T1[i], dw=DW[at:at + mid * Ci], B=B, h_in=H, w_in=W, c_in=Ci, c_out=mid, ksize=1,
+                                 pre=(stats[i, 2, :Ci], stats[i, 3, :Ci]), pre_relu=True))
+            at += mid * Ci
+            problems.append(dict(x=T1[i], dy=G[:, Ci:Ci + g], dw=DW[at:at + g * 9 * mid], B=B, h_in=H, w_in=W, c_in=mid, c_out=g, ksize=3,
+                                 pre=(stats[i, 6, :mid], stats[i, 7, :mid]), pre_relu=True))
+            at += g * 9 * mid
+        bases = [buf, G, T1, D_T1, stats, DW]
+        batch = ops.WgradBatch(problems, bases, ws.numel())
+
+        def singles():
+            for p in problems:
+                ops.conv_wgrad(p["x"], B, H, W, p["c_in"], p["dy"], p["c_out"], p["ksize"], ws=ws, pre=p["pre"], pre_relu=True)
+
+        us_single, us_batch = _time(singles), _time(lambda: batch.run(bases, ws))
+        splits = sorted({p[2] for p in batch.plan})
+        wgs = sum(-(-p["c_out"] // pl[0]) * -(-(p["c_in"] * p["ksize"] ** 2) // pl[1]) * pl[2] for p, pl in zip(problems, batch.plan))
+        print("%-8s px %6d  %2d problems  single launches %8.1f us  one batch %8.1f us  (x%.2f)  batch: %d workgroups, split %s, "
+              "%.1f MB of partials" % (name, npix, len(problems), us_single, us_batch, us_single / us_batch, wgs,
+                                       "-".join(str(v) for v in (splits[0], splits[-1])) if len(splits) > 1 else splits[0],
+                                       4e-6 * batch.ws_used), flush=True)
+        del buf, G, T1, D_T1, stats, DW, batch, problems
+
 
 def main():
     dev = torch.device("cuda:0")
@@ -39,6 +91,7 @@ def main():
         fl = 2.0 * B * H * W * cout * cin * k * k
         by = 4.0 * (B * h * w * cin + B * H * W * cout)
         print("%-14s px %7d  M=%4d N=%6d  %8.1f us  %6.1f TF/s  %6.0f GB/s" % (name, B * H * W, cout, cin * k * k, us, fl / us / 1e6, by / us / 1e3), flush=True)
+    blocks(dev, ws)
 
 if __name__ == "__main__":
     main()
