@@ -22,6 +22,7 @@ SYMBOLS = (
     "bts_depth_loss_ws_doubles", "bts_depth_loss_fwd_f32", "bts_depth_loss_bwd_f32",
     "bts_reduc_bwd_f32", "bts_reduc_bwd_max_waves",
     "bts_conv_wgrad_batch_table_bytes", "bts_conv_wgrad_batch_plan_f32", "bts_conv_wgrad_batch_f32",
+    "bts_adamw_table_bytes", "bts_adamw_flat_span", "bts_adamw_plan_f32", "bts_adamw_step_f32",
 )
 
 ABI_VERSION = 17
@@ -60,6 +61,29 @@ class ConvWgradDesc(C.Structure):
 class ConvWgradBatchItem(C.Structure):
     """struct bts_conv_wgrad_batch_item (include/bts_hip.h)."""
     _fields_ = [("bm", C.c_int), ("bn", C.c_int), ("split", C.c_long), ("pix_per_split", C.c_long), ("ws_offset", C.c_long)]
+
+
+class AdamwPack(C.Structure):
+    """struct bts_adamw_pack (include/bts_hip.h)."""
+    _fields_ = [("dst", C.c_void_p), ("k_pad", C.c_long), ("c_in_ld", C.c_int), ("mode", C.c_int)]
+
+
+class AdamwItem(C.Structure):
+    """struct bts_adamw_item (include/bts_hip.h)."""
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("numel", C.c_long),
+                ("hyper", C.c_int), ("c_out", C.c_int), ("c_in", C.c_int), ("ksize", C.c_int),
+                ("n_packs", C.c_int), ("reserved", C.c_int), ("packs", AdamwPack * 2)]
+
+
+class AdamwHyper(C.Structure):
+    """struct bts_adamw_hyper (include/bts_hip.h)."""
+    _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
+                ("weight_decay", C.c_double), ("step", C.c_double)]
+
+
+class AdamwPlanItem(C.Structure):
+    """struct bts_adamw_plan_item (include/bts_hip.h)."""
+    _fields_ = [("kind", C.c_int), ("reserved", C.c_int), ("first_block", C.c_long), ("n_blocks", C.c_long)]
 
 
 class BtsHipError(RuntimeError):
@@ -203,6 +227,14 @@ def load_real():
     lib.bts_depth_loss_fwd_f32.argtypes = [vp, vp, vp, f, l, i, f, vp, l, vp, vp, vp]
     lib.bts_depth_loss_bwd_f32.restype = i
     lib.bts_depth_loss_bwd_f32.argtypes = [vp, vp, vp, f, l, i, f, vp, vp, vp, vp]
+    lib.bts_adamw_table_bytes.restype = l
+    lib.bts_adamw_table_bytes.argtypes = [i]
+    lib.bts_adamw_flat_span.restype = l
+    lib.bts_adamw_flat_span.argtypes = []
+    lib.bts_adamw_plan_f32.restype = i
+    lib.bts_adamw_plan_f32.argtypes = [vp, i, vp, C.POINTER(l), vp]
+    lib.bts_adamw_step_f32.restype = i
+    lib.bts_adamw_step_f32.argtypes = [vp, i, l, vp, i, vp, vp]
     if lib.bts_hip_abi_version() != ABI_VERSION:
         raise BtsHipError("bts_amd: ABI version mismatch (%d != %d)" % (lib.bts_hip_abi_version(), ABI_VERSION))
     _lib = lib

@@ -105,7 +105,8 @@ class _Proxy:
         if not name.startswith("bts_") or name in ("bts_hip_error_string", "bts_hip_abi_version", "bts_conv_plan_f32",
                                                   "bts_conv_wgrad_plan_f32", "bts_conv_wgrad_batch_table_bytes",
                                                   "bts_conv_wgrad_batch_plan_f32", "bts_eval_ws_doubles", "bts_bn_train_ws_floats", "bts_pack_weights_blocks",
-                                                  "bts_depth_loss_ws_doubles"):
+                                                  "bts_depth_loss_ws_doubles", "bts_adamw_table_bytes", "bts_adamw_flat_span",
+                                                  "bts_adamw_plan_f32"):
             return real
         if name not in _KINDS:
             def passthrough(*args):

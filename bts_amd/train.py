@@ -63,7 +63,13 @@ class WeightPacker:
     (forward) and as the same layout of the flipped, transposed kernel (input gradient).  Entries are registered on
     first use; ``refresh()`` -- called at the top of each training forward -- re-packs every entry whose parameter
     changed (``Tensor._version``) in ONE launch of bts_pack_weights_f32.  A stale entry met later is re-packed on the
-    spot, so correctness never depends on ``refresh`` having been called."""
+    spot, so correctness never depends on ``refresh`` having been called.
+
+    ``versions_trusted``: whether ``Tensor._version`` tells, right now, which parameters changed.  False by default (torch's
+    fused optimisers rewrite the parameters without bumping it: begin_step() then re-packs everything); whoever stepped
+    last decides -- ``optim.NativeAdamW.step`` bumps every version it touches, re-packs the entries it can itself and sets
+    it True, the post-step hook of ``trainer.make_optimizer`` on a torch optimiser sets it False.  ``epoch`` counts changes
+    of the entry set (the native optimiser rebuilds its table when it moves)."""
 
     FWD, DGRAD = 0, 1
 
@@ -71,6 +77,8 @@ class WeightPacker:
         self.entries = {}          # (data_ptr, shape, c_in_ld, mode, groups) -> dict(wref, dst, version, rows)
         self._table = None
         self._table_key = None
+        self.versions_trusted = False
+        self.epoch = 0
 
     @staticmethod
     def bundle_channels(weight, groups):
@@ -148,6 +156,7 @@ class WeightPacker:
             e = self.entries[key] = dict(wref=weakref.ref(weight), ptr=weight.data_ptr(), rows=rows, version=-1,
                                          dst=torch.empty(shape, dtype=torch.float32, device=weight.device))
             self._table_key = None
+            self.epoch += 1
         if e["version"] != e["wref"]()._version:
             table, blocks, n_rows = self._table_for([e])
             self._launch([e], table, blocks, n_rows)
@@ -156,10 +165,15 @@ class WeightPacker:
     def refresh(self, force: bool = False):
         """Re-pack every registered weight whose parameter changed since its last packing -- with ``force``: every
         registered weight -- in one launch."""
-        dead = [k for k, e in self.entries.items() if e["wref"]() is None]
+        # strong references for the duration of the call: a registered weight that is only reachable through a reference
+        # cycle (every BtsModel is) can be collected by any allocation below, between this check and the launch
+        alive = {k: e["wref"]() for k, e in self.entries.items()}
+        dead = [k for k, w in alive.items() if w is None]
         for k in dead:
             del self.entries[k]
-        stale = [e for e in self.entries.values() if force or e["version"] != e["wref"]()._version]
+        if dead:
+            self.epoch += 1
+        stale = [e for k, e in self.entries.items() if force or e["version"] != alive[k]._version]
         if not stale:
             return
         key = tuple(id(e) for e in stale)
@@ -179,12 +193,16 @@ def begin_step():
     training loop -- torch's fused optimisers (``AdamW(fused=True)``, ``_fused_adamw_``) rewrite the parameters without
     bumping it -- and in steady state the optimiser has touched every weight anyway (one 0.5 ms launch per step).  For
     the same reason a training forward also ages the eval-mode packs and recorded graphs/plans of every model
-    (``workspace.invalidate_packs``): the next eval forward re-packs from the current values."""
+    (``workspace.invalidate_packs``): the next eval forward re-packs from the current values.
+
+    The exception is ``WeightPacker.versions_trusted``: after a step of ``optim.NativeAdamW`` the versions ARE the change
+    signal and the entries it re-packed itself are current, so only what is stale by version goes into the pack launch
+    (frozen weights are not touched; often nothing is launched at all)."""
     if _STEP_DEPTH[0] > 0:                 # inside model_step(): the model's forward already did this
         return
     from . import workspace
     workspace.invalidate_packs()
-    _PACKER.refresh(force=True)
+    _PACKER.refresh(force=not _PACKER.versions_trusted)
 
 
 _STEP_DEPTH = [0]

@@ -44,11 +44,20 @@ def set_misc(model, encoder_name: str, fix_first_conv_blocks: bool = False, fix_
 
 
 def make_optimizer(model, learning_rate: float = 1e-4, weight_decay: float = 1e-2, adam_eps: float = 1e-3,
-                   fused: Optional[bool] = None):
+                   fused: Optional[bool] = None, native: bool = False):
     """AdamW with weight decay on the encoder only (bts_main.py:354-356; defaults of arguments_train_eigen.txt).
     ``fused`` (default: on when every parameter lives on a GPU): torch's single-kernel-per-chunk implementation of the
-    same update instead of the multi-tensor one (~8 passes over the 47 M parameters)."""
+    same update instead of the multi-tensor one (~8 passes over the 47 M parameters).
+    ``native=True``: ``optim.NativeAdamW`` with the same two groups -- one HIP launch that also re-packs the convolution
+    weights it updates and gives the packer a trustworthy change signal (opt-in; not together with ``fused=True``)."""
     core = model.module if hasattr(model, "module") else model
+    if native:
+        if fused:
+            raise ValueError("make_optimizer: native=True and fused=True name two different implementations; pick one")
+        from .optim import NativeAdamW
+        return NativeAdamW([{'params': core.encoder.parameters(), 'weight_decay': weight_decay},
+                            {'params': core.decoder.parameters(), 'weight_decay': 0}],
+                           lr=learning_rate, eps=adam_eps)
     if fused is None:
         fused = all(p.is_cuda for p in core.parameters())
     opt = torch.optim.AdamW([{'params': core.encoder.parameters(), 'weight_decay': weight_decay},
@@ -58,8 +67,15 @@ def make_optimizer(model, learning_rate: float = 1e-4, weight_decay: float = 1e-
     # caches, recorded plans and captured graphs fingerprint: age them after every step, whatever mode the model is in
     # (a model kept in eval() and stepped by hand would otherwise go on computing with the previous step's packs).
     # Writers that bypass the optimiser and go through `.data` call bts_amd.workspace.invalidate_packs() themselves.
+    # For the same reason the training step's packer stops trusting versions (whoever stepped last decides).
     from . import workspace as _workspace
-    opt.register_step_post_hook(lambda optimizer, args, kwargs: _workspace.invalidate_packs())
+
+    def _after_step(optimizer, args, kwargs):
+        _workspace.invalidate_packs()
+        from . import train as _train
+        _train._PACKER.versions_trusted = False
+
+    opt.register_step_post_hook(_after_step)
     return opt
 
 
@@ -75,9 +91,14 @@ def gt_mask(depth_gt: torch.Tensor, dataset: str) -> torch.Tensor:
 
 
 def train_step(model, optimizer, criterion, image, focal, depth_gt, mask: Optional[torch.Tensor] = None,
-               lr: Optional[float] = None, dataset: str = 'kitti'):
+               lr: Optional[float] = None, dataset: str = 'kitti', guard_nonfinite: bool = False):
     """One iteration of bts_main.py:465-606 without the external losses: zero_grad, forward, silog on valid pixels,
-    backward, learning-rate update, optimiser step.  Returns (loss, the model's 6 outputs)."""
+    backward, learning-rate update, optimiser step.  Returns (loss, the model's 6 outputs).
+    ``guard_nonfinite`` (``optim.NativeAdamW`` only): a NaN / inf loss skips the update on the device -- parameters and
+    optimiser state keep their bits -- without the host reading the loss."""
+    from .optim import NativeAdamW
+    if guard_nonfinite and not isinstance(optimizer, NativeAdamW):
+        raise ValueError("train_step: guard_nonfinite needs the native optimiser (make_optimizer(native=True))")
     optimizer.zero_grad(set_to_none=True)
     outs = model(image, focal)
     if mask is None and getattr(criterion, "native", False):
@@ -91,7 +112,10 @@ def train_step(model, optimizer, criterion, image, focal, depth_gt, mask: Option
     if lr is not None:
         for group in optimizer.param_groups:
             group['lr'] = lr
-    optimizer.step()
+    if guard_nonfinite:
+        optimizer.step(skip=(~torch.isfinite(loss.detach())).to(torch.float32).reshape(1))
+    else:
+        optimizer.step()
     return loss, outs
 
 

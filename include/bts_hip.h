@@ -520,6 +520,71 @@ int bts_depth_loss_bwd_f32(const float* est, const float* gt, const unsigned cha
                            bts_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * AdamW for the training step in ONE launch over every parameter (torch.optim.AdamW with amsgrad=False, maximize=False;
+ * the reference's optimiser, pytorch/bts_main.py:354-356, 606), which also writes the updated convolution weights out in
+ * the layouts of bts_pack_weights_f32 while they are on the chip.
+ *
+ *   p <- p * (1 - lr*wd);  m <- m + (g - m) * (1 - beta1);  v <- beta2 * v + (1 - beta2) * g * g;
+ *   p <- p - step_size * m / (sqrt(v) * inv_sqrt_bc2 + eps),   step_size = lr / (1 - beta1^step),
+ *   inv_sqrt_bc2 = 1 / sqrt(1 - beta2^step)
+ * in fp32 with IEEE sqrt and division (m and v each end in one fused multiply-add, nothing else is contracted); step_size, inv_sqrt_bc2 and the factors
+ * (1 - lr*wd), (1 - beta1), (1 - beta2) are computed in double on the host by the launch call and rounded once.  The
+ * update is elementwise: its bits do not depend on the launch shape.
+ *
+ * An item is one parameter: p, g (gradient), m (exp_avg), v (exp_avg_sq), `numel` contiguous floats each, 4-byte aligned,
+ * and the index of its hyper-parameter record (< 8).  n_packs == 0: a FLAT record (c_out, c_in, ksize may all be 0; when
+ * given they must multiply to numel); 16 bytes per lane where p, g, m, v share their offset to a 16-byte line.
+ * n_packs 1 or 2: a TILE record -- a dense OIHW weight [c_out][c_in][k][k], k in {1, 3} -- whose new values are also
+ * written to each pack destination as dst[row*k_pad + tap*c_in_ld + c]:
+ *   mode 0 (forward)        : row = c_out index, c = c_in index,  tap as stored,        c_in_ld >= c_in
+ *   mode 1 (input gradient) : row = c_in index,  c = c_out index, tap = k*k-1 - stored, c_in_ld >= c_out
+ * k_pad >= k*k*c_in_ld, dst 16-byte aligned.  Only the real elements are written: the padding of a destination (rows
+ * beyond the real ones, c >= inner, columns >= k*k*c_in_ld) is never touched.
+ *
+ *   bts_adamw_table_bytes(n)  bytes of the table for n items (host and device copy have the same size; 8-byte aligned
+ *                             records, the device copy 16-byte aligned)
+ *   bts_adamw_flat_span()     floats of a flat record that one workgroup covers
+ *   bts_adamw_plan_f32(...)   host only, no device needed: validates the items and fills `table_host`; *total_blocks is
+ *                             the grid; plan (may be NULL) receives kind (0 flat, 1 tile), first_block (the prefix sum of
+ *                             n_blocks) and n_blocks per item.  kind and the block counts are a function of the shapes and
+ *                             n_packs only, never of the pointers.  BTS_ERR_INVALID: a null pointer, numel <= 0,
+ *                             c_out*c_in*k*k != numel, ksize outside {1, 3} together with packs, more than 2 packs, a pack
+ *                             with c_in_ld < inner or k_pad < k*k*c_in_ld or a mode outside {0, 1}, a destination not
+ *                             16-byte aligned, p / g / m / v not 4-byte aligned, a hyper index outside [0, 8), more than
+ *                             2^31 - 1 blocks.  n = 0 is valid (total_blocks = 0).
+ *   bts_adamw_step_f32(...)   the launch.  `hyper`: n_hyper <= 8 HOST records, passed to the kernel by value.  `skip`:
+ *                             optional DEVICE scalar; non-zero or NaN leaves every byte of every buffer untouched (a
+ *                             non-finite loss skips the step without a host read).  Allocates nothing, synchronises
+ *                             nothing, hipGraph-capturable.  n = 0 launches nothing.  Overlapping items are a caller error.
+ */
+typedef struct bts_adamw_pack {
+    float* dst;
+    long   k_pad;
+    int    c_in_ld;
+    int    mode;             /* 0 = forward layout, 1 = input-gradient layout */
+} bts_adamw_pack;
+
+typedef struct bts_adamw_item {
+    float* p; const float* g; float* m; float* v;
+    long   numel;
+    int    hyper;
+    int    c_out, c_in, ksize;
+    int    n_packs, reserved;
+    bts_adamw_pack packs[2];
+} bts_adamw_item;
+
+typedef struct bts_adamw_hyper { double lr, beta1, beta2, eps, weight_decay, step; } bts_adamw_hyper;
+
+typedef struct bts_adamw_plan_item { int kind, reserved; long first_block, n_blocks; } bts_adamw_plan_item;
+
+long bts_adamw_table_bytes(int n);
+long bts_adamw_flat_span(void);
+int  bts_adamw_plan_f32(const bts_adamw_item* items, int n, void* table_host, long* total_blocks,
+                        bts_adamw_plan_item* plan /* [n] or NULL */);
+int  bts_adamw_step_f32(const void* table_dev, int n, long total_blocks, const bts_adamw_hyper* hyper, int n_hyper,
+                        const float* skip, bts_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * One-call execution of a recorded forward ("plan").  A BtsModel forward is a fixed sequence of ~120 (B=1) to ~460
  * (B=16, four sub-batches) launches of the entry points above with arguments that depend only on the input shape:
  * workspaces, packed weights and dims are fixed per shape, only the caller's input / output tensors move.  The host

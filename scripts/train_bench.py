@@ -38,6 +38,9 @@ def main():
     ap.add_argument("--batched-wgrad", action="store_true",
                     help="one multi-problem weight-gradient launch per DenseNet block (and per fused reduction scale) instead "
                          "of one launch per layer (BtsModel.batched_wgrad)")
+    ap.add_argument("--native-optim", action="store_true",
+                    help="AdamW as one HIP launch that also re-packs the conv weights it updates (optim.NativeAdamW) instead "
+                         "of torch's fused AdamW + a full re-pack")
     a = ap.parse_args()
     # BASELINE config 5 (B=32 over 8 GPUs = 4 per GPU, DDP): launch with
     #   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 scripts/train_bench.py
@@ -63,7 +66,7 @@ def main():
     loss_fn = M.silog_loss(0.85, native=a.native_loss)
     if not a.no_freeze:
         trainer.set_misc(model, a.encoder)          # the reference freezes the stem conv and the encoder norm affines
-    opt = trainer.make_optimizer(model, 1e-4, 1e-2, 1e-3)
+    opt = trainer.make_optimizer(model, 1e-4, 1e-2, 1e-3, native=a.native_optim)
     core = model
     if use_dist:
         model = trainer.wrap_ddp(model, dev)   # gradient all-reduce over RCCL, overlapped with backward by DDP's buckets
@@ -77,12 +80,21 @@ def main():
         fs = synth.encoder_features(synth.ENCODER_CHANNELS[a.encoder], B, H, W, seed=3)
         feats = [None] + [torch.from_numpy(f).to(dev).requires_grad_(True) for f in fs[1:]]
 
-    def step():
+    opt_events = []          # --trace: (start, end) events around optimizer.step(), whatever implementation it is
+
+    def step(timed=False):
         opt.zero_grad(set_to_none=True)
         outs = core.decoder(feats, focal) if a.decoder_only else model(x, focal)
         loss = loss_fn(outs[4], gt, mask)
         loss.backward()
-        opt.step()
+        if timed:
+            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+            ev[0].record()
+            opt.step()
+            ev[1].record()
+            opt_events.append(ev)
+        else:
+            opt.step()
         return loss
 
     for i in range(a.warmup):
@@ -107,14 +119,20 @@ def main():
                n_gpus=world, ddp=use_dist,
                loss="silog native (HIP)" if a.native_loss else "silog torch",
                config=dict(encoder=a.encoder, batch_per_gpu=B, height=H, width=W, decoder_only=a.decoder_only,
-                           fused_reduc=a.fused_reduc, batched_wgrad=a.batched_wgrad),
+                           fused_reduc=a.fused_reduc, batched_wgrad=a.batched_wgrad, native_optim=a.native_optim),
                peak_mem_gb=torch.cuda.max_memory_allocated() / 2**30)
     if a.trace:
         tr = ops.KernelTrace()
         ops.set_trace(tr)
-        step()
+        step(timed=True)
         ops.set_trace(None)
         summ = tr.summary()
+        # the whole optimiser step on the stream (torch's fused AdamW is not a library launch, so it has no trace tag); the
+        # native launch alone is the `adamw` row below (tag optim.adamw), set against 36 B per updated parameter
+        res["optimizer_step_ms"] = opt_events[0][0].elapsed_time(opt_events[0][1])
+        n_upd = sum(p.numel() for g in opt.param_groups for p in g["params"] if p.grad is not None)
+        res["updated_parameters"] = n_upd
+        res["adamw_bound_ms_at_6.3TBps"] = 36.0 * n_upd / 6.3e12 * 1e3
         rows = {}
         for kern, d in summ.items():
             for tag, v in d["tags"].items():
