@@ -23,6 +23,7 @@ SYMBOLS = (
     "bts_reduc_bwd_f32", "bts_reduc_bwd_max_waves",
     "bts_conv_wgrad_batch_table_bytes", "bts_conv_wgrad_batch_plan_f32", "bts_conv_wgrad_batch_f32",
     "bts_adamw_table_bytes", "bts_adamw_flat_span", "bts_adamw_plan_f32", "bts_adamw_step_f32",
+    "bts_upconv_up9_fwd_f32", "bts_upconv_up9_plan",
 )
 
 ABI_VERSION = 17
@@ -217,6 +218,10 @@ def load_real():
     lib.bts_get_depth_f32.argtypes = [vp, vp, i, i, i, i, f, vp, vp, vp]
     lib.bts_upconv_combine_f32.restype = i
     lib.bts_upconv_combine_f32.argtypes = [vp, l, i, i, i, i, vp, vp, i, vp, l, vp]
+    lib.bts_upconv_up9_fwd_f32.restype = i
+    lib.bts_upconv_up9_fwd_f32.argtypes = [vp, l, i, i, i, i, vp, i, vp, vp, i, vp, l, vp]
+    lib.bts_upconv_up9_plan.restype = i
+    lib.bts_upconv_up9_plan.argtypes = [i, i, i, i, i, i, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_long)]
     lib.bts_eval_ws_doubles.restype = l
     lib.bts_eval_ws_doubles.argtypes = [i, i, i]
     lib.bts_eval_depth_metrics_f32.restype = i

@@ -20,6 +20,7 @@ There is no PyTorch/CPU fallback: CPU tensors or a missing libbts_hip.so raise.
 """
 from __future__ import annotations
 
+import os
 from typing import Dict, Tuple
 
 import torch
@@ -189,10 +190,12 @@ class upconv(nn.Module):
         self.ratio = ratio
         self._packs = PackCache(self)
         self._packs_taps = PackCache(self)
+        self._packs_up9 = PackCache(self)
 
     def packed(self):
         """ratio 2: ("subpix", four 2x2 kernels, ops.pack_upconv_subpixel) or -- ``self.tap_gemm`` -- ("taps", the nine taps
-        side by side as one 1x1 weight, ops.pack_upconv_taps); plain 3x3 packing otherwise."""
+        side by side as one 1x1 weight, ops.pack_upconv_taps); plain 3x3 packing otherwise.  A "subpix" layer that the
+        library's plan query takes (run_nhwc) runs from a third form instead, ``packed_up9``."""
         def build():
             if self.ratio == 2 and self.tap_gemm:
                 return ("taps",) + ops.pack_upconv_taps(self.conv.weight.detach())
@@ -202,6 +205,15 @@ class upconv(nn.Module):
         cache = self._packs_taps if (self.ratio == 2 and self.tap_gemm) else self._packs
         return cache.get(self.conv.weight.device, build)
 
+    def packed_up9(self):
+        """("up9", U): the weight in shared-patch F(2x2,2x2) form (ops.pack_upconv_up9), made once per weight and device."""
+        return self._packs_up9.get(self.conv.weight.device, lambda: ("up9", ops.pack_upconv_up9(self.conv.weight.detach())))
+
+    # sub-pixel layers take the fused F(2x2,2x2) kernel (9 products per source pixel instead of 16) where the library's plan
+    # query says so: fp32, whole 32-channel chunks, no prologue, a well-filled tile grid and a chip-filling declared launch
+    # (ops.upconv_up9_plan).  False (or BTS_UPCONV_UP9=0) keeps every layer on the sub-pixel halo kernel (A/B)
+    up9 = os.environ.get("BTS_UPCONV_UP9", "1").strip() not in ("", "0")
+
     # nearest-2x + 3x3 as ONE 1x1 convolution with the nine taps side by side plus a tap-sum pass (9 tap-products per
     # source pixel) instead of four 2x2 parity convolutions (16): set by the decoder for upconv5, whose 11x38 x 2208-channel
     # source map is where the GEMM dominates and the extra pass is small (DESIGN.md section 3)
@@ -210,9 +222,14 @@ class upconv(nn.Module):
     def run_nhwc(self, x2d, B, h, w, y2d, taps_buf=None, e2=None, pre=None, pre_relu=False, c_in_real=None, splitk_ws=None,
                  tag="decoder_upconv"):
         """ELU(conv3x3(nearest2x(x))) [-> e2 affine] from the NHWC view x2d [B*h*w, C] into y2d [B*2h*2w, cout]."""
+        cout, c_in = self.conv.out_channels, self.conv.in_channels
+        cin = c_in_real if c_in_real is not None else c_in
+        # asked before packed(): a layer on the F(2x2,2x2) kernel never builds the sub-pixel form of its weight
+        if (self.up9 and self.ratio == 2 and not self.tap_gemm and pre is None and not pre_relu and c_in % 32 == 0
+                and cout % 32 == 0 and ops.upconv_up9_plan(h, w, c_in, cout).eligible):
+            return ops.upconv_up9_forward(x2d, B, h, w, self.packed_up9()[1], c_in, cout, y2d, act=ops.ACT_ELU, e2=e2, tag=tag,
+                                          c_in_real=cin)
         form, wp, n_or_pad, c_in_ld = self.packed()
-        cout = self.conv.out_channels
-        cin = c_in_real if c_in_real is not None else self.conv.in_channels
         if form == "taps":
             if taps_buf is None:
                 taps_buf = torch.empty((B * h * w, 9 * cout), dtype=torch.float32, device=x2d.device)

@@ -786,6 +786,7 @@ thread_local ConvChoice* g_dry = nullptr;
 #include "conv_halo.inc"
 #include "conv_halo_emu.inc"
 #include "conv_wino.inc"
+#include "conv_up9.inc"
 #include "conv_1x1.inc"
 #include "conv_stem.inc"
 
@@ -1166,4 +1167,43 @@ extern "C" int bts_conv_plan_ksteps_f32(const bts_conv_desc* d, long* issued, lo
     const int rc = conv_dry_run(d, c);
     *issued = c.ksteps_issued; *dense = c.ksteps_dense;      // both 0 for the kernel families that never skip
     return rc;
+}
+
+// ---- sub-pixel upconv, shared-patch F(2x2,2x2) form (conv_up9.inc): its own opt-in entry point and plan query, so that
+//      bts_conv_fwd_f32 / bts_conv_plan_f32 answer for every descriptor exactly as they did without it
+extern "C" int bts_upconv_up9_plan(int h, int w, int c_in, int c_out, int precision, int fill_frames, int* bm, int* bn,
+                                   long* workgroups) {
+    if (!bm || !bn || !workgroups) return BTS_ERR_INVALID;
+    if (fill_frames < 0 || fill_frames > 4096) return BTS_ERR_INVALID;
+    const int prec_env = knobs().precision;
+    long wgs = 0;
+    const bool ok = up9_eligible(h, w, c_in, c_out, prec_env >= 0 ? prec_env : precision, fill_frames > 0 ? fill_frames : knobs().fill_frames, &wgs);
+    *bm = ok ? UP9_WY * UP9_WX : 0; *bn = ok ? 32 : 0; *workgroups = ok ? wgs : 0;
+    return 0;
+}
+
+extern "C" int bts_upconv_up9_fwd_f32(const float* x, long x_pix_stride, int B, int h, int w, int c_in, const float* u, int c_out,
+                                      const float* e2_scale, const float* e2_shift, int act, float* y, long y_pix_stride,
+                                      bts_stream_t stream) {
+    if (!x || !u || !y || B <= 0 || h <= 0 || w <= 0 || c_in <= 0 || c_out <= 0) return BTS_ERR_INVALID;
+    if ((c_in % BK) || (c_out % 32)) return BTS_ERR_UNSUPPORTED;
+    if ((x_pix_stride & 3) || x_pix_stride < c_in || y_pix_stride < c_out) return BTS_ERR_INVALID;
+    if (((uintptr_t)x & 15) || ((uintptr_t)u & 15) || ((uintptr_t)y & 3)) return BTS_ERR_INVALID;
+    if ((e2_scale == nullptr) != (e2_shift == nullptr) || act < 0 || act > 2) return BTS_ERR_INVALID;
+    // the kernel addresses the source map with 32-bit element offsets and decodes tiles with 32-bit arithmetic
+    // (and an output row's columns with a 32-bit per-lane offset)
+    if ((double)B * h * w * (double)x_pix_stride >= 4294967296.0 || (double)h * w >= 2147483648.0 ||
+        (double)(2 * w + 64) * (double)y_pix_stride >= 4294967296.0) return BTS_ERR_UNSUPPORTED;
+    Up9Args a;
+    a.x = x; a.x_pix_stride = x_pix_stride; a.B = B; a.H = h; a.W = w; a.c_in = c_in;
+    a.u = u; a.c_out = c_out; a.e2_scale = e2_scale; a.e2_shift = e2_shift; a.act = act;
+    a.y = y; a.y_pix_stride = y_pix_stride;
+    double fill;
+    up9_grid(h, w, &a.n_ty, &a.n_tx, &fill);
+    a.n_ntiles = c_out / 32;
+    const long nwg = (long)B * a.n_ty * a.n_tx * a.n_ntiles;
+    if (nwg > 0x7fffffffL) return BTS_ERR_UNSUPPORTED;
+    a.ntiles = (int)nwg;
+    hipLaunchKernelGGL(conv_up9_kernel<32>, dim3((unsigned)nwg), dim3(256), 0, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
 }

@@ -78,6 +78,12 @@ extern "C" int bts_plan_run(bts_op* ops, int n_ops, const bts_plan_patch* patche
                                             a.y_pix_stride, stream);
                 break;
             }
+            case BTS_OP_UPCONV_UP9: {
+                auto& a = o.u.upconv_up9;
+                rc = bts_upconv_up9_fwd_f32(a.x, a.x_pix_stride, a.B, a.h, a.w, a.c_in, a.u, a.c_out, a.e2_scale, a.e2_shift, a.act,
+                                            a.y, a.y_pix_stride, stream);
+                break;
+            }
             default: rc = BTS_ERR_INVALID;
         }
         o.failed_code = rc;

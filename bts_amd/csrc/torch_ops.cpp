@@ -312,6 +312,39 @@ void conv_fwd(const Tensor& x, const Tensor& w, OptTensor pre_scale, OptTensor p
     check_rc(bts_conv_fwd_f32(&d, current_stream()), op);
 }
 
+// ---------------------------------------------------------------------------------------- upconv, F(2x2,2x2) form
+// nearest-2x + conv3x3 + activation + affine (bts.py:90-94) as one launch of the shared-patch F(2x2,2x2) kernel
+// (bts_upconv_up9_fwd_f32).  x: [B*h*w, >= c_in] NHWC view; u: ops.pack_upconv_up9 (36 * c_in * c_out floats);
+// y: [B*2h*2w, c_out] NHWC view.  geom = {B, h, w, c_in, c_out, act}.
+void upconv_up9(const Tensor& x, const Tensor& u, OptTensor e2_scale, OptTensor e2_shift, Tensor y, std::vector<int64_t> geom) {
+    const char* op = "bts_hip::upconv_up9";
+    TORCH_CHECK(geom.size() == 6, op, ": geom must hold 6 integers, got ", geom.size());
+    const int64_t B = geom[0], h = geom[1], w = geom[2], c_in = geom[3], c_out = geom[4], act = geom[5];
+    TORCH_CHECK(B > 0 && h > 0 && w > 0 && c_in > 0 && c_out > 0, op, ": non-positive dimension");
+    TORCH_CHECK(c_in % 32 == 0 && c_out % 32 == 0, op, ": c_in (", c_in, ") and c_out (", c_out, ") must be multiples of 32");
+    const long xs = rows2d_stride(x, op, "x"), ys = rows2d_stride(y, op, "y");
+    need_f32_cuda(u, op, "u");
+    same_device(x, u, op, "u");
+    same_device(x, y, op, "y");
+    TORCH_CHECK(x.size(0) == B * h * w && x.size(1) >= c_in, op, ": x (", x.sizes(), ") is not a [B*h*w, >= c_in] view");
+    TORCH_CHECK(y.size(0) == 4 * B * h * w && y.size(1) == c_out, op, ": y (", y.sizes(), ") is not a [B*2h*2w, c_out] view");
+    TORCH_CHECK(u.is_contiguous() && u.numel() == 36 * c_in * c_out, op, ": u must be the contiguous F(2x2,2x2) form of the weight, ",
+                36 * c_in * c_out, " floats (ops.pack_upconv_up9), got ", u.numel());
+    auto vec = [&](const OptTensor& t, const char* what) -> const float* {
+        if (!(t.has_value() && t->defined())) return nullptr;
+        need_f32_cuda(*t, op, what);
+        same_device(x, *t, op, what);
+        TORCH_CHECK(t->is_contiguous() && t->numel() >= c_out, op, ": ", what, " must be a contiguous vector of at least ", c_out, " floats");
+        return t->data_ptr<float>();
+    };
+    const float* es = vec(e2_scale, "e2_scale");
+    const float* eb = vec(e2_shift, "e2_shift");
+    TORCH_CHECK((es == nullptr) == (eb == nullptr), op, ": give both e2 vectors or neither");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+    check_rc(bts_upconv_up9_fwd_f32(x.data_ptr<float>(), xs, (int)B, (int)h, (int)w, (int)c_in, u.data_ptr<float>(), (int)c_out, es, eb, (int)act,
+                                    y.data_ptr<float>(), ys, current_stream()), op);
+}
+
 // ------------------------------------------------------------------------------------------------------ training losses
 // silog_loss / depth_l1_loss (pytorch/bts.py:41-63) over the valid pixels of the whole batch, csrc/loss.hip: no boolean gather, no host
 // sync.  kind 0 = silog (param = variance_focus), 1 = asymmetric L1 (param = inbalance_to_closer); mask bool / uint8 or None (gt > gt_min).
@@ -381,6 +414,7 @@ TORCH_LIBRARY(bts_hip, m) {
     m.def("conv_fwd(Tensor x, Tensor w, Tensor? pre_scale, Tensor? pre_shift, Tensor? e1_scale, Tensor? e1_shift, Tensor? e2_scale, "
           "Tensor? e2_shift, Tensor(a!) y, Tensor(b!)? y2, Tensor? res, Tensor(c!)? splitk_ws, Tensor[] tail_planes, Tensor? w_split, "
           "Tensor? w_wino, int[] geom) -> ()");
+    m.def("upconv_up9(Tensor x, Tensor u, Tensor? e2_scale, Tensor? e2_shift, Tensor(a!) y, int[] geom) -> ()");
     m.def("depth_loss(Tensor est, Tensor gt, Tensor? mask, float gt_min, int kind, float param) -> (Tensor loss, Tensor stats)");
     m.def("depth_loss_backward(Tensor est, Tensor gt, Tensor? mask, float gt_min, int kind, float param, Tensor stats, Tensor grad_loss) -> Tensor");
 }
@@ -394,6 +428,7 @@ TORCH_LIBRARY_IMPL(bts_hip, CUDA, m) {
     m.impl("reduc_lpg_train", &reduc_lpg_train);
     m.impl("reduction_1x1_train", &reduction_1x1_train);
     m.impl("conv_fwd", &conv_fwd);
+    m.impl("upconv_up9", &upconv_up9);
     m.impl("depth_loss", &depth_loss);
     m.impl("depth_loss_backward", &depth_loss_backward);
 }

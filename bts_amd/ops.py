@@ -925,6 +925,161 @@ def upconv_combine(taps2d: torch.Tensor, B: int, h: int, w: int, c: int, y2d: to
     return y2d
 
 
+# ---- upconv in shared-patch F(2x2,2x2) form (csrc/conv_up9.inc): 9 products per source pixel instead of the sub-pixel form's 16
+_UP9_S = {0: ((1.0, 0.0, 0.0), (0.0, 1.0, 1.0)), 1: ((1.0, 1.0, 0.0), (0.0, 0.0, 1.0))}    # parity -> 2x3 row sums (as _SUBPIX_SETS)
+_UP9_G = ((1.0, 0.0), (1.0, 1.0), (0.0, 1.0))
+
+
+def _up9_fragment_order(U: torch.Tensor) -> torch.Tensor:
+    """[cls, n, k, a, b] -> the flat order conv_up9_kernel loads (include/bts_hip.h, bts_upconv_up9_fwd_f32)."""
+    _, cout, cin, _, _ = U.shape
+    U = U.reshape(4, cout // 32, 32, cin // 32, 4, 2, 4, 3, 3)          # (cls, ct, li, chunk, g, lh, q, a, b)
+    return U.permute(7, 8, 3, 1, 0, 4, 5, 2, 6).contiguous().view(-1)   # (a, b, chunk, ct, cls, g, lh, li, q)
+
+
+def pack_upconv_up9(w: torch.Tensor) -> torch.Tensor:
+    """upconv weight [c_out, c_in, 3, 3] (c_in, c_out multiples of 32) -> U = G g_(py,px) G^T for the four parity classes
+    of pack_upconv_subpixel (g = the pre-summed 2x2 filters, G = [[1,0],[1,1],[0,1]]), fp32, in the MFMA B-fragment order
+    bts_upconv_up9_fwd_f32 loads: 36 * c_in * c_out floats.  Every U element is a plain fp32 sum of at most nine of the
+    3x3 weights.  Once per weight (inference weights are constant; upconv.packed caches it)."""
+    cout, cin, kh, kw = w.shape
+    if kh != 3 or kw != 3 or cin % 32 or cout % 32:
+        raise BtsHipError("pack_upconv_up9: needs a [c_out, c_in, 3, 3] weight with c_in and c_out multiples of 32")
+    wf = w.detach().float()
+    U = torch.empty((4, cout, cin, 3, 3), dtype=torch.float32, device=w.device)
+    for py in (0, 1):
+        for px in (0, 1):
+            g = {}
+            for ty in (0, 1):
+                for tx in (0, 1):
+                    acc = None
+                    for ky in _SUBPIX_SETS[(py, ty)]:
+                        for kx in _SUBPIX_SETS[(px, tx)]:
+                            acc = wf[:, :, ky, kx] if acc is None else acc + wf[:, :, ky, kx]
+                    g[(ty, tx)] = acc
+            rows = {(0, 0): g[(0, 0)], (0, 1): g[(0, 1)], (2, 0): g[(1, 0)], (2, 1): g[(1, 1)],
+                    (1, 0): g[(0, 0)] + g[(1, 0)], (1, 1): g[(0, 1)] + g[(1, 1)]}                # G g
+            for a in range(3):
+                U[2 * py + px, :, :, a, 0] = rows[(a, 0)]
+                U[2 * py + px, :, :, a, 1] = rows[(a, 0)] + rows[(a, 1)]
+                U[2 * py + px, :, :, a, 2] = rows[(a, 1)]
+    return _up9_fragment_order(U)
+
+
+def pack_upconv_up9_reference(w: torch.Tensor) -> torch.Tensor:
+    """torch fp64 statement of pack_upconv_up9, kept as its test oracle: U_(py,px)[a][b] = sum_(ky,kx) (G S_py)[a][ky]
+    w[ky][kx] (G S_px)[b][kx] straight from the 3x3 weight (S_p = the 2x3 row-sum matrix of parity p), computed in fp64
+    and rounded once."""
+    cout, cin, kh, kw = w.shape
+    if kh != 3 or kw != 3 or cin % 32 or cout % 32:
+        raise BtsHipError("pack_upconv_up9: needs a [c_out, c_in, 3, 3] weight with c_in and c_out multiples of 32")
+    G = torch.tensor(_UP9_G, dtype=torch.float64, device=w.device)
+    R = [G @ torch.tensor(_UP9_S[p], dtype=torch.float64, device=w.device) for p in (0, 1)]      # [3, 3] per parity
+    wd = w.detach().double()
+    U = torch.stack([torch.einsum("ay,nkyx,bx->nkab", R[py], wd, R[px]) for py in (0, 1) for px in (0, 1)])
+    return _up9_fragment_order(U.float())
+
+
+def upconv_up9_reference(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """The formulation itself in torch (any dtype, CPU or GPU), window by window as the kernel does it: x [B, c_in, H, W],
+    w [c_out, c_in, 3, 3] -> conv3x3(nearest2x(x)) [B, c_out, 2H, 2W].  Test oracle of the identity, not a product path."""
+    B, cin, H, W = x.shape
+    cout = w.shape[0]
+    dt, dev = x.dtype, x.device
+    G = torch.tensor(_UP9_G, dtype=dt, device=dev)
+    Bt = torch.tensor(((1.0, -1.0, 0.0), (0.0, 1.0, 0.0), (0.0, -1.0, 1.0)), dtype=dt, device=dev)
+    At = torch.tensor(((1.0, 1.0, 0.0), (0.0, 1.0, 1.0)), dtype=dt, device=dev)
+    nwy, nwx = H // 2 + 1, W // 2 + 1
+    xp = F.pad(x, (1, 2 * nwx - W, 1, 2 * nwy - H))                                  # source rows -1 .. 2 nwy - 1
+    d = xp.unfold(2, 3, 2).unfold(3, 3, 2)                                           # [B, c, nwy, nwx, 3, 3]: window (wy, wx)
+    V = torch.einsum("ar,bkyxrc,ec->bkyxae", Bt, d, Bt)
+    out = torch.zeros((B, cout, 2 * H + 4, 2 * W + 4), dtype=dt, device=dev)         # output row o lives at o + 1
+    cover = torch.zeros((2 * H + 4, 2 * W + 4), dtype=torch.int32, device=dev)
+    for py in (0, 1):
+        for px in (0, 1):
+            Ry = G @ torch.tensor(_UP9_S[py], dtype=dt, device=dev)
+            Rx = G @ torch.tensor(_UP9_S[px], dtype=dt, device=dev)
+            U = torch.einsum("ay,nkyx,bx->nkab", Ry, w.to(dt), Rx)
+            M = torch.einsum("bkyxae,nkae->bnyxae", V, U)
+            Y = torch.einsum("ia,bnyxae,je->bnyxij", At, M, At)                      # [B, n, wy, wx, 2, 2]
+            for i in (0, 1):
+                for j in (0, 1):
+                    # source position (2 wy - py + i, 2 wx - px + j) -> output pixel (2 sy + py, 2 sx + px), stored at + 1
+                    r0, c0 = 2 * (i - py) + py + 1, 2 * (j - px) + px + 1
+                    out[:, :, r0:r0 + 4 * nwy:4, c0:c0 + 4 * nwx:4] += Y[..., i, j]
+                    cover[r0:r0 + 4 * nwy:4, c0:c0 + 4 * nwx:4] += 1
+    if not bool((cover[1:2 * H + 1, 1:2 * W + 1] == 1).all()):
+        raise BtsHipError("upconv_up9_reference: an output pixel is not covered exactly once")
+    return out[:, :, 1:2 * H + 1, 1:2 * W + 1].contiguous()
+
+
+class Up9Plan(tuple):
+    """(bm, bn, workgroups per frame) of bts_upconv_up9_plan; all 0 = the layer stays on the sub-pixel path."""
+    bm = property(lambda self: self[0])
+    bn = property(lambda self: self[1])
+    workgroups = property(lambda self: self[2])
+    eligible = property(lambda self: self[0] > 0)
+
+
+def upconv_up9_plan(h: int, w: int, c_in: int, c_out: int, precision=None, fill_frames: Optional[int] = None) -> Up9Plan:
+    """Should this upconv take upconv_up9_forward?  Host-only query (bts_upconv_up9_plan); ``precision`` / ``fill_frames``
+    default to the launch_config in force."""
+    ff, pr = current_launch_config()
+    if precision is not None:
+        if precision not in _PRECISIONS:
+            raise BtsHipError("upconv_up9_plan: precision must be 'fp32' / 0, 'bf16x3' / 1 or 'bf16' / 2")
+        pr = _PRECISIONS[precision]
+    if fill_frames is not None:
+        ff = int(fill_frames)
+    bm, bn, wgs = C.c_int(0), C.c_int(0), C.c_long(0)
+    _lib.check(_lib.load_real().bts_upconv_up9_plan(int(h), int(w), int(c_in), int(c_out), int(pr), int(ff), C.byref(bm), C.byref(bn),
+                                                     C.byref(wgs)), "bts_upconv_up9_plan")
+    return Up9Plan((bm.value, bn.value, wgs.value))
+
+
+def upconv_up9_forward(x2d: torch.Tensor, B: int, h: int, w: int, u: torch.Tensor, c_in: int, c_out: int, y2d: torch.Tensor,
+                       act: int = ACT_ELU, e2: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, tag: str = "decoder_upconv",
+                       c_in_real: Optional[int] = None):
+    """act(conv3x3(nearest2x(x))) [-> e2 affine] in one launch of the F(2x2,2x2) kernel (bts_upconv_up9_fwd_f32):
+    x2d [B*h*w, >= c_in] NHWC view, u from pack_upconv_up9, y2d [B*2h*2w, c_out] NHWC view (a channel slice is fine).
+    Runs whatever the plan query says: callers ask upconv_up9_plan first."""
+    xs, xc = _rows2d(x2d, "upconv_up9_forward")
+    ys, yc = _rows2d(y2d, "upconv_up9_forward")
+    _need(u, "upconv_up9_forward")
+    if c_in % 32 or c_out % 32 or xc < c_in or yc != c_out or x2d.shape[0] != B * h * w or y2d.shape[0] != 4 * B * h * w:
+        raise BtsHipError("upconv_up9_forward: views %s / %s do not fit B=%d %dx%d, %d -> %d channels (multiples of 32)"
+                          % (tuple(x2d.shape), tuple(y2d.shape), B, h, w, c_in, c_out))
+    if u.numel() != 36 * c_in * c_out or not u.is_contiguous():
+        raise BtsHipError("upconv_up9_forward: u must come from pack_upconv_up9 (36 * c_in * c_out floats)")
+    if act not in (ACT_NONE, ACT_RELU, ACT_ELU):
+        raise BtsHipError("upconv_up9_forward: act must be none, ReLU or ELU")
+    es = eb = None
+    if e2 is not None:
+        es, eb = e2
+        _need(es, "upconv_up9_forward")
+        _need(eb, "upconv_up9_forward")
+        if es.numel() < c_out or eb.numel() < c_out:
+            raise BtsHipError("upconv_up9_forward: e2 vectors need %d elements" % c_out)
+    kern, flops, nbytes, xflops = "conv", 0.0, 0.0, None
+    if _trace is not None:
+        cin = c_in_real if c_in_real is not None else c_in
+        n_ty, n_tx = (h // 2 + 1 + 3) // 4, (w // 2 + 1 + 7) // 8
+        kern = "conv_up9_kernel<32>"
+        flops = 2.0 * 36 * B * h * w * c_out * cin                                  # the reference's 3x3 on the upsampled map
+        nbytes = 4.0 * (B * h * w * cin + 4 * B * h * w * c_out + 9 * c_out * cin)
+        xflops = 2.0 * 9 * (B * n_ty * n_tx * 32) * (4 * c_out) * c_in              # what the kernel issues, ragged tiles included
+    tops = torch_ops()
+    if tops is not None:
+        run = lambda: _op(lambda: tops.upconv_up9(x2d, u, es, eb, y2d, [B, h, w, c_in, c_out, int(act)]))
+    else:
+        run = lambda: _lib.load().bts_upconv_up9_fwd_f32(_ptr(x2d), xs, B, h, w, c_in, _ptr(u), c_out, _ptr(es), _ptr(eb), int(act),
+                                                         _ptr(y2d), ys, _stream(x2d))
+    with torch.cuda.device(x2d.device):
+        rc = _launch(kern, tag, flops, nbytes, run, xflops=xflops)
+    _lib.check(rc, "bts_upconv_up9_fwd_f32")
+    return y2d
+
+
 def pad_vec(v: Optional[torch.Tensor], n: int, fill: float = 0.0) -> Optional[torch.Tensor]:
     if v is None:
         return None

@@ -37,6 +37,7 @@ _KINDS = {
     "bts_get_depth_f32": (9, "get_depth"),
     "bts_lpg_fwd_f32": (10, "lpg"),
     "bts_upconv_combine_f32": (11, "upconv_combine"),
+    "bts_upconv_up9_fwd_f32": (12, "upconv_up9"),
 }
 
 _structs: Dict[str, type] = {}
@@ -106,7 +107,7 @@ class _Proxy:
                                                   "bts_conv_wgrad_plan_f32", "bts_conv_wgrad_batch_table_bytes",
                                                   "bts_conv_wgrad_batch_plan_f32", "bts_eval_ws_doubles", "bts_bn_train_ws_floats", "bts_pack_weights_blocks",
                                                   "bts_depth_loss_ws_doubles", "bts_adamw_table_bytes", "bts_adamw_flat_span",
-                                                  "bts_adamw_plan_f32"):
+                                                  "bts_adamw_plan_f32", "bts_upconv_up9_plan"):
             return real
         if name not in _KINDS:
             def passthrough(*args):

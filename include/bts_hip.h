@@ -261,6 +261,27 @@ int bts_upconv_combine_f32(const float* taps, long taps_pix_stride, int B, int h
                            const float* e2_scale, const float* e2_shift, int act, float* y, long y_pix_stride,
                            bts_stream_t stream);
 
+/* The same upconv (nearest-2x + 3x3 conv + activation + affine) as ONE fused launch in shared-patch F(2x2,2x2) form
+ * (csrc/conv_up9.inc): the four parity classes of the sub-pixel statement share one transformed 3x3 source window, so
+ * the matrix pipe issues 9 products per source pixel, input and output channel instead of the sub-pixel halo kernel's
+ * 16.  Opt-in: bts_conv_fwd_f32 never takes this path on its own.
+ *   x: NHWC source map [B,h,w], x_pix_stride >= c_in floats per pixel (a multiple of 4), 16-byte aligned
+ *   u: U = G g_(py,px) G^T for the four classes in MFMA B-fragment order, 36 * c_in * c_out floats, 16-byte aligned:
+ *      float index ((((((xi * (c_in/32) + chunk) * (c_out/32) + ct) * 4 + cls) * 4 + g) * 64 + lh * 32 + li) * 4 + q
+ *      = U_cls[xi][n = 32 ct + li][k = 32 chunk + 8 g + 4 lh + q], cls = 2 py + px, xi = 3 a + b (bts_amd/ops.py:pack_upconv_up9)
+ *   y: NHWC [B,2h,2w], y_pix_stride >= c_out; act 0 none / 1 ReLU / 2 ELU; e2_* [c_out] or both NULL
+ * c_in % 32 == 0 and c_out % 32 == 0, else BTS_ERR_UNSUPPORTED.  Non-finite inputs spread over their 3x3 window (inf -> NaN). */
+int bts_upconv_up9_fwd_f32(const float* x, long x_pix_stride, int B, int h, int w, int c_in, const float* u, int c_out,
+                           const float* e2_scale, const float* e2_shift, int act, float* y, long y_pix_stride,
+                           bts_stream_t stream);
+
+/* Should a layer take bts_upconv_up9_fwd_f32 (host-side query, no GPU work, no pointers)?  Eligible: precision 0, whole
+ * 32-channel chunks both ways, a grid of 4x8-window workgroup tiles that is at least 0.70 real windows, and a declared
+ * launch (fill_frames as in bts_conv_desc, 0 = the library default; never B) of at least 2048 workgroups.
+ *   *bm = windows per workgroup (32), *bn = output channels per workgroup (32), *workgroups = workgroups PER FRAME;
+ *   all three 0 when the layer should stay on bts_conv_fwd_f32's sub-pixel path. */
+int bts_upconv_up9_plan(int h, int w, int c_in, int c_out, int precision, int fill_frames, int* bm, int* bn, long* workgroups);
+
 /* Which kernel bts_conv_fwd_f32 will launch for this descriptor (host-side query, no GPU work: it walks the real
  * dispatch path): lets a profiler attribute a launch to its kernel instantiation.
  *   *kind = one kernel family (kind & BTS_CONV_KIND_MASK) plus any of the BTS_CONV_FLAG_* bits. */
@@ -600,7 +621,7 @@ int  bts_adamw_step_f32(const void* table_dev, int n, long total_blocks, const b
  */
 enum { BTS_OP_CONV = 1, BTS_OP_REDUC = 2, BTS_OP_REDUC_LPG = 3, BTS_OP_LPG_FUSED = 4, BTS_OP_NCHW_TO_NHWC = 5,
        BTS_OP_NHWC_TO_NCHW = 6, BTS_OP_MAXPOOL = 7, BTS_OP_BN_RELU_AVGPOOL = 8, BTS_OP_GET_DEPTH = 9, BTS_OP_LPG = 10,
-       BTS_OP_UPCONV_COMBINE = 11 };
+       BTS_OP_UPCONV_COMBINE = 11, BTS_OP_UPCONV_UP9 = 12 };
 
 typedef struct bts_op {
     int kind;          /* BTS_OP_*                                                              */
@@ -624,6 +645,8 @@ typedef struct bts_op {
                  float* final_depth; } get_depth;
         struct { const float* taps; long taps_pix_stride; int B, h, w, c; const float* e2_scale; const float* e2_shift; int act;
                  float* y; long y_pix_stride; } upconv_combine;
+        struct { const float* x; long x_pix_stride; int B, h, w, c_in; const float* u; int c_out; const float* e2_scale;
+                 const float* e2_shift; int act; float* y; long y_pix_stride; } upconv_up9;
     } u;
 } bts_op;
 
