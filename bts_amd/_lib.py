@@ -24,6 +24,8 @@ SYMBOLS = (
     "bts_conv_wgrad_batch_table_bytes", "bts_conv_wgrad_batch_plan_f32", "bts_conv_wgrad_batch_f32",
     "bts_adamw_table_bytes", "bts_adamw_flat_span", "bts_adamw_plan_f32", "bts_adamw_step_f32",
     "bts_upconv_up9_fwd_f32", "bts_upconv_up9_plan",
+    "bts_upconv_dgrad_f32", "bts_upconv_dgrad_plan", "bts_upconv_wgrad_f32", "bts_upconv_wgrad_plan_f32",
+    "bts_upconv_train_pack_blocks", "bts_upconv_train_pack_f32",
 )
 
 ABI_VERSION = 17
@@ -222,6 +224,19 @@ def load_real():
     lib.bts_upconv_up9_fwd_f32.argtypes = [vp, l, i, i, i, i, vp, i, vp, vp, i, vp, l, vp]
     lib.bts_upconv_up9_plan.restype = i
     lib.bts_upconv_up9_plan.argtypes = [i, i, i, i, i, i, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_long)]
+    lib.bts_upconv_dgrad_f32.restype = i
+    lib.bts_upconv_dgrad_f32.argtypes = [vp, l, i, i, i, i, vp, i, vp, l, i, i, vp, l, vp]
+    lib.bts_upconv_dgrad_plan.restype = i
+    lib.bts_upconv_dgrad_plan.argtypes = [i, i, i, i, i, i, i, l, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    lib.bts_upconv_wgrad_f32.restype = i
+    lib.bts_upconv_wgrad_f32.argtypes = [vp, l, i, i, i, i, vp, l, i, vp, vp, l, vp]
+    lib.bts_upconv_wgrad_plan_f32.restype = i
+    lib.bts_upconv_wgrad_plan_f32.argtypes = [i, i, i, i, i, l, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_long),
+                                              C.POINTER(C.c_long)]
+    lib.bts_upconv_train_pack_blocks.restype = l
+    lib.bts_upconv_train_pack_blocks.argtypes = [l, l, l, l]
+    lib.bts_upconv_train_pack_f32.restype = i
+    lib.bts_upconv_train_pack_f32.argtypes = [vp, i, l, vp]
     lib.bts_eval_ws_doubles.restype = l
     lib.bts_eval_ws_doubles.argtypes = [i, i, i]
     lib.bts_eval_depth_metrics_f32.restype = i

@@ -390,6 +390,9 @@ class bts(nn.Module):
                                                         # chains the library does not build (bts_size 256) keep the layer graph
         self.batched_wgrad = False                      # train() mode, with fused_reduction_train: True computes the weight
                                                         # gradients of one scale's layers in one batched launch (ops.WgradBatch)
+        self.subpixel_upconv_train = False              # train() mode: True runs the ratio-2 upconvs in sub-pixel form in the
+                                                        # forward, input-gradient and weight-gradient passes (train._UpconvFn;
+                                                        # 16 products per source pixel instead of 36)
 
     # ------------------------------------------------------------------ weight packing (lazy)
     _OWN = ("bn5", "conv5", "bn4", "conv4", "bn4_2", "daspp_conv", "bn3", "conv3", "bn2", "conv2", "conv1", "get_depth")
@@ -680,6 +683,15 @@ class BtsModel(nn.Module):
     @fused_reduction_train.setter
     def fused_reduction_train(self, on: bool):
         self.decoder.fused_reduction_train = bool(on)
+
+    @property
+    def subpixel_upconv_train(self) -> bool:
+        """The decoder's switch of the same name (bts.subpixel_upconv_train), default False."""
+        return self.decoder.subpixel_upconv_train
+
+    @subpixel_upconv_train.setter
+    def subpixel_upconv_train(self, on: bool):
+        self.decoder.subpixel_upconv_train = bool(on)
 
     @property
     def batched_wgrad(self) -> bool:

@@ -947,19 +947,20 @@ void choose_tile(long M, int c_out, int* bm, int* bn) {
 }  // namespace
 
 namespace {
-int conv_dispatch(const bts_conv_desc* d, bts_stream_t stream);
+// even_ok: bts_upconv_dgrad_f32's own 4x4 / stride-2 gather; bts_conv_fwd_f32's accept set stays odd ksize
+int conv_dispatch(const bts_conv_desc* d, bts_stream_t stream, bool even_ok = false);
 }
 
 extern "C" int bts_conv_fwd_f32(const bts_conv_desc* d, bts_stream_t stream) { return conv_dispatch(d, stream); }
 
 namespace {
-int conv_dispatch(const bts_conv_desc* d, bts_stream_t stream) {
+int conv_dispatch(const bts_conv_desc* d, bts_stream_t stream, bool even_ok) {
     if (!d || !d->x || !d->w || !d->y) return BTS_ERR_INVALID;
     if (d->B <= 0 || d->h_in <= 0 || d->w_in <= 0 || d->c_out <= 0) return BTS_ERR_INVALID;
     if (d->up != 1 && d->up != 2) return BTS_ERR_UNSUPPORTED;
     if (d->subpixel) {   // 3x3 conv on a nearest-2x upsampled input, as four 2x2 convs on the source
         if (d->ksize != 2 || d->up != 1 || d->stride != 1 || d->dil != 1 || d->y_nchw) return BTS_ERR_INVALID;
-    } else if (d->ksize < 1 || d->ksize > 7 || !(d->ksize & 1)) return BTS_ERR_UNSUPPORTED;
+    } else if (d->ksize < 1 || d->ksize > 7 || (!(d->ksize & 1) && !even_ok)) return BTS_ERR_UNSUPPORTED;
     if (d->dil < 1 || d->stride < 1 || d->pad < 0) return BTS_ERR_INVALID;
     if (d->up == 2 && d->stride != 1) return BTS_ERR_UNSUPPORTED;
     if (d->c_in_ld <= 0 || (d->c_in_ld & 3) || (d->k_pad % BK) || d->k_pad < d->ksize * d->ksize * d->c_in_ld)
@@ -1206,4 +1207,57 @@ extern "C" int bts_upconv_up9_fwd_f32(const float* x, long x_pix_stride, int B, 
     a.ntiles = (int)nwg;
     hipLaunchKernelGGL(conv_up9_kernel<32>, dim3((unsigned)nwg), dim3(256), 0, (hipStream_t)stream, a);
     return (int)hipGetLastError();
+}
+
+// ---- input gradient of the sub-pixel upconv (training): one 4x4 / stride-2 / padding-1 convolution over dy at its natural
+//      [B,2h,2w,c_out] layout, dx[Y,X] = sum_{r,s} K[r,s] dy[2Y-1+r, 2X-1+s] -- 16 products per source pixel, no upsampled
+//      intermediate.  It runs on the row-tiled conv_fwd_kernel (the tap decode divides by a runtime ksize, the gather
+//      carries the stride, tap skipping is off for strided launches, and none of the geometry-chosen families accepts a
+//      stride-2 4x4), reached from this entry point's own descriptor; split-K and precision behave as in bts_conv_fwd_f32.
+namespace {
+int upconv_dgrad_desc(const float* dy, long dy_pix_stride, int B, int h, int w, int c_out, const float* w_dgrad, int c_in,
+                      float* dx, long dx_pix_stride, int precision, int fill_frames, float* splitk_ws, long splitk_ws_floats,
+                      bts_conv_desc& d) {
+    if (!dy || !w_dgrad || !dx) return BTS_ERR_INVALID;
+    if (B <= 0 || h <= 0 || w <= 0 || c_in <= 0 || c_out <= 0) return BTS_ERR_INVALID;
+    if ((c_in & 3) || (c_out & 3)) return BTS_ERR_INVALID;
+    if ((dy_pix_stride & 3) || dy_pix_stride < c_out || (dx_pix_stride & 3) || dx_pix_stride < c_in) return BTS_ERR_INVALID;
+    if (((uintptr_t)dy & 15) || ((uintptr_t)w_dgrad & 15) || ((uintptr_t)dx & 15)) return BTS_ERR_INVALID;
+    if ((splitk_ws == nullptr) != (splitk_ws_floats == 0) || splitk_ws_floats < 0 || ((uintptr_t)splitk_ws & 15)) return BTS_ERR_INVALID;
+    if ((double)h * 2.0 >= 1073741824.0 || (double)w * 2.0 >= 1073741824.0) return BTS_ERR_UNSUPPORTED;
+    d = bts_conv_desc{};
+    d.x = dy; d.x_pix_stride = dy_pix_stride; d.c_in_ld = c_out;
+    d.k_pad = (16 * c_out + BK - 1) / BK * BK;
+    d.B = B; d.h_in = 2 * h; d.w_in = 2 * w; d.up = 1;
+    d.ksize = 4; d.dil = 1; d.stride = 2; d.pad = 1;
+    d.w = w_dgrad; d.c_out = c_in; d.c_out_pad = (c_in + 31) / 32 * 32;
+    d.y = dx; d.y_pix_stride = dx_pix_stride;
+    d.splitk_ws = splitk_ws; d.splitk_ws_floats = splitk_ws_floats;
+    d.precision = precision; d.fill_frames = fill_frames;
+    return 0;
+}
+}  // namespace
+
+extern "C" int bts_upconv_dgrad_f32(const float* dy, long dy_pix_stride, int B, int h, int w, int c_out, const float* w_dgrad,
+                                    int c_in, float* dx, long dx_pix_stride, int precision, int fill_frames, float* splitk_ws,
+                                    long splitk_ws_floats, bts_stream_t stream) {
+    bts_conv_desc d;
+    if (const int rc = upconv_dgrad_desc(dy, dy_pix_stride, B, h, w, c_out, w_dgrad, c_in, dx, dx_pix_stride, precision, fill_frames,
+                                         splitk_ws, splitk_ws_floats, d); rc != 0) return rc;
+    return conv_dispatch(&d, stream, true);
+}
+
+extern "C" int bts_upconv_dgrad_plan(int B, int h, int w, int c_out, int c_in, int precision, int fill_frames, long splitk_ws_floats,
+                                     int* bm, int* bn, int* kind) {
+    if (!bm || !bn || !kind) return BTS_ERR_INVALID;
+    bts_conv_desc d;
+    float* dummy = (float*)(uintptr_t)(1 << 20);       // pointers are checked, never followed
+    if (const int rc = upconv_dgrad_desc(dummy, c_out, B, h, w, c_out, dummy, c_in, dummy, c_in, precision, fill_frames,
+                                         splitk_ws_floats > 0 ? dummy : nullptr, splitk_ws_floats, d); rc != 0) return rc;
+    ConvChoice c{BTS_CONV_KIND_ROW, 0, 0, 1};
+    g_dry = &c;
+    const int rc = conv_dispatch(&d, nullptr, true);
+    g_dry = nullptr;
+    *bm = c.bm; *bn = c.bn; *kind = c.kind | (c.ksplit > 1 ? BTS_CONV_FLAG_SPLITK : 0);
+    return rc;
 }

@@ -63,7 +63,12 @@ struct WgradArgs {
 // One workgroup = 4 waves arranged WM x WN over a BM x BN tile of dw; each wave owns (BM/WM) x (BN/WN).  The body is
 // shared by the single-problem launch (tile / split / bundle = blockIdx.x / .y / .z) and the batched launch (all three
 // derived from the workgroup's rank inside its problem).
-template <int BM, int BN, int WM, int WN>
+//
+// SUBPIX (bts_upconv_wgrad_f32): the sub-pixel upconv's class gradients.  `bundle` is then the parity class 2*py + px, the
+// K axis walks the B*h*w SOURCE pixels (a.H x a.W = a.Hs x a.Ws = the source map), the A operand of pixel (b, Y, X) is
+// dy at (b, 2Y+py, 2X+px) of the [B, 2h, 2w] gradient, and the 2x2 taps gather x at (Y-1+py+ty, X-1+px+tx); neither
+// operand is offset by the class, and the class results land in dense blocks [split][class][c_out][4*c_in] of a.out.
+template <int BM, int BN, int WM, int WN, bool SUBPIX = false>
 __device__ __forceinline__ void wgrad_tile(const WgradArgs& a, const unsigned tile, const unsigned split_idx,
                                            const unsigned bundle) {
     static_assert(WM * WN == 4, "4 waves");
@@ -83,8 +88,9 @@ __device__ __forceinline__ void wgrad_tile(const WgradArgs& a, const unsigned ti
     const int l31 = lane & 31, khalf = lane >> 5;
     const int tile_n = tile % a.n_ntiles, tile_m = tile / a.n_ntiles;
     const int m0 = tile_m * BM, n0 = tile_n * BN;
-    const float* __restrict__ xg = a.x + (size_t)bundle * a.c_in;      // this bundle's channel slice
-    const float* __restrict__ dyg = a.dy + (size_t)bundle * a.c_out;
+    const float* __restrict__ xg = a.x + (SUBPIX ? (size_t)0 : (size_t)bundle * a.c_in);      // this bundle's channel slice
+    const float* __restrict__ dyg = a.dy + (SUBPIX ? (size_t)0 : (size_t)bundle * a.c_out);
+    [[maybe_unused]] const int cpy = (int)(bundle >> 1), cpx = (int)(bundle & 1);             // SUBPIX: the class parities
 
     // ---- loader roles (fixed for the whole K walk) ----
     const int a_col = (tid % ACOLS) * 4, a_row = tid / ACOLS;
@@ -96,7 +102,7 @@ __device__ __forceinline__ void wgrad_tile(const WgradArgs& a, const unsigned ti
     const int nn = b_ok ? n4 : 0;
     const int tap = nn / a.c_in, ci = nn - tap * a.c_in;    // c_in % 4 == 0: a float4 never straddles a tap
     const int ky = tap / a.ksize, kx = tap - ky * a.ksize;
-    const int off_y = ky * a.dil - a.pad, off_x = kx * a.dil - a.pad;
+    const int off_y = SUBPIX ? ky - 1 + cpy : ky * a.dil - a.pad, off_x = SUBPIX ? kx - 1 + cpx : kx * a.dil - a.pad;
 
     const unsigned k_begin = split_idx * a.pix_per_split;
     const unsigned k_end = min(a.M, k_begin + a.pix_per_split);
@@ -109,7 +115,7 @@ __device__ __forceinline__ void wgrad_tile(const WgradArgs& a, const unsigned ti
     f32x4 psc = {1.f, 1.f, 1.f, 1.f}, psh = {0.f, 0.f, 0.f, 0.f};          // this thread's four input channels never change
     const bool has_pre = a.pre_scale != nullptr;
     if (has_pre) {
-        const int cpre = bundle * a.c_in + ci;
+        const int cpre = (SUBPIX ? 0 : (int)bundle * a.c_in) + ci;
         psc = *reinterpret_cast<const f32x4*>(a.pre_scale + cpre);
         psh = *reinterpret_cast<const f32x4*>(a.pre_shift + cpre);
     }
@@ -122,13 +128,31 @@ __device__ __forceinline__ void wgrad_tile(const WgradArgs& a, const unsigned ti
         py[p] = (int)(rem / (unsigned)a.W);
         px[p] = (int)(rem - (unsigned)py[p] * (unsigned)a.W);
     }
+    [[maybe_unused]] int qb[PA], qy[PA], qx[PA];   // SUBPIX: (frame, row, column) of each A row's source pixel at the next step
+    if constexpr (SUBPIX) {
+#pragma unroll
+        for (int p = 0; p < PA; ++p) {
+            const unsigned pix = k_begin + a_row + p * AROWS;
+            const unsigned b = pix / HW, rem = pix - b * HW;
+            qb[p] = (int)b;
+            qy[p] = (int)(rem / (unsigned)a.W);
+            qx[p] = (int)(rem - (unsigned)qy[p] * (unsigned)a.W);
+        }
+    }
     auto issue = [&](int it, f32x4 (&ra)[PA], f32x4 (&rb)[PB]) __attribute__((always_inline)) {
         const unsigned base = k_begin + (unsigned)it * WBK;
 #pragma unroll
         for (int p = 0; p < PA; ++p) {
             const unsigned pix = base + a_row + p * AROWS;
             const bool ok = a_ok && pix < k_end;
-            const float* src = dyg + (size_t)(ok ? pix : 0u) * a.dy_pix_stride + a_m;
+            size_t row = ok ? pix : 0u;
+            if constexpr (SUBPIX) {                                      // dy lives at (2Y+py, 2X+px) of the [B,2h,2w] map
+                row = ok ? ((size_t)qb[p] * (2 * a.H) + (size_t)(2 * qy[p] + cpy)) * (size_t)(2 * a.W) + (size_t)(2 * qx[p] + cpx) : 0;
+                qx[p] += WBK;
+                while (qx[p] >= a.W) { qx[p] -= a.W; ++qy[p]; }
+                while (qy[p] >= a.H) { qy[p] -= a.H; ++qb[p]; }
+            }
+            const float* src = dyg + row * a.dy_pix_stride + a_m;
             f32x4 v = *reinterpret_cast<const f32x4*>(src);
             ra[p] = ok ? v : (f32x4)(0.f);
         }
@@ -858,5 +882,221 @@ extern "C" int bts_pack_weights_f32(const void* table, int n_entries, long total
     if (!table || n_entries <= 0 || total_blocks <= 0 || total_blocks > 2147483647L) return BTS_ERR_INVALID;
     hipLaunchKernelGGL(pack_weights_kernel, dim3((unsigned)total_blocks), dim3(256), 0, (hipStream_t)stream,
                        (const PackEntry*)table, n_entries);
+    return (int)hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Sub-pixel upconv in the training step (bts_upconv_wgrad_f32, bts_upconv_train_pack_f32; include/bts_hip.h).
+//
+// Weight gradient: per parity class (py, px) the 2x2 class filter's gradient is a [c_out] x [4*c_in] GEMM over the B*h*w
+// source pixels -- wgrad_tile<SUBPIX> with the class as gridDim.z -- written as [split][class][c_out][4*c_in] into the
+// caller's workspace (split >= 1: the class results need a home even unsplit).  upconv_wgrad_fold_kernel then produces
+// dw[co][3*ky+kx][ci] in a FIXED order:
+//   1. per class cls = 0..3, the split partials of element (co, tau_py(ky)*2 + tau_px(kx), ci) exactly as
+//      wgrad_reduce_kernel sums them (lane j adds splits j, j+16, ..., four at a time as (a0+a1)+(a2+a3); then the 16
+//      lane sums are added in lane order) -> r_cls;
+//   2. dw = ((r_0 + r_1) + r_2) + r_3.
+// tau_0 = (0,1,1), tau_1 = (0,0,1): the adjoint of the pre-sum in pack_upconv_subpixel.  No atomics; bit-reproducible.
+namespace {
+
+template <int BM, int BN, int WM, int WN>
+__global__ __launch_bounds__(256, 2) void upconv_wgrad_kernel(const WgradArgs a) {
+    wgrad_tile<BM, BN, WM, WN, true>(a, blockIdx.x, blockIdx.y, blockIdx.z);
+}
+
+__global__ __launch_bounds__(256) void upconv_wgrad_fold_kernel(const float* __restrict__ ws, float* __restrict__ dw, int c_out,
+                                                                int c_in, int ksplit) {
+    const long count4 = (long)c_out * 9 * c_in / 4;
+    const long per = (long)c_out * 4 * c_in;               // floats of one class block
+    const int el = threadIdx.x & 15, lane = threadIdx.x >> 4;
+    const long t = (long)blockIdx.x * 16 + el;
+    const long tt = t < count4 ? t : count4 - 1;
+    const long idx = tt * 4;
+    const int co = (int)(idx / (9L * c_in));
+    const int rem = (int)(idx - (long)co * 9 * c_in);
+    const int tap = rem / c_in, ci = rem - tap * c_in;
+    const int ky = tap / 3, kx = tap - 3 * ky;
+    __shared__ f32x4 red[4][16][16];
+#pragma unroll
+    for (int cls = 0; cls < 4; ++cls) {
+        const int py = cls >> 1, px = cls & 1;
+        const int ty = py == 0 ? (ky >= 1) : (ky >= 2), tx = px == 0 ? (kx >= 1) : (kx >= 2);
+        const float* p = ws + (long)cls * per + ((long)co * 4 + (ty * 2 + tx)) * c_in + ci;
+        const size_t step = (size_t)4 * per;               // one split = four class blocks
+        f32x4 v = (f32x4)(0.f);
+        int s = lane;
+        for (; s + 48 < ksplit; s += 64) {
+            const f32x4 a0 = *reinterpret_cast<const f32x4*>(p + (size_t)s * step), a1 = *reinterpret_cast<const f32x4*>(p + (size_t)(s + 16) * step);
+            const f32x4 a2 = *reinterpret_cast<const f32x4*>(p + (size_t)(s + 32) * step), a3 = *reinterpret_cast<const f32x4*>(p + (size_t)(s + 48) * step);
+            v += (a0 + a1) + (a2 + a3);
+        }
+        for (; s < ksplit; s += 16) v += *reinterpret_cast<const f32x4*>(p + (size_t)s * step);
+        red[cls][lane][el] = v;
+    }
+    __syncthreads();
+    if (lane == 0 && t < count4) {
+        f32x4 r[4];
+#pragma unroll
+        for (int cls = 0; cls < 4; ++cls) {
+            r[cls] = red[cls][0][el];
+#pragma unroll
+            for (int j = 1; j < 16; ++j) r[cls] += red[cls][j][el];
+        }
+        reinterpret_cast<f32x4*>(dw)[t] = ((r[0] + r[1]) + r[2]) + r[3];
+    }
+}
+
+template <int BM, int BN, int WM, int WN>
+int launch_upconv_wgrad(WgradArgs a, long split, float* dw, float* ws, hipStream_t s) {
+    const int m_tiles = (a.c_out + BM - 1) / BM;
+    a.n_ntiles = (a.N + BN - 1) / BN;
+    const long tiles = (long)m_tiles * a.n_ntiles;
+    a.out = ws;
+    const size_t lds_bytes = (size_t)2 * WBK * (BM + BN) * sizeof(float);
+    auto kern = upconv_wgrad_kernel<BM, BN, WM, WN>;
+    static std::atomic<unsigned long long> lds_set{0};     // per instantiation: one bit per device (common.h)
+    if (hipError_t e = bts_ensure_dynamic_lds((const void*)kern, lds_bytes, lds_set); e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(kern, dim3((unsigned)tiles, (unsigned)split, 4u), dim3(256), lds_bytes, s, a);
+    const long count4 = (long)a.c_out * 9 * a.c_in / 4;
+    hipLaunchKernelGGL(upconv_wgrad_fold_kernel, dim3((unsigned)((count4 + 15) / 16)), dim3(256), 0, s, (const float*)ws, dw,
+                       a.c_out, a.c_in, (int)split);
+    return (int)hipGetLastError();
+}
+
+// Host side of bts_upconv_wgrad_f32, shared with its plan query: validation, kernel arguments, plan_wgrad's tile and
+// split for M = B*h*w source pixels, N = 4*c_in, four "bundles" (the classes).  Returns 0 or a BTS_ERR_* code.
+int prepare_upconv_wgrad(const float* x, long x_pix_stride, int B, int h, int w, int c_in, const float* dy, long dy_pix_stride,
+                         int c_out, const float* dw, const float* ws, long ws_floats, WgradArgs& a, WgradPlan& p) {
+    if (!x || !dy || !dw || !ws) return BTS_ERR_INVALID;
+    if (B <= 0 || h <= 0 || w <= 0 || c_in <= 0 || c_out <= 0) return BTS_ERR_INVALID;
+    if ((c_in & 3) || (c_out & 3)) return BTS_ERR_INVALID;
+    if ((x_pix_stride & 3) || x_pix_stride < c_in || (dy_pix_stride & 3) || dy_pix_stride < c_out) return BTS_ERR_INVALID;
+    if (((uintptr_t)x & 15) || ((uintptr_t)dy & 15) || ((uintptr_t)dw & 15) || ((uintptr_t)ws & 15) || ws_floats < 0) return BTS_ERR_INVALID;
+    const double mpix = (double)B * h * w;
+    if (4.0 * mpix >= 2147483648.0 || (double)h * w >= 1073741824.0) return BTS_ERR_UNSUPPORTED;   // 32-bit pixel decode, 2h x 2w rows
+    if (36.0 * c_in * (double)c_out >= 2147483648.0) return BTS_ERR_UNSUPPORTED;
+    a.x = x; a.dy = dy; a.out = nullptr;
+    a.x_pix_stride = x_pix_stride; a.dy_pix_stride = dy_pix_stride;
+    a.c_in = c_in; a.c_out = c_out; a.N = 4 * c_in;
+    a.B = B; a.h_in = h; a.w_in = w; a.Hs = h; a.Ws = w; a.ups = 0; a.H = h; a.W = w;
+    a.ksize = 2; a.dil = 1; a.stride = 1; a.pad = 0;
+    a.M = (unsigned)mpix;
+    a.pix_per_split = 0; a.n_ntiles = 0;
+    a.pre_scale = nullptr; a.pre_shift = nullptr; a.pre_relu = 0;
+    a.n_bundles = 4;
+    const long per = 16L * c_out * c_in;                   // floats of the four class blocks of one split
+    if (ws_floats < per) return BTS_ERR_INVALID;
+    p = plan_wgrad(c_out, a.N, (long)a.M, ws_floats, true, 4);
+    const long pps = (((long)a.M + p.split - 1) / p.split + WBK - 1) / WBK * WBK;
+    p.split = ((long)a.M + pps - 1) / pps;                 // no empty splits
+    a.pix_per_split = (unsigned)pps;
+    if (p.split * per > ws_floats) return BTS_ERR_INVALID;
+    return 0;
+}
+
+// ---- per-step packs of the upconv weights (bts_upconv_train_pack_f32) ----
+struct UpconvPackEntry {    // 12 x int64, filled by the host (bts_amd/train.py)
+    const float* src;       // OIHW [c_out][c_in][3][3]
+    float* fwd;             // [4][c_out_pad][k_pad_f], k = (2*ty+tx)*c_in_ld + c   (ops.pack_upconv_subpixel)
+    float* dgrad;           // [c_in_pad][k_pad_d], k = (4*r+s)*c_out_ld + n         (bts_upconv_dgrad_f32)
+    long c_out, c_in, c_in_ld, c_out_ld, c_out_pad, k_pad_f, c_in_pad, k_pad_d;
+    long first_block;       // prefix sum of blocks over the table
+};
+
+// g_(py,px)[ty][tx] of one (output, input) channel pair: the 3x3 taps the class tap covers, added in fp32 in the order
+// ky outer, kx inner (pack_upconv_subpixel's order); w9 = the pair's nine taps.  Additions only: nothing to contract.
+__device__ __forceinline__ float subpix_class_tap(const float* __restrict__ w9, int py, int ty, int px, int tx) {
+    const int ky0 = ty == 0 ? 0 : (py == 0 ? 1 : 2), nky = py != ty ? 2 : 1;     // (0,0):{0} (0,1):{1,2} (1,0):{0,1} (1,1):{2}
+    const int kx0 = tx == 0 ? 0 : (px == 0 ? 1 : 2), nkx = px != tx ? 2 : 1;
+    float acc = w9[ky0 * 3 + kx0];
+    if (nkx == 2) acc = __fadd_rn(acc, w9[ky0 * 3 + kx0 + 1]);
+    if (nky == 2) {
+        acc = __fadd_rn(acc, w9[(ky0 + 1) * 3 + kx0]);
+        if (nkx == 2) acc = __fadd_rn(acc, w9[(ky0 + 1) * 3 + kx0 + 1]);
+    }
+    return acc;
+}
+
+__global__ __launch_bounds__(256) void upconv_train_pack_kernel(const UpconvPackEntry* __restrict__ table, int n) {
+    int lo = 0, hi = n - 1;                       // the entry whose block range holds blockIdx.x
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (table[mid].first_block <= (long)blockIdx.x) lo = mid; else hi = mid - 1;
+    }
+    const UpconvPackEntry e = table[lo];
+    const long n_fwd = 4 * e.c_out_pad * e.k_pad_f, total = n_fwd + e.c_in_pad * e.k_pad_d;     // both multiples of 4
+    const long base = ((long)blockIdx.x - e.first_block) * PACK_PER_BLOCK;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const long i0 = base + ((long)u * 256 + threadIdx.x) * 4;
+        if (i0 >= total) continue;
+        f32x4 v = (f32x4)(0.f);
+        if (i0 < n_fwd) {
+            const long cls = i0 / (e.c_out_pad * e.k_pad_f), r0 = i0 - cls * e.c_out_pad * e.k_pad_f;
+            const long row = r0 / e.k_pad_f, col0 = r0 - row * e.k_pad_f;
+            if (row < e.c_out) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const long col = col0 + j, tap = col / e.c_in_ld, c = col - tap * e.c_in_ld;
+                    if (tap < 4 && c < e.c_in)
+                        v[j] = subpix_class_tap(e.src + (row * e.c_in + c) * 9, (int)(cls >> 1), (int)(tap >> 1), (int)(cls & 1), (int)(tap & 1));
+                }
+            }
+            *reinterpret_cast<f32x4*>(e.fwd + i0) = v;
+        } else {
+            const long i1 = i0 - n_fwd;
+            const long row = i1 / e.k_pad_d, col0 = i1 - row * e.k_pad_d;      // row = input channel
+            if (row < e.c_in) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const long col = col0 + j, rs = col / e.c_out_ld, nn = col - rs * e.c_out_ld;
+                    if (rs < 16 && nn < e.c_out) {
+                        const int r = (int)(rs >> 2), sx = (int)(rs & 3);      // K[r][s]: 3 - r = py + 2 ty, 3 - s = px + 2 tx
+                        v[j] = subpix_class_tap(e.src + (nn * e.c_in + row) * 9, (3 - r) & 1, (3 - r) >> 1, (3 - sx) & 1, (3 - sx) >> 1);
+                    }
+                }
+            }
+            *reinterpret_cast<f32x4*>(e.dgrad + i1) = v;
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int bts_upconv_wgrad_f32(const float* x, long x_pix_stride, int B, int h, int w, int c_in, const float* dy,
+                                    long dy_pix_stride, int c_out, float* dw, float* ws, long ws_floats, bts_stream_t stream) {
+    WgradArgs a;
+    WgradPlan p;
+    if (const int rc = prepare_upconv_wgrad(x, x_pix_stride, B, h, w, c_in, dy, dy_pix_stride, c_out, dw, ws, ws_floats, a, p); rc != 0) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    switch (p.variant) {
+        case 0: return launch_upconv_wgrad<128, 128, 2, 2>(a, p.split, dw, ws, s);
+        case 1: return launch_upconv_wgrad<64, 128, 1, 4>(a, p.split, dw, ws, s);
+        case 2: return launch_upconv_wgrad<32, 128, 1, 4>(a, p.split, dw, ws, s);
+        default: return launch_upconv_wgrad<64, 64, 2, 2>(a, p.split, dw, ws, s);
+    }
+}
+
+extern "C" int bts_upconv_wgrad_plan_f32(int B, int h, int w, int c_in, int c_out, long ws_floats, int* bm, int* bn, long* split,
+                                         long* pix_per_split) {
+    WgradArgs a;
+    WgradPlan p;
+    const float* dummy = (const float*)(uintptr_t)(1 << 20);      // pointers are checked, never followed
+    if (const int rc = prepare_upconv_wgrad(dummy, c_in, B, h, w, c_in, dummy, c_out, c_out, dummy, dummy, ws_floats, a, p); rc != 0) return rc;
+    if (bm) *bm = WGRAD_BM[p.variant];
+    if (bn) *bn = WGRAD_BN[p.variant];
+    if (split) *split = p.split;
+    if (pix_per_split) *pix_per_split = (long)a.pix_per_split;
+    return 0;
+}
+
+extern "C" long bts_upconv_train_pack_blocks(long c_out_pad, long k_pad_f, long c_in_pad, long k_pad_d) {
+    return (4 * c_out_pad * k_pad_f + c_in_pad * k_pad_d + PACK_PER_BLOCK - 1) / PACK_PER_BLOCK;
+}
+
+extern "C" int bts_upconv_train_pack_f32(const void* table, int n_entries, long total_blocks, bts_stream_t stream) {
+    if (!table || ((uintptr_t)table & 7) || n_entries <= 0 || total_blocks <= 0 || total_blocks > 2147483647L) return BTS_ERR_INVALID;
+    hipLaunchKernelGGL(upconv_train_pack_kernel, dim3((unsigned)total_blocks), dim3(256), 0, (hipStream_t)stream,
+                       (const UpconvPackEntry*)table, n_entries);
     return (int)hipGetLastError();
 }

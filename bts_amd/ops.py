@@ -1538,6 +1538,182 @@ def conv_wgrad(x2d: torch.Tensor, B: int, h_in: int, w_in: int, c_in: int, dy2d:
     return dw
 
 
+# ---- sub-pixel upconv in the training step (bts_upconv_dgrad_f32 / bts_upconv_wgrad_f32 / bts_upconv_train_pack_f32)
+_SUBPIX_S = {0: ((1.0, 0.0, 0.0), (0.0, 1.0, 1.0)), 1: ((1.0, 1.0, 0.0), (0.0, 0.0, 1.0))}   # row sums of _SUBPIX_SETS
+_SUBPIX_TAU = {0: (0, 1, 1), 1: (0, 0, 1)}                                                   # 3x3 tap -> class tap (the adjoint)
+
+
+def upconv_subpixel_grads_reference(x: torch.Tensor, w: torch.Tensor, dy: torch.Tensor):
+    """The sub-pixel statement of upconv = conv3x3(nearest2x(x), w, padding 1) and of its two gradients, in fp64 on the
+    CPU -- the oracle of the training kernels (include/bts_hip.h states the same three identities).  x [B,c_in,h,w],
+    w [c_out,c_in,3,3], dy [B,c_out,2h,2w] -> (y [B,c_out,2h,2w], dx like x, dw like w)."""
+    x, w, dy = x.detach().double().cpu(), w.detach().double().cpu(), dy.detach().double().cpu()
+    B, cin, h, wd = x.shape
+    cout = w.shape[0]
+    S = {p: torch.tensor(_SUBPIX_S[p], dtype=torch.float64) for p in (0, 1)}
+    g = {(py, px): torch.einsum("ta,ncab,ub->nctu", S[py], w, S[px]) for py in (0, 1) for px in (0, 1)}   # [c_out,c_in,2,2]
+    xp = F.pad(x, (1, 1, 1, 1))                       # x[Y-1+py+ty, X-1+px+tx] = xp[Y+py+ty, X+px+tx]
+    dyp = F.pad(dy, (1, 1, 1, 1))                     # dy[2Y-1+r, 2X-1+s] = dyp[2Y+r, 2X+s]
+    y = torch.zeros((B, cout, 2 * h, 2 * wd), dtype=torch.float64)
+    dx = torch.zeros_like(x)
+    dw = torch.zeros_like(w)
+    for (py, px), gc in g.items():
+        for ty in (0, 1):
+            for tx in (0, 1):
+                xs = xp[:, :, py + ty:py + ty + h, px + tx:px + tx + wd]
+                y[:, :, py::2, px::2] += torch.einsum("nc,bchw->bnhw", gc[:, :, ty, tx], xs)
+                r, s = 3 - py - 2 * ty, 3 - px - 2 * tx                                  # K[r,s] = g_(py,px)[ty,tx]^T
+                dx += torch.einsum("nc,bnhw->bchw", gc[:, :, ty, tx], dyp[:, :, r:r + 2 * h:2, s:s + 2 * wd:2])
+                dg = torch.einsum("bnhw,bchw->nc", dy[:, :, py::2, px::2], xs)
+                for ky in range(3):
+                    for kx in range(3):
+                        if _SUBPIX_TAU[py][ky] == ty and _SUBPIX_TAU[px][kx] == tx:
+                            dw[:, :, ky, kx] += dg
+    return y, dx, dw
+
+
+def pack_upconv_dgrad_reference(w: torch.Tensor) -> torch.Tensor:
+    """Torch statement of the input-gradient pack bts_upconv_train_pack_f32 writes: [round_up(c_in,32)][round_up(16*c_out,32)]
+    with element [c][(4r+s)*c_out + n] = K[r,s][c][n], K[3-py-2ty, 3-px-2tx] = g_(py,px)[ty,tx]^T -- each the fp32 sum
+    pack_upconv_subpixel computes for its forward twin (c_in and c_out multiples of 4)."""
+    cout, cin = w.shape[0], w.shape[1]
+    fwd, cop, cld = pack_upconv_subpixel(w, c_in_ld=cin)
+    out = torch.zeros((round_up(cin, 32), round_up(16 * cout, 32)), dtype=torch.float32, device=w.device)
+    for py in (0, 1):
+        for px in (0, 1):
+            for ty in (0, 1):
+                for tx in (0, 1):
+                    rs = 4 * (3 - py - 2 * ty) + (3 - px - 2 * tx)
+                    t = 2 * ty + tx
+                    out[:cin, rs * cout:(rs + 1) * cout] = fwd[2 * py + px, :cout, t * cld:t * cld + cin].t()
+    return out
+
+
+def upconv_train_pack_shapes(c_out: int, c_in: int) -> Tuple[Tuple[int, int, int], Tuple[int, int]]:
+    """Shapes of the two packs of one upconv weight: forward [4, c_out_pad, k_pad] (pack_upconv_subpixel with
+    c_in_ld = c_in) and input gradient [c_in_pad, k_pad'] (pack_upconv_dgrad_reference)."""
+    return (4, round_up(c_out, 32), round_up(4 * c_in, 32)), (round_up(c_in, 32), round_up(16 * c_out, 32))
+
+
+def upconv_train_pack(weights: Sequence[torch.Tensor], fwd: Sequence[torch.Tensor], dgrad: Sequence[torch.Tensor],
+                      table: Optional[Tuple[torch.Tensor, int]] = None) -> Tuple[torch.Tensor, int]:
+    """Both training packs of every upconv weight (contiguous OIHW [c_out,c_in,3,3] fp32, channel counts multiples of 4) in
+    ONE launch of bts_upconv_train_pack_f32 into the caller's ``fwd`` / ``dgrad`` buffers (upconv_train_pack_shapes).
+    Returns the (device table, blocks) it launched with; pass it back as ``table`` to launch again without an upload --
+    the table holds addresses, so only for the same tensors."""
+    import numpy as np
+    if not weights:
+        raise BtsHipError("upconv_train_pack: no weights")
+    lib = _lib.load()
+    dev = weights[0].device
+    if table is None:
+        rows, first = [], 0
+        for wt, f, d in zip(weights, fwd, dgrad):
+            for t in (wt, f, d):
+                _need(t, "upconv_train_pack")
+            cout, cin, kh, kw = wt.shape
+            fs, ds = upconv_train_pack_shapes(cout, cin)
+            if (kh, kw) != (3, 3) or cout % 4 or cin % 4 or not wt.is_contiguous() or tuple(f.shape) != fs or tuple(d.shape) != ds \
+                    or not f.is_contiguous() or not d.is_contiguous():
+                raise BtsHipError("upconv_train_pack: weight %s / packs %s, %s do not fit" % (tuple(wt.shape), tuple(f.shape), tuple(d.shape)))
+            rows.append([wt.data_ptr(), f.data_ptr(), d.data_ptr(), cout, cin, cin, cout, fs[1], fs[2], ds[0], ds[1], first])
+            first += int(lib.bts_upconv_train_pack_blocks(fs[1], fs[2], ds[0], ds[1]))
+        table = (torch.from_numpy(np.asarray(rows, dtype=np.int64)).to(dev), first)
+    tab, blocks = table
+    with torch.cuda.device(dev):
+        rc = _launch("upconv_train_pack_kernel", "pack", 0.0, 0.0,
+                     lambda: lib.bts_upconv_train_pack_f32(tab.data_ptr(), tab.shape[0], blocks, _stream(weights[0])))
+    _lib.check(rc, "bts_upconv_train_pack_f32")
+    return table
+
+
+def upconv_dgrad_plan(B: int, h: int, w: int, c_out: int, c_in: int, splitk_ws_floats: int = 0, precision=None,
+                      fill_frames: Optional[int] = None) -> Tuple[int, int, int, bool]:
+    """Which kernel upconv_dgrad will launch: (bm, bn, kind, splits K).  Host-only (bts_upconv_dgrad_plan)."""
+    ff, pr = current_launch_config()
+    if precision is not None:
+        pr = _PRECISIONS[precision]
+    if fill_frames is not None:
+        ff = int(fill_frames)
+    bm, bn, kind = C.c_int(0), C.c_int(0), C.c_int(0)
+    _lib.check(_lib.load().bts_upconv_dgrad_plan(B, h, w, c_out, c_in, int(pr), int(ff), int(splitk_ws_floats), C.byref(bm), C.byref(bn),
+                                                 C.byref(kind)), "bts_upconv_dgrad_plan")
+    return bm.value, bn.value, kind.value & 15, bool(kind.value & 16)
+
+
+def upconv_dgrad(dy2d: torch.Tensor, B: int, h: int, w: int, w_dgrad: torch.Tensor, c_out: int, c_in: int, dx2d: torch.Tensor,
+                 splitk_ws: Optional[torch.Tensor] = None, tag: str = "upconv.dgrad") -> torch.Tensor:
+    """Input gradient of the sub-pixel upconv (bts_upconv_dgrad_f32): dy2d [B*2h*2w, >= c_out] NHWC view -> dx2d
+    [B*h*w, c_in] NHWC view (channel slices of wider buffers are fine), one 4x4 / stride-2 convolution with ``w_dgrad``
+    from upconv_train_pack.  fp32 or bf16x3 by the launch_config in force; ``splitk_ws`` lets small maps split K."""
+    ds, dc = _rows2d(dy2d, "upconv_dgrad")
+    xs, xc = _rows2d(dx2d, "upconv_dgrad")
+    _need(w_dgrad, "upconv_dgrad")
+    if c_in % 4 or c_out % 4 or dc < c_out or xc != c_in or dy2d.shape[0] != 4 * B * h * w or dx2d.shape[0] != B * h * w:
+        raise BtsHipError("upconv_dgrad: views %s / %s do not fit B=%d %dx%d, %d <- %d channels (multiples of 4)"
+                          % (tuple(dy2d.shape), tuple(dx2d.shape), B, h, w, c_in, c_out))
+    if tuple(w_dgrad.shape) != upconv_train_pack_shapes(c_out, c_in)[1] or not w_dgrad.is_contiguous():
+        raise BtsHipError("upconv_dgrad: w_dgrad must be the input-gradient pack of upconv_train_pack")
+    ff, pr = current_launch_config()
+    if pr == 2:
+        raise BtsHipError("upconv_dgrad: conv_precision 'bf16' is an inference mode")
+    ws_ptr, ws_n = None, 0
+    if splitk_ws is not None:
+        _need(splitk_ws, "upconv_dgrad")
+        if not splitk_ws.is_contiguous():
+            raise BtsHipError("upconv_dgrad: splitk_ws must be contiguous")
+        ws_ptr, ws_n = splitk_ws.data_ptr(), splitk_ws.numel()
+    kern = "conv"
+    if _trace is not None:
+        bm, bn, _, sk = upconv_dgrad_plan(B, h, w, c_out, c_in, ws_n)
+        kern = "conv_fwd_kernel<%d,%d,k4s2>%s" % (bm, bn, "+splitk" if sk else "")
+    flops = 2.0 * 36 * B * h * w * c_out * c_in               # the reference's 3x3 adjoint on the upsampled map
+    nbytes = 4.0 * (4 * B * h * w * c_out + B * h * w * c_in + 16 * c_out * c_in)
+    with torch.cuda.device(dy2d.device):
+        rc = _launch(kern, tag, flops, nbytes,
+                     lambda: _lib.load().bts_upconv_dgrad_f32(_ptr(dy2d), ds, B, h, w, c_out, _ptr(w_dgrad), c_in, _ptr(dx2d), xs, int(pr),
+                                                              int(ff), ws_ptr, ws_n, _stream(dy2d)),
+                     xflops=2.0 * 16 * B * h * w * c_out * c_in)
+    _lib.check(rc, "bts_upconv_dgrad_f32")
+    return dx2d
+
+
+def upconv_wgrad_plan(B: int, h: int, w: int, c_in: int, c_out: int, ws_floats: int) -> Tuple[int, int, int, int]:
+    """Tile and pixel split upconv_wgrad will run under a workspace of ``ws_floats`` floats: (bm, bn, split,
+    pix_per_split); the launch writes split * 16 * c_out * c_in floats of it.  Host-only (bts_upconv_wgrad_plan_f32)."""
+    bm, bn, split, pps = C.c_int(0), C.c_int(0), C.c_long(0), C.c_long(0)
+    _lib.check(_lib.load().bts_upconv_wgrad_plan_f32(B, h, w, c_in, c_out, int(ws_floats), C.byref(bm), C.byref(bn), C.byref(split),
+                                                     C.byref(pps)), "bts_upconv_wgrad_plan_f32")
+    return bm.value, bn.value, split.value, pps.value
+
+
+def upconv_wgrad(x2d: torch.Tensor, B: int, h: int, w: int, c_in: int, dy2d: torch.Tensor, c_out: int, ws: torch.Tensor,
+                 tag: str = "upconv.wgrad") -> torch.Tensor:
+    """Weight gradient of the sub-pixel upconv (bts_upconv_wgrad_f32): x2d [B*h*w, >= c_in], dy2d [B*2h*2w, >= c_out] NHWC
+    views -> dw [c_out, 9, c_in] (OHWI, as conv_wgrad).  ``ws`` is mandatory (>= 16 * c_out * c_in floats): the sixteen
+    class GEMMs land there, split over pixels as conv_wgrad's planner decides, and a fixed-order launch folds them."""
+    xs, xc = _rows2d(x2d, "upconv_wgrad")
+    ds, dc = _rows2d(dy2d, "upconv_wgrad")
+    if ws is None:
+        raise BtsHipError("upconv_wgrad: the workspace is mandatory")
+    _need(ws, "upconv_wgrad")
+    if c_in % 4 or c_out % 4 or c_in > xc or c_out > dc or x2d.shape[0] != B * h * w or dy2d.shape[0] != 4 * B * h * w:
+        raise BtsHipError("upconv_wgrad: views %s / %s do not fit B=%d %dx%d, %d -> %d channels (multiples of 4)"
+                          % (tuple(x2d.shape), tuple(dy2d.shape), B, h, w, c_in, c_out))
+    if not ws.is_contiguous() or ws.numel() < 16 * c_out * c_in:
+        raise BtsHipError("upconv_wgrad: the workspace must be contiguous and hold at least %d floats" % (16 * c_out * c_in))
+    dw = torch.empty((c_out, 9, c_in), dtype=torch.float32, device=x2d.device)
+    flops = 2.0 * 36 * B * h * w * c_out * c_in
+    nbytes = 4.0 * (B * h * w * c_in + 4 * B * h * w * c_out + 9 * c_out * c_in)
+    with torch.cuda.device(x2d.device):
+        rc = _launch("upconv_wgrad_kernel", tag, flops, nbytes,
+                     lambda: _lib.load().bts_upconv_wgrad_f32(_ptr(x2d), xs, B, h, w, c_in, _ptr(dy2d), ds, c_out, _ptr(dw), _ptr(ws),
+                                                              ws.numel(), _stream(x2d)),
+                     xflops=2.0 * 16 * B * h * w * c_out * c_in)
+    _lib.check(rc, "bts_upconv_wgrad_f32")
+    return dw
+
+
 # ---- many weight gradients in one launch (bts_conv_wgrad_batch_*, include/bts_hip.h)
 def conv_wgrad_batch_plan_descs(descs: Sequence[ConvWgradDesc], bases: Sequence[Tuple[int, int]], ws_floats: int,
                                 with_table: bool = False):

@@ -107,7 +107,8 @@ class _Proxy:
                                                   "bts_conv_wgrad_plan_f32", "bts_conv_wgrad_batch_table_bytes",
                                                   "bts_conv_wgrad_batch_plan_f32", "bts_eval_ws_doubles", "bts_bn_train_ws_floats", "bts_pack_weights_blocks",
                                                   "bts_depth_loss_ws_doubles", "bts_adamw_table_bytes", "bts_adamw_flat_span",
-                                                  "bts_adamw_plan_f32", "bts_upconv_up9_plan"):
+                                                  "bts_adamw_plan_f32", "bts_upconv_up9_plan", "bts_upconv_dgrad_plan",
+                                                  "bts_upconv_wgrad_plan_f32", "bts_upconv_train_pack_blocks"):
             return real
         if name not in _KINDS:
             def passthrough(*args):

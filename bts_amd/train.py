@@ -186,6 +186,81 @@ class WeightPacker:
 _PACKER = WeightPacker()
 
 
+class UpconvPacker:
+    """The two per-step packs of every upconv weight on the sub-pixel training path (decoder.subpixel_upconv_train):
+    the four pre-summed 2x2 class filters the forward reads (ops.pack_upconv_subpixel's layout and bits) and the 4x4 /
+    stride-2 kernel of the input gradient (ops.pack_upconv_dgrad_reference).  Weights are registered on first use and
+    packed on the spot.  Every ``begin_step()`` ages the whole set (``invalidate()``), and the first upconv of the step
+    then re-packs ALL registered weights from the OIHW parameters in ONE launch of bts_upconv_train_pack_f32
+    (``refresh()``), whatever ``Tensor._version`` or ``WeightPacker.versions_trusted`` say: the packs are current after
+    torch's fused optimisers and after ``optim.NativeAdamW`` alike, and a step that runs no sub-pixel upconv (the switch
+    off) launches nothing.  Every refill bumps ``_bts_pack_seq`` on the buffers, so the forms ops.conv_forward derives
+    from them (the bf16x3 planes) are re-made."""
+
+    def __init__(self):
+        self.entries = {}          # (data_ptr, shape) -> dict(wref, ptr, fwd, dgrad, version)
+        self._table = None
+        self._table_key = None
+        self._aged = False
+
+    def invalidate(self):
+        """A new step began: nothing packed before it may be used again."""
+        self._aged = True
+
+    @staticmethod
+    def _stamp(items):
+        for e in items:
+            e["version"] = e["wref"]()._version
+            for buf in (e["fwd"], e["dgrad"]):
+                buf._bts_pack_seq = getattr(buf, "_bts_pack_seq", 0) + 1
+
+    def get(self, weight):
+        """(forward pack [4, c_out_pad, k_pad], input-gradient pack [c_in_pad, k_pad']) of ``weight``."""
+        if self._aged:
+            self.refresh()
+        key = (weight.data_ptr(), tuple(weight.shape))
+        e = self.entries.get(key)
+        if e is not None and e["wref"]() is None:          # the address now belongs to someone else's values
+            e = None
+        if e is None:
+            if not weight.is_contiguous():
+                raise BtsHipError("train.upconv: weight must be contiguous OIHW")
+            fs, ds = ops.upconv_train_pack_shapes(weight.shape[0], weight.shape[1])
+            e = self.entries[key] = dict(wref=weakref.ref(weight), ptr=weight.data_ptr(), version=-1,
+                                         fwd=torch.empty(fs, dtype=torch.float32, device=weight.device),
+                                         dgrad=torch.empty(ds, dtype=torch.float32, device=weight.device))
+            self._table_key = None
+        if e["version"] != weight._version:                # new, or rewritten in the open since the last begin_step()
+            ops.upconv_train_pack([weight.detach()], [e["fwd"]], [e["dgrad"]])
+            self._stamp([e])
+        return e["fwd"], e["dgrad"]
+
+    def refresh(self):
+        """Re-pack every registered weight, changed or not, in one launch per device."""
+        self._aged = False
+        alive = {k: e["wref"]() for k, e in self.entries.items()}     # strong references for the duration of the call
+        for k in [k for k, w in alive.items() if w is None]:
+            del self.entries[k]
+            self._table_key = None
+        if not self.entries:
+            return
+        items = list(self.entries.values())
+        key = tuple(id(e) for e in items)
+        if self._table_key != key:
+            self._table, self._table_key = {}, key
+        by_dev = {}
+        for k, e in self.entries.items():
+            by_dev.setdefault(str(e["fwd"].device), []).append((alive[k], e))
+        for dev, pairs in by_dev.items():
+            ws = [w.detach() for w, _ in pairs]
+            self._table[dev] = ops.upconv_train_pack(ws, [e["fwd"] for _, e in pairs], [e["dgrad"] for _, e in pairs],
+                                                     table=self._table.get(dev))
+        self._stamp(items)
+
+
+_UPCONV_PACKER = UpconvPacker()
+
+
 def begin_step():
     """Top of a training forward: bring all packed weights up to date with one launch.
 
@@ -197,12 +272,16 @@ def begin_step():
 
     The exception is ``WeightPacker.versions_trusted``: after a step of ``optim.NativeAdamW`` the versions ARE the change
     signal and the entries it re-packed itself are current, so only what is stale by version goes into the pack launch
-    (frozen weights are not touched; often nothing is launched at all)."""
+    (frozen weights are not touched; often nothing is launched at all).
+
+    The sub-pixel upconv packs (``UpconvPacker``, decoder.subpixel_upconv_train) are never part of that bargain: every
+    step ages them all, and the step's first sub-pixel upconv re-packs them from the parameters in one launch."""
     if _STEP_DEPTH[0] > 0:                 # inside model_step(): the model's forward already did this
         return
     from . import workspace
     workspace.invalidate_packs()
     _PACKER.refresh(force=not _PACKER.versions_trusted)
+    _UPCONV_PACKER.invalidate()
 
 
 _STEP_DEPTH = [0]
@@ -434,10 +513,60 @@ def atrous_forward(m, x):
     return conv2d(x, seq[4].weight, padding=m.dilation, dilation=m.dilation, tag="aspp3x3")
 
 
-def upconv_forward(m, x):
-    """upconv.forward, bts.py:90-94."""
+class _UpconvFn(torch.autograd.Function):
+    """y = elu(conv3x3(nearest_2x(x), w, padding 1)) in sub-pixel form in all three passes (include/bts_hip.h states the
+    identities): 16 products per source pixel instead of the 36 of ``conv2d(..., up=2)``, no upsampled input gradient and
+    no 2x2 sum pass behind it.  ELU' stays on ATen, as in ``_ConvFn``."""
+
+    @staticmethod
+    def forward(ctx, x, weight, tag):
+        refuse_bf16("train.upconv")
+        ops._need(x, "train.upconv")
+        ops._need(weight, "train.upconv")
+        B, C, h, w = x.shape
+        cout, cin, k, k2 = weight.shape
+        if cin != C or k != 3 or k2 != 3 or C % 4 or cout % 4:
+            raise BtsHipError("train.upconv: weight %s does not fit input %s (3x3, channels multiples of 4)"
+                              % (tuple(weight.shape), tuple(x.shape)))
+        x2d, _ = _nhwc_rows(x.detach())
+        wf, wd = _UPCONV_PACKER.get(weight)
+        y = torch.empty((B, 2 * h, 2 * w, cout), dtype=torch.float32, device=x.device)
+        ops.conv_forward(x2d, B, h, w, wf, cout, 3, up=2, c_in_ld=C, y2d=y.view(B * 4 * h * w, cout), subpixel=True,
+                         act=ops.ACT_ELU, tag=tag + ".fwd", c_in_real=C)
+        out = y.permute(0, 3, 1, 2)
+        ctx.save_for_backward(x2d, out, wd)   # ELU'(v) = 1 (y > 0) or y + 1; wd: this step's pack (refills happen between steps)
+        ctx.geom = (B, C, h, w, cout, tag)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x2d, out, wd = ctx.saved_tensors
+        B, C, h, w, cout, tag = ctx.geom
+        grad_out = torch.ops.aten.elu_backward(grad_out, 1.0, 1.0, 1.0, True, out)
+        dy2d, co4 = _nhwc_rows(grad_out)
+        dev = grad_out.device
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dxr = torch.empty((B, h, w, C), dtype=torch.float32, device=dev)
+            ops.upconv_dgrad(dy2d, B, h, w, wd, cout, C, dxr.view(B * h * w, C), splitk_ws=_splitk_workspace(dev), tag=tag + ".dgrad")
+            dx = dxr.permute(0, 3, 1, 2)
+        if ctx.needs_input_grad[1]:
+            g = ops.upconv_wgrad(x2d, B, h, w, C, dy2d, cout, _workspace(dev), tag=tag + ".wgrad")
+            dw = g.reshape(cout, 3, 3, C).permute(0, 3, 1, 2).contiguous()     # OIHW, the layout DDP buckets expect
+        return dx, dw, None
+
+
+def upconv_forward(m, x, subpixel=None):
+    """upconv.forward, bts.py:90-94.  ``subpixel`` (the decoder passes its ``subpixel_upconv_train``; None: the module's
+    own ``subpixel_train`` attribute, default False): ratio-2 layers whose channel counts are multiples of 4 run in
+    sub-pixel form in all three passes (_UpconvFn); everything else stays on ``conv2d``."""
     if m.ratio not in (1, 2):
         raise BtsHipError("upconv: ratio %r not built (1 or 2)" % (m.ratio,))
+    w = m.conv.weight
+    if subpixel is None:
+        subpixel = getattr(m, "subpixel_train", False)
+    if subpixel and m.ratio == 2 and w.shape[0] % 4 == 0 and w.shape[1] % 4 == 0:
+        return _UpconvFn.apply(x, w, "upconv")
     return conv2d(x, m.conv.weight, padding=1, up=int(m.ratio), tag="upconv", act=ops.ACT_ELU)
 
 
@@ -508,9 +637,10 @@ def _decoder_forward(dec, features, focal):
     md = dec.params.max_depth
     cl = torch.channels_last
     x = F.relu(features[5]).contiguous(memory_format=cl)
-    x = _bn(upconv_forward(dec.upconv5, x), dec.bn5)
+    sub = bool(getattr(dec, "subpixel_upconv_train", False))
+    x = _bn(upconv_forward(dec.upconv5, x, sub), dec.bn5)
     iconv5 = _conv_elu(dec.conv5, torch.cat([x, skip3], 1), "conv5")
-    x = _bn(upconv_forward(dec.upconv4, iconv5), dec.bn4)
+    x = _bn(upconv_forward(dec.upconv4, iconv5, sub), dec.bn4)
     concat4 = torch.cat([x, skip2], 1)
     iconv4 = _bn(_conv_elu(dec.conv4, concat4, "conv4"), dec.bn4_2)
 
@@ -533,13 +663,13 @@ def _decoder_forward(dec, features, focal):
         return lpg_mod(plane_eq, focal).unsqueeze(1) / md
 
     depth_8x8 = lpg_scale(dec.reduc8x8, dec.lpg8x8, daspp_feat)
-    x = _bn(upconv_forward(dec.upconv3, daspp_feat), dec.bn3)
+    x = _bn(upconv_forward(dec.upconv3, daspp_feat, sub), dec.bn3)
     iconv3 = _conv_elu(dec.conv3, torch.cat([x, skip1, depth_8x8[:, :, ::4, ::4]], 1), "conv3")
     depth_4x4 = lpg_scale(dec.reduc4x4, dec.lpg4x4, iconv3)
-    x = _bn(upconv_forward(dec.upconv2, iconv3), dec.bn2)
+    x = _bn(upconv_forward(dec.upconv2, iconv3, sub), dec.bn2)
     iconv2 = _conv_elu(dec.conv2, torch.cat([x, skip0, depth_4x4[:, :, ::2, ::2]], 1), "conv2")
     depth_2x2 = lpg_scale(dec.reduc2x2, dec.lpg2x2, iconv2)
-    upconv1 = upconv_forward(dec.upconv1, iconv2)
+    upconv1 = upconv_forward(dec.upconv1, iconv2, sub)
     if fused and fused_reduction_available(dec.reduc1x1, 0):
         reduc1x1 = fused_reduction_final(dec.reduc1x1, upconv1, batched)
     else:

@@ -393,6 +393,61 @@ int  bts_conv_wgrad_batch_plan_f32(const bts_conv_wgrad_desc* descs, int n, cons
 int  bts_conv_wgrad_batch_f32(const void* table_host, const void* table_dev, int n, const void* const* bases, int n_bases,
                               float* ws, bts_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Sub-pixel upconv in the training step (reference upconv, pytorch/bts.py:83-94: nearest-2x + 3x3 convolution).  With
+ * S_0 = [[1,0,0],[0,1,1]], S_1 = [[1,1,0],[0,0,1]] and the class filters g_(py,px) = S_py w S_px^T (2x2, the filters of
+ * bts_conv_desc.subpixel), x zero outside the [h,w] source map:
+ *   forward          y[2Y+py, 2X+px] = sum_{ty,tx} g_(py,px)[ty,tx] x[Y-1+py+ty, X-1+px+tx]        (bts_conv_fwd_f32, subpixel)
+ *   input gradient   dx[Y,X] = sum_{r,s in 0..3} K[r,s] dy[2Y-1+r, 2X-1+s],  K[3-py-2ty, 3-px-2tx] = g_(py,px)[ty,tx]^T
+ *   weight gradient  dg_(py,px)[ty,tx] = sum_{b,Y,X} dy[2Y+py, 2X+px] (x) x[Y-1+py+ty, X-1+px+tx],
+ *                    dw[ky,kx] = sum_{py,px} dg_(py,px)[tau_py(ky), tau_px(kx)],  tau_0 = (0,1,1), tau_1 = (0,0,1)
+ * 16 products per source pixel, input and output channel in every pass (the 3x3 on the upsampled grid issues 36).
+ * c_in % 4 == 0 and c_out % 4 == 0 throughout, every pointer 16-byte aligned, pixel strides multiples of 4 floats and at
+ * least the channel count; anything else is BTS_ERR_INVALID before any GPU work.
+ *
+ * bts_upconv_dgrad_f32: dx = the 4x4 / stride-2 / padding-1 convolution above, on the row-tiled convolution kernel.
+ *   dy: NHWC [B,2h,2w], dy_pix_stride >= c_out;  dx: NHWC [B,h,w], dx_pix_stride >= c_in (every real channel written)
+ *   w_dgrad: [round_up(c_in,32)][round_up(16*c_out,32)], element [c][(4r+s)*c_out + n] = K[r,s][c][n], zero padded
+ *            (bts_upconv_train_pack_f32 writes it)
+ *   precision, fill_frames, splitk_ws / splitk_ws_floats: as in bts_conv_desc (precision 0 or 1 in training; the
+ *            workspace is NULL with 0 floats, or lets under-filled launches split K with the fixed-order reduction).
+ * bts_upconv_dgrad_plan: the kernel that launch will take (host only, no pointers): *bm x *bn tile and *kind as
+ * bts_conv_plan_f32 reports them (BTS_CONV_KIND_ROW, plus BTS_CONV_FLAG_SPLITK when it splits). */
+int bts_upconv_dgrad_f32(const float* dy, long dy_pix_stride, int B, int h, int w, int c_out, const float* w_dgrad, int c_in,
+                         float* dx, long dx_pix_stride, int precision, int fill_frames, float* splitk_ws, long splitk_ws_floats,
+                         bts_stream_t stream);
+int bts_upconv_dgrad_plan(int B, int h, int w, int c_out, int c_in, int precision, int fill_frames, long splitk_ws_floats,
+                          int* bm, int* bn, int* kind);
+
+/* bts_upconv_wgrad_f32: dw in OHWI [c_out][9][c_in] (the layout bts_conv_wgrad_f32 writes).
+ *   x: forward input NHWC [B,h,w], x_pix_stride >= c_in;  dy: NHWC [B,2h,2w], dy_pix_stride >= c_out
+ *   ws: MANDATORY scratch of ws_floats floats, exclusive to this stream while the call runs (the class gradients need a
+ *       home even unsplit).  The launch writes EXACTLY split * 16 * c_out * c_in floats -- [split][class][c_out][4*c_in],
+ *       class = 2 py + px, column (2 ty + tx) * c_in + ci -- and nothing beyond; ws_floats below 16 * c_out * c_in is
+ *       BTS_ERR_INVALID.
+ * Tile and pixel split are bts_conv_wgrad_f32's planner on M = B*h*w source pixels, N = 4*c_in and four bundles (the
+ * classes).  A second launch sums in a fixed order (no atomics, bit-reproducible): per class the split partials exactly as
+ * bts_conv_wgrad_f32's reduction does (lane j of 16 adds splits j, j+16, ... four at a time as (a0+a1)+(a2+a3), then the
+ * 16 lane sums in lane order) giving r_0..r_3, then dw = ((r_0 + r_1) + r_2) + r_3.
+ * bts_upconv_wgrad_plan_f32: tile, split and pixels per split that launch will use for a workspace of ws_floats floats
+ * (host only, no pointers, no device; rejects what the launch rejects); any of the four outputs may be NULL. */
+int bts_upconv_wgrad_f32(const float* x, long x_pix_stride, int B, int h, int w, int c_in, const float* dy, long dy_pix_stride,
+                         int c_out, float* dw, float* ws, long ws_floats, bts_stream_t stream);
+int bts_upconv_wgrad_plan_f32(int B, int h, int w, int c_in, int c_out, long ws_floats, int* bm, int* bn, long* split,
+                              long* pix_per_split);
+
+/* bts_upconv_train_pack_f32: both packs of every registered upconv weight in ONE launch, once per training step.
+ * table: n_entries device records of 12 int64 each --
+ *   { src (OIHW float* [c_out][c_in][3][3]), fwd (float*), dgrad (float*), c_out, c_in, c_in_ld, c_out_ld, c_out_pad,
+ *     k_pad_f, c_in_pad, k_pad_d, first_block (prefix sum of bts_upconv_train_pack_blocks over the table) }
+ *   fwd   [4][c_out_pad][k_pad_f]: [2py+px][n][(2ty+tx)*c_in_ld + c] = g_(py,px)[ty,tx][n][c]   (bts_conv_desc.subpixel)
+ *   dgrad [c_in_pad][k_pad_d]    : [c][(4r+s)*c_out_ld + n] = K[r,s][c][n]                       (bts_upconv_dgrad_f32)
+ * zero elsewhere.  Every element is the fp32 sum of the 1, 2 or 4 taps of w it covers, added in the order ky outer, kx
+ * inner with one rounding per addition (no fused contraction): the forward pack is bit-identical to
+ * bts_amd/ops.py:pack_upconv_subpixel, and a dgrad element has the bits of its forward twin. */
+long bts_upconv_train_pack_blocks(long c_out_pad, long k_pad_f, long c_in_pad, long k_pad_d);
+int bts_upconv_train_pack_f32(const void* table, int n_entries, long total_blocks, bts_stream_t stream);
+
 /* Batched weight re-packing for the training step (the optimiser rewrites the OIHW parameters every iteration,
  * bts_main.py:606): one launch lays every registered weight out as bts_conv_fwd_f32 wants it.
  * table: n_entries device records of 14 int64 each --
