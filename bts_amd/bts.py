@@ -393,6 +393,11 @@ class bts(nn.Module):
         self.subpixel_upconv_train = False              # train() mode: True runs the ratio-2 upconvs in sub-pixel form in the
                                                         # forward, input-gradient and weight-gradient passes (train._UpconvFn;
                                                         # 16 products per source pixel instead of 36)
+        self.bf16_tail_convs = False                    # eval, conv_precision "bf16": True runs conv3 / conv2 -- which that mode
+                                                        # otherwise keeps on the fp32 tail kernel -- on the bf16 halo tile with
+                                                        # the depth plane added in fp32 (ops.conv_tail_bf16_forward),
+                                                        # where the library's plan query takes the layer
+        self._packs_tail_bf16 = PackCache(self)
 
     # ------------------------------------------------------------------ weight packing (lazy)
     _OWN = ("bn5", "conv5", "bn4", "conv4", "bn4_2", "daspp_conv", "bn3", "conv3", "bn2", "conv2", "conv1", "get_depth")
@@ -400,6 +405,19 @@ class bts(nn.Module):
     def packed(self):
         return self._packs.get(self.conv5[0].weight.device, self._build_pack,
                                key_modules=lambda origin: [getattr(origin, n) for n in self._OWN])
+
+    def packed_tail_bf16(self):
+        """{"conv3": (w_main, w_tail), "conv2": ...}: the two planar-tail layers' weights as ops.pack_conv_tail_bf16 lays
+        them out; layers whose main channels are no whole 32-channel chunks are absent.  Made once per weights and device."""
+        def build():
+            out = {}
+            for name in ("conv3", "conv2"):
+                w = getattr(self, name)[0].weight.detach()
+                if (w.shape[1] - 1) % 32 == 0:
+                    out[name] = ops.pack_conv_tail_bf16(w, 1)
+            return out
+        return self._packs_tail_bf16.get(self.conv3[0].weight.device, build,
+                                         key_modules=lambda origin: [origin.conv3, origin.conv2])
 
     def _build_pack(self):
         nf = self.num_features
@@ -529,6 +547,17 @@ class bts(nn.Module):
                                     y2d=y2d, y_nchw=y_nchw, tag="decoder_upconv" if up == 2 else "decoder_conv",
                                     c_in_real=c_in_real, subpixel=(up == 2), splitk_ws=ws["splitk"], tail_planes=tail)
 
+        # conv3 / conv2 under conv_precision "bf16" with the bf16_tail_convs switch: bf16 main channels, fp32 depth plane
+        tail_bf16 = bool(self.bf16_tail_convs) and ops.current_launch_config()[1] == 2
+        P_tail = self.packed_tail_bf16() if tail_bf16 else {}
+
+        def tail_conv(name_w, x2d, hh, ww, cout, y2d, c_in_real, plane):
+            c_main = x2d.shape[1]
+            if name_w in P_tail and ops.conv_tail_bf16_plan(hh, ww, c_main, cout).eligible:
+                wm, wt = P_tail[name_w]
+                return ops.conv_tail_bf16_forward(x2d, B, hh, ww, wm, wt, plane, c_main, cout, y2d, act=ELU, c_in_real=c_in_real)
+            return conv(name_w, x2d, hh, ww, cout, y2d=y2d, c_in_real=c_in_real, tail=[plane])
+
         # H/16 and H/8 trunk (bts.py:226-235)
         sk = ws["splitk"]
         self.upconv5.run_nhwc(dense2d, B, H // 32, W // 32, ws["cat5"][:, :nf], taps_buf=ws.get("taps5"), e2=P["bn5"],
@@ -573,7 +602,7 @@ class bts(nn.Module):
 
         # H/4 (bts.py:258-270)
         self.upconv3.run_nhwc(ws["daspp_feat"], B, h8, w8, c3[:, :q], e2=P["bn3"], splitk_ws=sk)
-        conv("conv3", c3, h4, w4, q, y2d=ws["iconv3"], c_in_real=q + f[1] + 1, tail=[ws["ds8"]])
+        tail_conv("conv3", c3, h4, w4, q, ws["iconv3"], q + f[1] + 1, ws["ds8"])
         depth_4x4_scaled = out_tensor(1, 1)
         a4 = am()
         c2 = ws["cat2"]
@@ -582,7 +611,7 @@ class bts(nn.Module):
 
         # H/2 (bts.py:272-283)
         self.upconv2.run_nhwc(ws["iconv3"], B, h4, w4, c2[:, :nf // 8], e2=P["bn2"], splitk_ws=sk)
-        conv("conv2", c2, h2, w2, nf // 8, y2d=ws["iconv2"], c_in_real=nf // 8 + f[0] + 1, tail=[ws["ds4"]])
+        tail_conv("conv2", c2, h2, w2, nf // 8, ws["iconv2"], nf // 8 + f[0] + 1, ws["ds4"])
         depth_2x2_scaled = out_tensor(2, 1)
         a2 = am()
         self.reduc2x2.run_lpg_nhwc(ws["iconv2"], B, h2, w2, 2, depth_2x2_scaled, None, a2)
@@ -692,6 +721,16 @@ class BtsModel(nn.Module):
     @subpixel_upconv_train.setter
     def subpixel_upconv_train(self, on: bool):
         self.decoder.subpixel_upconv_train = bool(on)
+
+    @property
+    def bf16_tail_convs(self) -> bool:
+        """The decoder's switch of the same name (bts.bf16_tail_convs), default False: with conv_precision "bf16", conv3 / conv2
+        on the bf16 halo tile with an fp32 depth plane instead of the fp32 tail kernel."""
+        return self.decoder.bf16_tail_convs
+
+    @bf16_tail_convs.setter
+    def bf16_tail_convs(self, on: bool):
+        self.decoder.bf16_tail_convs = bool(on)
 
     @property
     def batched_wgrad(self) -> bool:

@@ -787,6 +787,7 @@ thread_local ConvChoice* g_dry = nullptr;
 #include "conv_halo_emu.inc"
 #include "conv_wino.inc"
 #include "conv_up9.inc"
+#include "conv_tail_bf16.inc"
 #include "conv_1x1.inc"
 #include "conv_stem.inc"
 
@@ -1207,6 +1208,43 @@ extern "C" int bts_upconv_up9_fwd_f32(const float* x, long x_pix_stride, int B, 
     a.ntiles = (int)nwg;
     hipLaunchKernelGGL(conv_up9_kernel<32>, dim3((unsigned)nwg), dim3(256), 0, (hipStream_t)stream, a);
     return (int)hipGetLastError();
+}
+
+// ---- planar-tail 3x3 convolution with bf16 main operands (conv_tail_bf16.inc): its own opt-in entry point and plan query,
+//      so that bts_conv_fwd_f32 / bts_conv_plan_f32 answer for every descriptor exactly as they did without it
+extern "C" int bts_conv_tail_bf16_plan(int h, int w, int c_main, int c_out, int n_tail, int fill_frames, int* bn, long* workgroups) {
+    if (!bn || !workgroups) return BTS_ERR_INVALID;
+    if (fill_frames < 0 || fill_frames > 4096) return BTS_ERR_INVALID;
+    const int ff = fill_frames > 0 ? fill_frames : knobs().fill_frames;
+    long wgs = 0;
+    const bool ok = tail_bf16_eligible(h, w, c_main, c_out, n_tail, &wgs);
+    *bn = ok ? tail_bf16_bn(c_out) : 0; *workgroups = ok ? ff * wgs : 0;
+    return 0;
+}
+
+extern "C" int bts_conv_tail_bf16_fwd_f32(const float* x, long x_pix_stride, int B, int h, int w, int c_main, const void* w_main,
+                                          const float* w_tail, const float* tail_plane, int n_tail, int c_out, int c_out_pad,
+                                          const float* e2_scale, const float* e2_shift, int act, float* y, long y_pix_stride,
+                                          bts_stream_t stream) {
+    if (!x || !w_main || !w_tail || !tail_plane || !y) return BTS_ERR_INVALID;
+    if (B <= 0 || h <= 0 || w <= 0 || c_main <= 0 || c_out <= 0) return BTS_ERR_INVALID;
+    if (n_tail < 1 || n_tail > 4) return BTS_ERR_INVALID;
+    if (n_tail != 1 || (c_main % BK)) return BTS_ERR_UNSUPPORTED;
+    if ((c_out_pad & 31) || c_out_pad < c_out) return BTS_ERR_INVALID;
+    if ((x_pix_stride & 3) || x_pix_stride < c_main || y_pix_stride < c_out) return BTS_ERR_INVALID;
+    if (((uintptr_t)x & 15) || ((uintptr_t)w_main & 15) || ((uintptr_t)w_tail & 15) || ((uintptr_t)tail_plane & 3) || ((uintptr_t)y & 3))
+        return BTS_ERR_INVALID;
+    if ((e2_scale == nullptr) != (e2_shift == nullptr) || act < 0 || act > 2) return BTS_ERR_INVALID;
+    // the kernel addresses both operands with 32-bit element offsets, decodes tiles with 32-bit arithmetic and addresses the
+    // pixels of an output tile row with a 32-bit per-lane offset
+    if ((double)B * h * w * (double)x_pix_stride >= 4294967296.0 || (double)B * h * w >= 2147483648.0 ||
+        (double)c_out_pad * 9.0 * c_main >= 4294967296.0 || 64.0 * (double)y_pix_stride >= 4294967296.0) return BTS_ERR_UNSUPPORTED;
+    TailBf16Args a;
+    a.x = x; a.x_pix_stride = x_pix_stride; a.B = B; a.H = h; a.W = w; a.c_main = c_main;
+    a.w_main = static_cast<const unsigned short*>(w_main); a.w_tail = w_tail; a.tail = tail_plane;
+    a.c_out = c_out; a.c_out_pad = c_out_pad; a.e2_scale = e2_scale; a.e2_shift = e2_shift; a.act = act;
+    a.y = y; a.y_pix_stride = y_pix_stride; a.n_ntiles = 0;
+    return tail_bf16_bn(c_out) == 128 ? launch_tail_bf16<128>(a, (hipStream_t)stream) : launch_tail_bf16<64>(a, (hipStream_t)stream);
 }
 
 // ---- input gradient of the sub-pixel upconv (training): one 4x4 / stride-2 / padding-1 convolution over dy at its natural

@@ -345,6 +345,52 @@ void upconv_up9(const Tensor& x, const Tensor& u, OptTensor e2_scale, OptTensor 
                                     y.data_ptr<float>(), ys, current_stream()), op);
 }
 
+// ------------------------------------------------------------------------------- planar-tail 3x3, bf16 main operands
+// conv3x3 over [main channels | one depth plane] + activation + affine as one launch of the bf16 halo tile with an fp32 tail
+// (bts_conv_tail_bf16_fwd_f32).  x: [B*h*w, >= c_main] NHWC view; w_main: bf16 [c_out_pad, 9 * c_main]; w_tail: fp32
+// [c_out_pad, 9, 4] (ops.pack_conv_tail_bf16); tail: the plane, B*h*w floats; y: [B*h*w, c_out] NHWC view.
+// geom = {B, h, w, c_main, c_out, act}.
+void conv_tail_bf16(const Tensor& x, const Tensor& w_main, const Tensor& w_tail, const Tensor& tail, OptTensor e2_scale, OptTensor e2_shift,
+                    Tensor y, std::vector<int64_t> geom) {
+    const char* op = "bts_hip::conv_tail_bf16";
+    TORCH_CHECK(geom.size() == 6, op, ": geom must hold 6 integers, got ", geom.size());
+    const int64_t B = geom[0], h = geom[1], w = geom[2], c_main = geom[3], c_out = geom[4], act = geom[5];
+    TORCH_CHECK(B > 0 && h > 0 && w > 0 && c_main > 0 && c_out > 0, op, ": non-positive dimension");
+    TORCH_CHECK(c_main % 32 == 0, op, ": c_main (", c_main, ") must be a multiple of 32");
+    const long xs = rows2d_stride(x, op, "x"), ys = rows2d_stride(y, op, "y");
+    TORCH_CHECK(w_main.is_cuda(), op, ": w_main must be a CUDA(ROCm) tensor (no CPU fallback)");
+    TORCH_CHECK(w_main.scalar_type() == at::kBFloat16, op, ": w_main must be bfloat16, got ", w_main.scalar_type());
+    need_f32_cuda(w_tail, op, "w_tail");
+    need_f32_cuda(tail, op, "tail");
+    same_device(x, w_main, op, "w_main");
+    same_device(x, w_tail, op, "w_tail");
+    same_device(x, tail, op, "tail");
+    same_device(x, y, op, "y");
+    TORCH_CHECK(x.size(0) == B * h * w && x.size(1) >= c_main, op, ": x (", x.sizes(), ") is not a [B*h*w, >= c_main] view");
+    TORCH_CHECK(y.size(0) == B * h * w && y.size(1) == c_out, op, ": y (", y.sizes(), ") is not a [B*h*w, c_out] view");
+    TORCH_CHECK(w_main.is_contiguous() && w_main.dim() == 2 && w_main.size(1) == 9 * c_main && w_main.size(0) >= c_out && w_main.size(0) % 32 == 0,
+                op, ": w_main must be contiguous [c_out_pad, 9 * c_main] with c_out_pad a multiple of 32 (ops.pack_conv_tail_bf16), got ", w_main.sizes());
+    const int64_t c_out_pad = w_main.size(0);
+    TORCH_CHECK(w_tail.is_contiguous() && w_tail.numel() == c_out_pad * 36, op, ": w_tail must be contiguous [c_out_pad, 9, 4], got ", w_tail.sizes());
+    TORCH_CHECK(tail.is_contiguous() && tail.numel() == B * h * w, op, ": tail must be one contiguous plane of B*h*w floats (n_tail 1), got ",
+                tail.sizes());
+    TORCH_CHECK(act >= 0 && act <= 2, op, ": act must be 0 (none), 1 (ReLU) or 2 (ELU), got ", act);
+    auto vec = [&](const OptTensor& t, const char* what) -> const float* {
+        if (!(t.has_value() && t->defined())) return nullptr;
+        need_f32_cuda(*t, op, what);
+        same_device(x, *t, op, what);
+        TORCH_CHECK(t->is_contiguous() && t->numel() >= c_out, op, ": ", what, " must be a contiguous vector of at least ", c_out, " floats");
+        return t->data_ptr<float>();
+    };
+    const float* es = vec(e2_scale, "e2_scale");
+    const float* eb = vec(e2_shift, "e2_shift");
+    TORCH_CHECK((es == nullptr) == (eb == nullptr), op, ": give both e2 vectors or neither");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+    check_rc(bts_conv_tail_bf16_fwd_f32(x.data_ptr<float>(), xs, (int)B, (int)h, (int)w, (int)c_main, w_main.data_ptr(), w_tail.data_ptr<float>(),
+                                        tail.data_ptr<float>(), 1, (int)c_out, (int)c_out_pad, es, eb, (int)act, y.data_ptr<float>(), ys,
+                                        current_stream()), op);
+}
+
 // ------------------------------------------------------------------------------------------------------ training losses
 // silog_loss / depth_l1_loss (pytorch/bts.py:41-63) over the valid pixels of the whole batch, csrc/loss.hip: no boolean gather, no host
 // sync.  kind 0 = silog (param = variance_focus), 1 = asymmetric L1 (param = inbalance_to_closer); mask bool / uint8 or None (gt > gt_min).
@@ -415,6 +461,7 @@ TORCH_LIBRARY(bts_hip, m) {
           "Tensor? e2_shift, Tensor(a!) y, Tensor(b!)? y2, Tensor? res, Tensor(c!)? splitk_ws, Tensor[] tail_planes, Tensor? w_split, "
           "Tensor? w_wino, int[] geom) -> ()");
     m.def("upconv_up9(Tensor x, Tensor u, Tensor? e2_scale, Tensor? e2_shift, Tensor(a!) y, int[] geom) -> ()");
+    m.def("conv_tail_bf16(Tensor x, Tensor w_main, Tensor w_tail, Tensor tail, Tensor? e2_scale, Tensor? e2_shift, Tensor(a!) y, int[] geom) -> ()");
     m.def("depth_loss(Tensor est, Tensor gt, Tensor? mask, float gt_min, int kind, float param) -> (Tensor loss, Tensor stats)");
     m.def("depth_loss_backward(Tensor est, Tensor gt, Tensor? mask, float gt_min, int kind, float param, Tensor stats, Tensor grad_loss) -> Tensor");
 }
@@ -429,6 +476,7 @@ TORCH_LIBRARY_IMPL(bts_hip, CUDA, m) {
     m.impl("reduction_1x1_train", &reduction_1x1_train);
     m.impl("conv_fwd", &conv_fwd);
     m.impl("upconv_up9", &upconv_up9);
+    m.impl("conv_tail_bf16", &conv_tail_bf16);
     m.impl("depth_loss", &depth_loss);
     m.impl("depth_loss_backward", &depth_loss_backward);
 }

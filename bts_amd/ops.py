@@ -1080,6 +1080,99 @@ def upconv_up9_forward(x2d: torch.Tensor, B: int, h: int, w: int, u: torch.Tenso
     return y2d
 
 
+# ---- planar-tail 3x3 (decoder conv3 / conv2) with bf16 main operands and an fp32 tail (csrc/conv_tail_bf16.inc)
+def pack_conv_tail_bf16(weight_oihw: torch.Tensor, n_tail: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """[c_out, c_main + n_tail, 3, 3] -> (w_main, w_tail) as bts_conv_tail_bf16_fwd_f32 reads them.  w_main: bfloat16
+    [c_out_pad, 9 * c_main], k = tap * c_main + c, the main-channel weights rounded to the nearest bf16 (ties to even:
+    ``Tensor.to(torch.bfloat16)``).  w_tail: float32 [c_out_pad, 9, 4], slot j = tail plane j, the tail weights bit for bit.
+    Rows past c_out and unused slots are zero."""
+    if weight_oihw.dim() != 4 or tuple(weight_oihw.shape[2:]) != (3, 3) or not 1 <= n_tail <= 4 or weight_oihw.shape[1] <= n_tail:
+        raise BtsHipError("pack_conv_tail_bf16: needs a [c_out, c_main + n_tail, 3, 3] weight and 1..4 tail planes")
+    cout, cin = weight_oihw.shape[:2]
+    c_main = cin - n_tail
+    if c_main % 32:
+        raise BtsHipError("pack_conv_tail_bf16: %d main channels; the bf16 halo tile needs a multiple of 32" % c_main)
+    wf = weight_oihw.detach().float()
+    cout_pad = round_up(cout, 32)
+    w_main = torch.zeros((cout_pad, 9 * c_main), dtype=torch.bfloat16, device=wf.device)
+    w_main[:cout] = wf[:, :c_main].permute(0, 2, 3, 1).reshape(cout, 9 * c_main).to(torch.bfloat16)
+    w_tail = torch.zeros((cout_pad, 9, 4), dtype=torch.float32, device=wf.device)
+    w_tail[:cout, :, :n_tail] = wf[:, c_main:].permute(0, 2, 3, 1).reshape(cout, 9, n_tail)
+    return w_main.contiguous(), w_tail.contiguous()
+
+
+class TailBf16Plan(tuple):
+    """(bn, workgroups of the declared launch) of bts_conv_tail_bf16_plan; all 0 = the layer stays on the fp32 tail kernel."""
+    bn = property(lambda self: self[0])
+    workgroups = property(lambda self: self[1])
+    eligible = property(lambda self: self[0] > 0)
+
+
+def conv_tail_bf16_plan(h: int, w: int, c_main: int, c_out: int, n_tail: int = 1, fill_frames: Optional[int] = None) -> TailBf16Plan:
+    """Should this planar-tail layer take conv_tail_bf16_forward?  Host-only query (bts_conv_tail_bf16_plan);
+    ``fill_frames`` defaults to the launch_config in force."""
+    ff = current_launch_config()[0] if fill_frames is None else int(fill_frames)
+    bn, wgs = C.c_int(0), C.c_long(0)
+    _lib.check(_lib.load_real().bts_conv_tail_bf16_plan(int(h), int(w), int(c_main), int(c_out), int(n_tail), int(ff), C.byref(bn),
+                                                         C.byref(wgs)), "bts_conv_tail_bf16_plan")
+    return TailBf16Plan((bn.value, wgs.value))
+
+
+def conv_tail_bf16_forward(x2d: torch.Tensor, B: int, h: int, w: int, w_main: torch.Tensor, w_tail: torch.Tensor,
+                           tail_plane: torch.Tensor, c_main: int, c_out: int, y2d: torch.Tensor, act: int = ACT_ELU,
+                           e2: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, tag: str = "decoder_conv",
+                           c_in_real: Optional[int] = None):
+    """act(conv3x3([x | plane])) [-> e2 affine] in one launch of the bf16 halo tile with an fp32 tail
+    (bts_conv_tail_bf16_fwd_f32): x2d [B*h*w, >= c_main] NHWC view, (w_main, w_tail) from pack_conv_tail_bf16, tail_plane
+    one contiguous [B,h,w] (or [B,1,h,w]) map, y2d [B*h*w, c_out] NHWC view (a channel slice is fine).  Runs whatever the
+    plan query says: callers ask conv_tail_bf16_plan first."""
+    name = "conv_tail_bf16_forward"
+    xs, xc = _rows2d(x2d, name)
+    ys, yc = _rows2d(y2d, name)
+    _need(w_tail, name)
+    _need(tail_plane, name)
+    if not isinstance(w_main, torch.Tensor) or not w_main.is_cuda or w_main.dtype != torch.bfloat16:
+        raise BtsHipError("conv_tail_bf16_forward: w_main must be a bfloat16 CUDA/ROCm tensor (pack_conv_tail_bf16)")
+    if c_main % 32 or xc < c_main or yc != c_out or x2d.shape[0] != B * h * w or y2d.shape[0] != B * h * w:
+        raise BtsHipError("conv_tail_bf16_forward: views %s / %s do not fit B=%d %dx%d, %d (a multiple of 32) -> %d channels"
+                          % (tuple(x2d.shape), tuple(y2d.shape), B, h, w, c_main, c_out))
+    if w_main.dim() != 2 or w_main.shape[1] != 9 * c_main or w_main.shape[0] < c_out or w_main.shape[0] % 32 or not w_main.is_contiguous():
+        raise BtsHipError("conv_tail_bf16_forward: w_main must be contiguous [c_out_pad, 9 * c_main] (pack_conv_tail_bf16)")
+    cout_pad = w_main.shape[0]
+    if w_tail.numel() != 36 * cout_pad or not w_tail.is_contiguous():
+        raise BtsHipError("conv_tail_bf16_forward: w_tail must be contiguous [c_out_pad, 9, 4] (pack_conv_tail_bf16)")
+    if tail_plane.numel() != B * h * w or not tail_plane.is_contiguous():
+        raise BtsHipError("conv_tail_bf16_forward: tail_plane must be one contiguous map of B*h*w floats")
+    if act not in (ACT_NONE, ACT_RELU, ACT_ELU):
+        raise BtsHipError("conv_tail_bf16_forward: act must be none, ReLU or ELU")
+    es = eb = None
+    if e2 is not None:
+        es, eb = e2
+        _need(es, name)
+        _need(eb, name)
+        if es.numel() < c_out or eb.numel() < c_out:
+            raise BtsHipError("conv_tail_bf16_forward: e2 vectors need %d elements" % c_out)
+    kern, flops, nbytes, xflops = "conv", 0.0, 0.0, None
+    if _trace is not None:
+        cin = c_in_real if c_in_real is not None else c_main + 1
+        bn = 128 if c_out >= 128 else 64
+        kern = conv_plan.tail_bf16_kernel_name(bn)
+        flops = 2.0 * 9 * B * h * w * c_out * cin
+        nbytes = 4.0 * (B * h * w * (cin + c_out)) + 2.0 * 9 * c_out * c_main + 4.0 * 9 * c_out
+        tiles = B * ((h + 3) // 4) * ((w + 31) // 32)
+        xflops = 2.0 * 9 * (tiles * 128) * (round_up(c_out, bn)) * (c_main + 1)     # ragged tiles included
+    tops = torch_ops()
+    if tops is not None:
+        run = lambda: _op(lambda: tops.conv_tail_bf16(x2d, w_main, w_tail, tail_plane, es, eb, y2d, [B, h, w, c_main, c_out, int(act)]))
+    else:
+        run = lambda: _lib.load().bts_conv_tail_bf16_fwd_f32(_ptr(x2d), xs, B, h, w, c_main, _ptr(w_main), _ptr(w_tail), _ptr(tail_plane), 1,
+                                                             c_out, cout_pad, _ptr(es), _ptr(eb), int(act), _ptr(y2d), ys, _stream(x2d))
+    with torch.cuda.device(x2d.device):
+        rc = _launch(kern, tag, flops, nbytes, run, xflops=xflops)
+    _lib.check(rc, "bts_conv_tail_bf16_fwd_f32")
+    return y2d
+
+
 def pad_vec(v: Optional[torch.Tensor], n: int, fill: float = 0.0) -> Optional[torch.Tensor]:
     if v is None:
         return None

@@ -282,6 +282,34 @@ int bts_upconv_up9_fwd_f32(const float* x, long x_pix_stride, int B, int h, int 
  *   all three 0 when the layer should stay on bts_conv_fwd_f32's sub-pixel path. */
 int bts_upconv_up9_plan(int h, int w, int c_in, int c_out, int precision, int fill_frames, int* bm, int* bn, long* workgroups);
 
+/* A planar-tail 3x3 convolution (stride 1, padding 1: the decoder's conv3 / conv2, whose last input channel is a dense depth
+ * plane) with bf16 MAIN operands and an fp32 tail, in one launch (csrc/conv_tail_bf16.inc):
+ *   y[b][Y][X][n] = e2(act( sum_{tap, c < c_main} bf16(x[b][Y+dy][X+dx][c]) * w_main[n][tap * c_main + c]
+ *                         + sum_{tap} tail_plane[b][Y+dy][X+dx] * w_tail[n][tap][0] )),   tap = 3 (dy+1) + (dx+1)
+ * The main products are exact products of bf16 pairs accumulated in fp32 (v_mfma_f32_32x32x16_bf16); x is rounded to the
+ * nearest bf16 (ties to even) on its way to LDS, w_main is supplied rounded.  The tail is NOT rounded: nine fp32 FMAs per
+ * output, added after the main sum.  Pixels outside the map contribute 0 to both.  Opt-in: bts_conv_fwd_f32 never takes
+ * this path on its own (precision 2 keeps these layers on BTS_CONV_KIND_HALO_TAIL, in fp32).
+ *   x         : NHWC [B,h,w], x_pix_stride >= c_main floats per pixel (a multiple of 4), 16-byte aligned; c_main % 32 == 0
+ *   w_main    : bf16 [c_out_pad][9 * c_main], k = tap * c_main + c, 16-byte aligned (bts_amd/ops.py:pack_conv_tail_bf16)
+ *   w_tail    : fp32 [c_out_pad][9][4], slot j = tail plane j (unused slots zero), 16-byte aligned
+ *   tail_plane: fp32 [B,h,w], 4-byte aligned; n_tail = 1 (2..4: BTS_ERR_UNSUPPORTED)
+ *   y         : NHWC [B,h,w], y_pix_stride >= c_out (a channel slice is fine: nothing is written outside it)
+ *   c_out_pad % 32 == 0, >= c_out (rows past c_out are read, never stored); act 0 none / 1 ReLU / 2 ELU; e2_* [c_out] or both NULL
+ * c_main % 32 != 0: BTS_ERR_UNSUPPORTED.  Sum order fixed: bits do not depend on B. */
+int bts_conv_tail_bf16_fwd_f32(const float* x, long x_pix_stride, int B, int h, int w, int c_main, const void* w_main,
+                               const float* w_tail, const float* tail_plane, int n_tail, int c_out, int c_out_pad,
+                               const float* e2_scale, const float* e2_shift, int act, float* y, long y_pix_stride,
+                               bts_stream_t stream);
+
+/* Should a planar-tail layer take bts_conv_tail_bf16_fwd_f32 (host-side query, no GPU work, no pointers)?  Eligible:
+ * n_tail == 1, c_main % 32 == 0, c_out >= 64 and a grid of 4x32-pixel tiles that is at least 0.80 real pixels (the bf16 halo
+ * tile's own threshold).  Per-frame geometry and the declared fill_frames (as in bts_conv_desc, 0 = the library default)
+ * only, never B.
+ *   *bn = output channels per workgroup (128 or 64), *workgroups = workgroups of the DECLARED launch (fill_frames frames);
+ *   both 0 when the layer should stay on bts_conv_fwd_f32's fp32 tail kernel. */
+int bts_conv_tail_bf16_plan(int h, int w, int c_main, int c_out, int n_tail, int fill_frames, int* bn, long* workgroups);
+
 /* Which kernel bts_conv_fwd_f32 will launch for this descriptor (host-side query, no GPU work: it walks the real
  * dispatch path): lets a profiler attribute a launch to its kernel instantiation.
  *   *kind = one kernel family (kind & BTS_CONV_KIND_MASK) plus any of the BTS_CONV_FLAG_* bits. */
@@ -676,7 +704,7 @@ int  bts_adamw_step_f32(const void* table_dev, int n, long total_blocks, const b
  */
 enum { BTS_OP_CONV = 1, BTS_OP_REDUC = 2, BTS_OP_REDUC_LPG = 3, BTS_OP_LPG_FUSED = 4, BTS_OP_NCHW_TO_NHWC = 5,
        BTS_OP_NHWC_TO_NCHW = 6, BTS_OP_MAXPOOL = 7, BTS_OP_BN_RELU_AVGPOOL = 8, BTS_OP_GET_DEPTH = 9, BTS_OP_LPG = 10,
-       BTS_OP_UPCONV_COMBINE = 11, BTS_OP_UPCONV_UP9 = 12 };
+       BTS_OP_UPCONV_COMBINE = 11, BTS_OP_UPCONV_UP9 = 12, BTS_OP_CONV_TAIL_BF16 = 13 };
 
 typedef struct bts_op {
     int kind;          /* BTS_OP_*                                                              */
@@ -702,6 +730,9 @@ typedef struct bts_op {
                  float* y; long y_pix_stride; } upconv_combine;
         struct { const float* x; long x_pix_stride; int B, h, w, c_in; const float* u; int c_out; const float* e2_scale;
                  const float* e2_shift; int act; float* y; long y_pix_stride; } upconv_up9;
+        struct { const float* x; long x_pix_stride; int B, h, w, c_main; const void* w_main; const float* w_tail;
+                 const float* tail_plane; int n_tail, c_out, c_out_pad; const float* e2_scale; const float* e2_shift; int act;
+                 float* y; long y_pix_stride; } conv_tail_bf16;
     } u;
 } bts_op;
 

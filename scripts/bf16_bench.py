@@ -10,6 +10,7 @@ alike.  The bf16 outputs are then compared with the fp32 outputs of the same inp
     python scripts/bf16_bench.py                          # configs[1] (DenseNet161, B=16, 352x1216) and configs[2]
     python scripts/bf16_bench.py --configs 1 --rounds 5
     python scripts/bf16_bench.py --only bf16 --configs 1 --steps 3   # bf16 forwards only (run under rocprofv3)
+    python scripts/bf16_bench.py --bf16-tail                 # a third graph: bf16 with conv3 / conv2 on the bf16 tail kernel
 """
 import argparse
 import json
@@ -66,6 +67,12 @@ def accuracy(got, ref):
     return rep
 
 
+def set_variant(model, p):
+    """"fp32" / "bf16": the precision with the decoder's bf16_tail_convs switch off; "bf16_tail": bf16 with it on."""
+    model.conv_precision = "bf16" if p == "bf16_tail" else p
+    model.bf16_tail_convs = p == "bf16_tail"
+
+
 def run_config(idx, args, device):
     from bts_amd import synth
     from bts_amd.graph import GraphedModel
@@ -74,9 +81,9 @@ def run_config(idx, args, device):
     B, H, W = cfg["B"], cfg["H"], cfg["W"]
     image = torch.from_numpy(synth.image_batch(B, H, W, 1234)).to(device)
     focal = torch.from_numpy(synth.focal_values(B, params.dataset, 1234)).to(device)
-    precs = [args.only] if args.only else ["fp32", "bf16"]
+    precs = [args.only] if args.only else ["fp32", "bf16"] + (["bf16_tail"] if args.bf16_tail else [])
     if args.only:                                   # profiling run: eager forwards, no timing claims
-        model.conv_precision = args.only
+        set_variant(model, "bf16_tail" if (args.bf16_tail and args.only == "bf16") else args.only)
         with torch.no_grad():
             for _ in range(args.steps):
                 model(image, focal)
@@ -86,7 +93,7 @@ def run_config(idx, args, device):
     outs = {}
     with torch.no_grad():
         for p in precs:                              # capture (two eager passes inside) + warm-up replays
-            model.conv_precision = p
+            set_variant(model, p)
             for _ in range(args.warmup):
                 o = gm(image, focal)
             torch.cuda.synchronize()
@@ -94,7 +101,7 @@ def run_config(idx, args, device):
         times = {p: [] for p in precs}
         for r in range(args.rounds):
             for p in (precs if r % 2 == 0 else precs[::-1]):
-                model.conv_precision = p
+                set_variant(model, p)
                 gm(image, focal)                     # one untimed replay: the switch itself is not measured
                 s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 torch.cuda.synchronize()
@@ -104,7 +111,7 @@ def run_config(idx, args, device):
                 e.record()
                 e.synchronize()
                 times[p].append(s.elapsed_time(e) / args.steps)
-        model.conv_precision = "bf16"
+        set_variant(model, "bf16")
         again = [t.clone() for t in gm(image, focal)]
     res = {"config": idx, "encoder": cfg["encoder"], "batch": B, "height": H, "width": W, "steps_per_round": args.steps,
            "rounds": args.rounds, "warmup": args.warmup, "hipgraph": True, "sub_batch_streams": model.sub_batches}
@@ -114,6 +121,9 @@ def run_config(idx, args, device):
     res["speedup_bf16_over_fp32"] = res["bf16"]["frames_per_s"] / res["fp32"]["frames_per_s"]
     res["bf16_vs_fp32_outputs"] = accuracy(outs["bf16"], outs["fp32"])
     res["bf16_repeat_bit_identical"] = all(torch.equal(a, b) for a, b in zip(outs["bf16"], again))
+    if "bf16_tail" in outs:
+        res["speedup_bf16_tail_over_bf16"] = res["bf16_tail"]["frames_per_s"] / res["bf16"]["frames_per_s"]
+        res["bf16_tail_vs_fp32_outputs"] = accuracy(outs["bf16_tail"], outs["fp32"])
     return res
 
 
@@ -124,6 +134,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=6, help="alternating fp32 / bf16 rounds")
     ap.add_argument("--warmup", type=int, default=3, help="replays per precision before timing (after the capture)")
     ap.add_argument("--only", choices=("fp32", "bf16"), default=None, help="run one precision eagerly (profiling)")
+    ap.add_argument("--bf16-tail", action="store_true",
+                    help="also time bf16 with the decoder's bf16_tail_convs switch on (a third graph in the same alternation)")
     ap.add_argument("--out", default=None, help="also write the JSON document here")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bf16_bench.py needs a GPU"
