@@ -24,6 +24,7 @@ SYMBOLS = (
     "bts_conv_wgrad_batch_table_bytes", "bts_conv_wgrad_batch_plan_f32", "bts_conv_wgrad_batch_f32",
     "bts_adamw_table_bytes", "bts_adamw_flat_span", "bts_adamw_plan_f32", "bts_adamw_step_f32",
     "bts_upconv_up9_fwd_f32", "bts_upconv_up9_plan", "bts_conv_tail_bf16_fwd_f32", "bts_conv_tail_bf16_plan",
+    "bts_conv_tail_wino_fwd_f32", "bts_conv_tail_wino_plan",
     "bts_upconv_dgrad_f32", "bts_upconv_dgrad_plan", "bts_upconv_wgrad_f32", "bts_upconv_wgrad_plan_f32",
     "bts_upconv_train_pack_blocks", "bts_upconv_train_pack_f32",
 )
@@ -228,6 +229,10 @@ def load_real():
     lib.bts_conv_tail_bf16_fwd_f32.argtypes = [vp, l, i, i, i, i, vp, vp, vp, i, i, i, vp, vp, i, vp, l, vp]
     lib.bts_conv_tail_bf16_plan.restype = i
     lib.bts_conv_tail_bf16_plan.argtypes = [i, i, i, i, i, i, C.POINTER(C.c_int), C.POINTER(C.c_long)]
+    lib.bts_conv_tail_wino_fwd_f32.restype = i
+    lib.bts_conv_tail_wino_fwd_f32.argtypes = [vp, l, i, i, i, i, vp, vp, vp, vp, vp, vp, i, i, i, vp, vp]
+    lib.bts_conv_tail_wino_plan.restype = i
+    lib.bts_conv_tail_wino_plan.argtypes = [i, i, i, i, i, i, i, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_long)]
     lib.bts_upconv_dgrad_f32.restype = i
     lib.bts_upconv_dgrad_f32.argtypes = [vp, l, i, i, i, i, vp, i, vp, l, i, i, vp, l, vp]
     lib.bts_upconv_dgrad_plan.restype = i

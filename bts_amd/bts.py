@@ -398,6 +398,7 @@ class bts(nn.Module):
                                                         # the depth plane added in fp32 (ops.conv_tail_bf16_forward),
                                                         # where the library's plan query takes the layer
         self._packs_tail_bf16 = PackCache(self)
+        self._packs_conv1_wino = PackCache(self)
 
     # ------------------------------------------------------------------ weight packing (lazy)
     _OWN = ("bn5", "conv5", "bn4", "conv4", "bn4_2", "daspp_conv", "bn3", "conv3", "bn2", "conv2", "conv1", "get_depth")
@@ -418,6 +419,18 @@ class bts(nn.Module):
             return out
         return self._packs_tail_bf16.get(self.conv3[0].weight.device, build,
                                          key_modules=lambda origin: [origin.conv3, origin.conv2])
+
+    # conv1 (32 features + four depth planes -> 32 channels at full resolution) takes the fused Winograd F(2x2,3x3) kernel
+    # with its planar tail in direct form (16 products per 2x2 window and channel pair instead of 36) where the library's
+    # plan query says so: fp32, bts_size 512's 32 -> 32 shape, a well-filled tile grid and a chip-filling declared launch
+    # (ops.conv_tail_wino_plan).  False (or BTS_CONV1_WINO=0) keeps it on the halo kernel (A/B)
+    conv1_wino = os.environ.get("BTS_CONV1_WINO", "1").strip() not in ("", "0")
+
+    def packed_conv1_wino(self):
+        """(u, w_tail): conv1's weight as ops.pack_conv_tail_wino lays it out, made once per weight and device."""
+        return self._packs_conv1_wino.get(self.conv1[0].weight.device,
+                                          lambda: ops.pack_conv_tail_wino(self.conv1[0].weight.detach(), 4),
+                                          key_modules=lambda origin: [origin.conv1])
 
     def _build_pack(self):
         nf = self.num_features
@@ -625,8 +638,12 @@ class bts(nn.Module):
         self.reduc1x1.run_nhwc(c1, reduc1x1, False)
         iconv1 = out_tensor(5, n16c)
         # concat1 = cat[upconv1, reduc1x1, depth_2x2, depth_4x4, depth_8x8] (bts.py:287): the four maps are read in place
-        conv("conv1", c1, H, W, n16c, y_nchw=iconv1, c_in_real=n16c + 4,
-             tail=[reduc1x1, depth_2x2_scaled, depth_4x4_scaled, depth_8x8_scaled])
+        planes1 = [reduc1x1, depth_2x2_scaled, depth_4x4_scaled, depth_8x8_scaled]
+        if self.conv1_wino and n16c == 32 and c1.shape[1] == 32 and ops.conv_tail_wino_plan(H, W, 32, n16c, 4).eligible:
+            u1, wt1 = self.packed_conv1_wino()
+            ops.conv_tail_wino_forward(c1, B, H, W, u1, wt1, planes1, iconv1, act=ELU)
+        else:
+            conv("conv1", c1, H, W, n16c, y_nchw=iconv1, c_in_real=n16c + 4, tail=planes1)
         fo = None
         if self.params.dataset == 'kitti':
             fo = focal.to(device=dev, dtype=torch.float32).reshape(-1).contiguous()

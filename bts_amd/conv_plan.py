@@ -60,6 +60,11 @@ def kernel_name(plan: Plan, nchw: bool, subpixel: bool) -> str:
     return {Family.STEM: "conv_stem_kernel<%d>", Family.WINO: "conv_wino_kernel<%d>"}[f] % plan.bn
 
 
+def tail_wino_kernel_name() -> str:
+    """The kernel bts_conv_tail_wino_fwd_f32 launches (its own entry point: no bts_conv_plan_f32 kind), as KernelTrace records it."""
+    return "conv_wino_tail_kernel<32>"
+
+
 def tail_bf16_kernel_name(bn: int) -> str:
     """The kernel bts_conv_tail_bf16_fwd_f32 launches (its own entry point: no bts_conv_plan_f32 kind), as KernelTrace records it."""
     return "conv_tail_bf16_kernel<%d>" % bn

@@ -787,6 +787,7 @@ thread_local ConvChoice* g_dry = nullptr;
 #include "conv_halo_emu.inc"
 #include "conv_wino.inc"
 #include "conv_up9.inc"
+#include "conv_wino_tail.inc"
 #include "conv_tail_bf16.inc"
 #include "conv_1x1.inc"
 #include "conv_stem.inc"
@@ -1245,6 +1246,46 @@ extern "C" int bts_conv_tail_bf16_fwd_f32(const float* x, long x_pix_stride, int
     a.c_out = c_out; a.c_out_pad = c_out_pad; a.e2_scale = e2_scale; a.e2_shift = e2_shift; a.act = act;
     a.y = y; a.y_pix_stride = y_pix_stride; a.n_ntiles = 0;
     return tail_bf16_bn(c_out) == 128 ? launch_tail_bf16<128>(a, (hipStream_t)stream) : launch_tail_bf16<64>(a, (hipStream_t)stream);
+}
+
+// ---- conv1 (32 features + planar tail -> 32, NCHW) as a fused Winograd F(2x2,3x3) kernel (conv_wino_tail.inc): its own opt-in
+//      entry point and plan query, so that bts_conv_fwd_f32 / bts_conv_plan_f32 answer for every descriptor exactly as before
+extern "C" int bts_conv_tail_wino_plan(int h, int w, int c_main, int c_out, int n_tail, int precision, int fill_frames, int* bm,
+                                       int* bn, long* workgroups) {
+    if (!bm || !bn || !workgroups) return BTS_ERR_INVALID;
+    if (fill_frames < 0 || fill_frames > 4096) return BTS_ERR_INVALID;
+    const int prec_env = knobs().precision;
+    long wgs = 0;
+    const bool ok = wino_tail_eligible(h, w, c_main, c_out, n_tail, prec_env >= 0 ? prec_env : precision,
+                                       fill_frames > 0 ? fill_frames : knobs().fill_frames, &wgs);
+    *bm = ok ? WT_WY * WT_WX : 0; *bn = ok ? 32 : 0; *workgroups = ok ? wgs : 0;
+    return 0;
+}
+
+extern "C" int bts_conv_tail_wino_fwd_f32(const float* x, long x_pix_stride, int B, int h, int w, int c_main, const float* u,
+                                          const float* w_tail, const float* tail0, const float* tail1, const float* tail2,
+                                          const float* tail3, int n_tail, int c_out, int act, float* y, bts_stream_t stream) {
+    if (!x || !u || !w_tail || !y || B <= 0 || h <= 0 || w <= 0 || c_main <= 0 || c_out <= 0) return BTS_ERR_INVALID;
+    if (n_tail < 0 || n_tail > 4 || act < 0 || act > 2) return BTS_ERR_INVALID;
+    if (c_main != 32 || c_out != 32) return BTS_ERR_UNSUPPORTED;
+    if ((x_pix_stride & 3) || x_pix_stride < c_main) return BTS_ERR_INVALID;
+    if (((uintptr_t)x & 15) || ((uintptr_t)u & 15) || ((uintptr_t)w_tail & 3) || ((uintptr_t)y & 7)) return BTS_ERR_INVALID;
+    const float* const planes[4] = {tail0, tail1, tail2, tail3};
+    for (int j = 0; j < n_tail; ++j)
+        if (!planes[j] || ((uintptr_t)planes[j] & 3)) return BTS_ERR_INVALID;
+    // the kernel addresses x and the planes with 32-bit element offsets and decodes tiles with 32-bit arithmetic
+    if ((double)B * h * w * (double)x_pix_stride >= 4294967296.0 || (double)B * h * w >= 2147483648.0) return BTS_ERR_UNSUPPORTED;
+    WinoTailArgs a;
+    a.x = x; a.x_pix_stride = x_pix_stride; a.B = B; a.H = h; a.W = w;
+    a.u = u; a.w_tail = w_tail; a.n_tail = n_tail; a.act = act; a.y = y;
+    for (int j = 0; j < 4; ++j) a.tail[j] = j < n_tail ? planes[j] : x;      // absent: any readable address, the lanes load zeros
+    double fill;
+    wino_tail_grid(h, w, &a.n_ty, &a.n_tx, &fill);
+    const long nwg = (long)B * a.n_ty * a.n_tx;
+    if (nwg > 0x7fffffffL) return BTS_ERR_UNSUPPORTED;
+    a.ntiles = (int)nwg;
+    hipLaunchKernelGGL(conv_wino_tail_kernel<32>, dim3((unsigned)nwg), dim3(256), 0, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
 }
 
 // ---- input gradient of the sub-pixel upconv (training): one 4x4 / stride-2 / padding-1 convolution over dy at its natural

@@ -90,6 +90,12 @@ extern "C" int bts_plan_run(bts_op* ops, int n_ops, const bts_plan_patch* patche
                                                 a.c_out, a.c_out_pad, a.e2_scale, a.e2_shift, a.act, a.y, a.y_pix_stride, stream);
                 break;
             }
+            case BTS_OP_CONV_TAIL_WINO: {
+                auto& a = o.u.conv_tail_wino;
+                rc = bts_conv_tail_wino_fwd_f32(a.x, a.x_pix_stride, a.B, a.h, a.w, a.c_main, a.u, a.w_tail, a.tail0, a.tail1, a.tail2,
+                                                a.tail3, a.n_tail, a.c_out, a.act, a.y, stream);
+                break;
+            }
             default: rc = BTS_ERR_INVALID;
         }
         o.failed_code = rc;

@@ -1173,6 +1173,149 @@ def conv_tail_bf16_forward(x2d: torch.Tensor, B: int, h: int, w: int, w_main: to
     return y2d
 
 
+# ---- conv1 (32 features + planar tail -> 32 channels, NCHW) as a fused Winograd F(2x2,3x3) kernel (csrc/conv_wino_tail.inc)
+_WINO_G = ((1.0, 0.0, 0.0), (0.5, 0.5, 0.5), (0.5, -0.5, 0.5), (0.0, 0.0, 1.0))
+_WINO_BT = ((1.0, 0.0, -1.0, 0.0), (0.0, 1.0, 1.0, 0.0), (0.0, -1.0, 1.0, 0.0), (0.0, 1.0, 0.0, -1.0))
+_WINO_AT = ((1.0, 1.0, 1.0, 0.0), (0.0, 1.0, -1.0, -1.0))
+
+
+def _conv_tail_wino_split(weight_oihw: torch.Tensor, n_tail: int):
+    if (weight_oihw.dim() != 4 or tuple(weight_oihw.shape[2:]) != (3, 3) or not 0 <= n_tail <= 4 or weight_oihw.shape[0] != 32
+            or weight_oihw.shape[1] != 32 + n_tail):
+        raise BtsHipError("pack_conv_tail_wino: needs a [32, 32 + n_tail, 3, 3] weight and 0..4 tail planes")
+    wf = weight_oihw.detach()
+    return wf[:, :32], wf[:, 32:]
+
+
+def _conv_tail_wino_order(U: torch.Tensor, wt: torch.Tensor, n_tail: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """U [n, c, 4, 4] fp32, wt [n, n_tail, 3, 3] -> the two flat fragment orders of include/bts_hip.h."""
+    u = U.reshape(2, 16, 2, 4, 4, 16)                                   # (cb, lw, half, lg, q, xi)
+    u = u.permute(5, 0, 2, 3, 1, 4).contiguous().view(-1)               # (xi, cb, half, lg, lw, q): lane = 16 lg + lw
+    t = torch.zeros((32, 9, 4), dtype=torch.float32, device=U.device)   # [n, tap, j]
+    t[:, :, :n_tail] = wt.float().permute(0, 2, 3, 1).reshape(32, 9, n_tail)
+    t = t.reshape(2, 16, 9, 4).permute(0, 2, 3, 1).contiguous().view(-1)       # (cb, tap, lg = j, lw)
+    return u, t
+
+
+def pack_conv_tail_wino(weight_oihw: torch.Tensor, n_tail: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """[32, 32 + n_tail, 3, 3] -> (u, w_tail) as bts_conv_tail_wino_fwd_f32 reads them (include/bts_hip.h): u = the 32
+    main channels in Winograd F(2x2,3x3) form, U = G g G^T computed in fp64 and rounded once, in MFMA A-fragment order
+    (16 * 32 * 32 floats); w_tail = the tail weights bit for bit in their fragment order (2 * 9 * 64 floats, unused
+    slots zero).  Once per weight (inference weights are constant; bts.packed_conv1_wino caches it)."""
+    g, wt = _conv_tail_wino_split(weight_oihw, n_tail)
+    G = torch.tensor(_WINO_G, dtype=torch.float64, device=g.device)
+    U = (G @ g.double() @ G.t()).float()                                # [n, c, 4, 4], one rounding
+    return _conv_tail_wino_order(U, wt, n_tail)
+
+
+def pack_conv_tail_wino_reference(weight_oihw: torch.Tensor, n_tail: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Element-by-element fp64 statement of pack_conv_tail_wino, kept as its test oracle: U[n][c][a][b] =
+    sum_{i,j} G[a][i] g[n][c][i][j] G[b][j], written into the documented float indices one by one."""
+    g, wt = _conv_tail_wino_split(weight_oihw, n_tail)
+    G = torch.tensor(_WINO_G, dtype=torch.float64)
+    U = torch.einsum("ai,ncij,bj->ncab", G, g.double().cpu(), G).float()
+    u = torch.zeros(16 * 32 * 32, dtype=torch.float32)
+    t = torch.zeros(2 * 9 * 64, dtype=torch.float32)
+    idx = torch.arange(16 * 32 * 32)
+    q, lane, half, cb, xi = idx % 4, (idx // 4) % 64, (idx // 256) % 2, (idx // 512) % 2, idx // 1024
+    u[idx] = U[16 * cb + (lane % 16), 16 * half + 4 * (lane // 16) + q, xi // 4, xi % 4]
+    wtc = wt.float().cpu()
+    for cb_ in range(2):
+        for tap in range(9):
+            for ln in range(64):
+                if ln // 16 < n_tail:
+                    t[(cb_ * 9 + tap) * 64 + ln] = wtc[16 * cb_ + ln % 16, ln // 16, tap // 3, tap % 3]
+    return u.to(weight_oihw.device), t.to(weight_oihw.device)
+
+
+def conv_tail_wino_reference(x: torch.Tensor, planes: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """The formulation itself in torch (any dtype, CPU or GPU), window by window as the kernel does it: x [B, c, H, W],
+    planes [B, n_tail, H, W], w [n, c + n_tail, 3, 3] -> conv3x3([x | planes]) [B, n, H, W] with the c main channels in
+    F(2x2,3x3) form and the tail in direct form.  Test oracle of the identity, not a product path."""
+    B, c, H, W = x.shape
+    n = w.shape[0]
+    dt, dev = x.dtype, x.device
+    G, Bt, At = (torch.tensor(m, dtype=dt, device=dev) for m in (_WINO_G, _WINO_BT, _WINO_AT))
+    nwy, nwx = (H + 1) // 2, (W + 1) // 2
+    xp = F.pad(x, (1, 2 * nwx + 1 - W, 1, 2 * nwy + 1 - H))                          # rows -1 .. 2 nwy
+    d = xp.unfold(2, 4, 2).unfold(3, 4, 2)                                           # [B, c, nwy, nwx, 4, 4]
+    V = torch.einsum("ar,bkyxrc,ec->bkyxae", Bt, d, Bt)
+    U = torch.einsum("ai,nkij,bj->nkab", G, w[:, :c].to(dt), G)
+    M = torch.einsum("bkyxae,nkae->bnyxae", V, U)
+    Y = torch.einsum("ia,bnyxae,je->bnyixj", At, M, At)                              # [B, n, wy, 2, wx, 2]
+    out = Y.reshape(B, n, 2 * nwy, 2 * nwx)[:, :, :H, :W].clone()
+    if planes is not None and planes.shape[1] > 0:
+        out += F.conv2d(planes.to(dt), w[:, c:].to(dt), padding=1)
+    return out.contiguous()
+
+
+class TailWinoPlan(tuple):
+    """(bm, bn, workgroups per frame) of bts_conv_tail_wino_plan; all 0 = the layer stays on bts_conv_fwd_f32."""
+    bm = property(lambda self: self[0])
+    bn = property(lambda self: self[1])
+    workgroups = property(lambda self: self[2])
+    eligible = property(lambda self: self[0] > 0)
+
+
+def conv_tail_wino_plan(h: int, w: int, c_main: int, c_out: int, n_tail: int = 4, precision=None,
+                        fill_frames: Optional[int] = None) -> TailWinoPlan:
+    """Should this planar-tail layer take conv_tail_wino_forward?  Host-only query (bts_conv_tail_wino_plan);
+    ``precision`` / ``fill_frames`` default to the launch_config in force."""
+    ff, pr = current_launch_config()
+    if precision is not None:
+        if precision not in _PRECISIONS:
+            raise BtsHipError("conv_tail_wino_plan: precision must be 'fp32' / 0, 'bf16x3' / 1 or 'bf16' / 2")
+        pr = _PRECISIONS[precision]
+    if fill_frames is not None:
+        ff = int(fill_frames)
+    bm, bn, wgs = C.c_int(0), C.c_int(0), C.c_long(0)
+    _lib.check(_lib.load_real().bts_conv_tail_wino_plan(int(h), int(w), int(c_main), int(c_out), int(n_tail), int(pr), int(ff),
+                                                         C.byref(bm), C.byref(bn), C.byref(wgs)), "bts_conv_tail_wino_plan")
+    return TailWinoPlan((bm.value, bn.value, wgs.value))
+
+
+def conv_tail_wino_forward(x2d: torch.Tensor, B: int, h: int, w: int, u: torch.Tensor, w_tail: torch.Tensor,
+                           tail_planes: Optional[Sequence[torch.Tensor]], y_nchw: torch.Tensor, act: int = ACT_ELU,
+                           tag: str = "decoder_conv"):
+    """act(conv3x3([x | planes])) in one launch of the fused Winograd kernel (bts_conv_tail_wino_fwd_f32): x2d
+    [B*h*w, >= 32] NHWC view (32 channels read), (u, w_tail) from pack_conv_tail_wino, tail_planes 0..4 contiguous
+    [B,h,w] (or [B,1,h,w]) maps, y_nchw contiguous [B,32,h,w].  Runs whatever the plan query says: callers ask
+    conv_tail_wino_plan first."""
+    name = "conv_tail_wino_forward"
+    xs, xc = _rows2d(x2d, name)
+    _need(u, name)
+    _need(w_tail, name)
+    _need(y_nchw, name)
+    planes = list(tail_planes) if tail_planes else []
+    if xc < 32 or x2d.shape[0] != B * h * w or tuple(y_nchw.shape) != (B, 32, h, w) or not y_nchw.is_contiguous():
+        raise BtsHipError("conv_tail_wino_forward: views %s / %s do not fit B=%d %dx%d, 32 -> 32 channels (NCHW result)"
+                          % (tuple(x2d.shape), tuple(y_nchw.shape), B, h, w))
+    if u.numel() != 16 * 32 * 32 or not u.is_contiguous() or w_tail.numel() != 2 * 9 * 64 or not w_tail.is_contiguous():
+        raise BtsHipError("conv_tail_wino_forward: (u, w_tail) must come from pack_conv_tail_wino")
+    if len(planes) > 4:
+        raise BtsHipError("conv_tail_wino_forward: at most four tail planes")
+    for t in planes:
+        _need(t, name)
+        if t.numel() != B * h * w or not t.is_contiguous():
+            raise BtsHipError("conv_tail_wino_forward: every tail plane must be one contiguous map of B*h*w floats")
+    if act not in (ACT_NONE, ACT_RELU, ACT_ELU):
+        raise BtsHipError("conv_tail_wino_forward: act must be none, ReLU or ELU")
+    kern, flops, nbytes, xflops = "conv", 0.0, 0.0, None
+    if _trace is not None:
+        kern = conv_plan.tail_wino_kernel_name()
+        flops = 2.0 * 9 * B * h * w * 32 * (32 + len(planes))                       # the reference's direct 3x3
+        nbytes = 4.0 * (B * h * w * (32 + len(planes) + 32) + 9 * 32 * (32 + len(planes)))
+        windows = B * ((h + 3) // 4) * ((w + 31) // 32) * 32                        # ragged tiles included
+        xflops = 2.0 * windows * 32 * (16 * 32 + 36 * 4)                            # 16 products per window (main) + the direct tail's k-step of 4
+    ptrs = [_ptr(planes[j]) if j < len(planes) else C.c_void_p(0) for j in range(4)]
+    run = lambda: _lib.load().bts_conv_tail_wino_fwd_f32(_ptr(x2d), xs, B, h, w, 32, _ptr(u), _ptr(w_tail), ptrs[0], ptrs[1], ptrs[2],
+                                                         ptrs[3], len(planes), 32, int(act), _ptr(y_nchw), _stream(x2d))
+    with torch.cuda.device(x2d.device):
+        rc = _launch(kern, tag, flops, nbytes, run, xflops=xflops)
+    _lib.check(rc, "bts_conv_tail_wino_fwd_f32")
+    return y_nchw
+
+
 def pad_vec(v: Optional[torch.Tensor], n: int, fill: float = 0.0) -> Optional[torch.Tensor]:
     if v is None:
         return None

@@ -39,6 +39,7 @@ _KINDS = {
     "bts_upconv_combine_f32": (11, "upconv_combine"),
     "bts_upconv_up9_fwd_f32": (12, "upconv_up9"),
     "bts_conv_tail_bf16_fwd_f32": (13, "conv_tail_bf16"),
+    "bts_conv_tail_wino_fwd_f32": (14, "conv_tail_wino"),
 }
 
 _structs: Dict[str, type] = {}
@@ -108,7 +109,7 @@ class _Proxy:
                                                   "bts_conv_wgrad_plan_f32", "bts_conv_wgrad_batch_table_bytes",
                                                   "bts_conv_wgrad_batch_plan_f32", "bts_eval_ws_doubles", "bts_bn_train_ws_floats", "bts_pack_weights_blocks",
                                                   "bts_depth_loss_ws_doubles", "bts_adamw_table_bytes", "bts_adamw_flat_span",
-                                                  "bts_adamw_plan_f32", "bts_upconv_up9_plan", "bts_conv_tail_bf16_plan", "bts_upconv_dgrad_plan",
+                                                  "bts_adamw_plan_f32", "bts_upconv_up9_plan", "bts_conv_tail_bf16_plan", "bts_conv_tail_wino_plan", "bts_upconv_dgrad_plan",
                                                   "bts_upconv_wgrad_plan_f32", "bts_upconv_train_pack_blocks"):
             return real
         if name not in _KINDS:
@@ -219,8 +220,9 @@ class PlanCache:
         fp = (workspace._generation[0], workspace.tensor_fingerprint(origin))
         # the launch declaration in force (fill_frames, precision) is baked into every recorded descriptor
         # ... and so is the decoder's choice of kernel for conv3 / conv2 (bts.bf16_tail_convs)
+        # ... and of kernel for conv1 (bts.conv1_wino)
         key = (tuple(x.shape), str(dev), slot, has_focal, stream, ops_mod.current_launch_config(),
-               bool(getattr(model.decoder, "bf16_tail_convs", False)))
+               bool(getattr(model.decoder, "bf16_tail_convs", False)), bool(getattr(model.decoder, "conv1_wino", False)))
         entry = self._plans.get(key)
         if entry is not None and entry[1] != fp:
             with self._lock:

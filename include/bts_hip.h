@@ -310,6 +310,39 @@ int bts_conv_tail_bf16_fwd_f32(const float* x, long x_pix_stride, int B, int h, 
  *   both 0 when the layer should stay on bts_conv_fwd_f32's fp32 tail kernel. */
 int bts_conv_tail_bf16_plan(int h, int w, int c_main, int c_out, int n_tail, int fill_frames, int* bn, long* workgroups);
 
+/* The decoder's full-resolution planar-tail 3x3 convolution (conv1: stride 1, padding 1, 32 NHWC feature channels plus up to
+ * four dense depth planes in, 32 channels out, activation, NCHW result) in one launch of a fused Winograd F(2x2,3x3) kernel
+ * (csrc/conv_wino_tail.inc):
+ *   y[b][n][Y][X] = act( sum_{tap, c < 32} x[b][Y+dy][X+dx][c] * w[n][c][tap]
+ *                      + sum_{tap, j < n_tail} plane_j[b][Y+dy][X+dx] * w_tail[n][tap][j] ),   tap = 3 (dy+1) + (dx+1)
+ * zero padding, stride 1, no affine stage.  MAIN term: Winograd F(2x2,3x3) with exact fp32 MFMA products, 16 per 2x2
+ * output window and channel pair instead of 36; U = G g G^T is made offline in fp64 and rounded once.  TAIL term: DIRECT
+ * form (36 MFMAs of one k-step), added after the output transform: a non-finite plane value reaches exactly the outputs
+ * whose nine taps touch it; a non-finite x value may spread over its 4x4 window.  Opt-in: bts_conv_fwd_f32 never takes
+ * this path on its own.
+ *   x      : NHWC [B,h,w], x_pix_stride >= 32 floats per pixel (a multiple of 4), 16-byte aligned
+ *   u      : 16 * 32 * 32 floats, 16-byte aligned, in MFMA A-fragment order (bts_amd/ops.py:pack_conv_tail_wino):
+ *            float index ((((xi * 2 + cb) * 2 + half) * 64 + lane) * 4 + q
+ *            = U[xi = 4 a + b][n = 16 cb + (lane & 15)][c = 16 half + 4 (lane >> 4) + q],  U[.][n][c] = G w[n][c] G^T,
+ *            G = [[1,0,0],[1/2,1/2,1/2],[1/2,-1/2,1/2],[0,0,1]]
+ *   w_tail : 2 * 9 * 64 floats: index (cb * 9 + tap) * 64 + lane = w_tail[n = 16 cb + (lane & 15)][tap][j = lane >> 4],
+ *            the tail weights bit for bit, slots j >= n_tail zero
+ *   tail0..3 : dense fp32 planes [B,h,w], 4-byte aligned; the first n_tail (0..4) are read, the others ignored (may be NULL):
+ *            an absent plane contributes exact zeros
+ *   y      : contiguous NCHW [B,32,h,w], 8-byte aligned;  act 0 none / 1 ReLU / 2 ELU
+ * c_main != 32 or c_out != 32: BTS_ERR_UNSUPPORTED.  Sum order fixed: a frame's bits depend neither on B nor on fill_frames. */
+int bts_conv_tail_wino_fwd_f32(const float* x, long x_pix_stride, int B, int h, int w, int c_main, const float* u,
+                               const float* w_tail, const float* tail0, const float* tail1, const float* tail2,
+                               const float* tail3, int n_tail, int c_out, int act, float* y, bts_stream_t stream);
+
+/* Should a layer take bts_conv_tail_wino_fwd_f32 (host-side query, no GPU work, no pointers)?  Eligible: precision 0,
+ * c_main == 32, c_out == 32, n_tail 0..4, a grid of 4x32-pixel workgroup tiles that is at least 0.70 real pixels, and a
+ * declared launch (fill_frames as in bts_conv_desc, 0 = the library default; never B) of at least 2048 workgroups.
+ *   *bm = windows per workgroup (32), *bn = output channels per workgroup (32), *workgroups = workgroups PER FRAME;
+ *   all three 0 when the layer should stay on bts_conv_fwd_f32. */
+int bts_conv_tail_wino_plan(int h, int w, int c_main, int c_out, int n_tail, int precision, int fill_frames, int* bm, int* bn,
+                            long* workgroups);
+
 /* Which kernel bts_conv_fwd_f32 will launch for this descriptor (host-side query, no GPU work: it walks the real
  * dispatch path): lets a profiler attribute a launch to its kernel instantiation.
  *   *kind = one kernel family (kind & BTS_CONV_KIND_MASK) plus any of the BTS_CONV_FLAG_* bits. */
@@ -704,7 +737,8 @@ int  bts_adamw_step_f32(const void* table_dev, int n, long total_blocks, const b
  */
 enum { BTS_OP_CONV = 1, BTS_OP_REDUC = 2, BTS_OP_REDUC_LPG = 3, BTS_OP_LPG_FUSED = 4, BTS_OP_NCHW_TO_NHWC = 5,
        BTS_OP_NHWC_TO_NCHW = 6, BTS_OP_MAXPOOL = 7, BTS_OP_BN_RELU_AVGPOOL = 8, BTS_OP_GET_DEPTH = 9, BTS_OP_LPG = 10,
-       BTS_OP_UPCONV_COMBINE = 11, BTS_OP_UPCONV_UP9 = 12, BTS_OP_CONV_TAIL_BF16 = 13 };
+       BTS_OP_UPCONV_COMBINE = 11, BTS_OP_UPCONV_UP9 = 12, BTS_OP_CONV_TAIL_BF16 = 13,
+       BTS_OP_CONV_TAIL_WINO = 14 };
 
 typedef struct bts_op {
     int kind;          /* BTS_OP_*                                                              */
@@ -733,6 +767,8 @@ typedef struct bts_op {
         struct { const float* x; long x_pix_stride; int B, h, w, c_main; const void* w_main; const float* w_tail;
                  const float* tail_plane; int n_tail, c_out, c_out_pad; const float* e2_scale; const float* e2_shift; int act;
                  float* y; long y_pix_stride; } conv_tail_bf16;
+        struct { const float* x; long x_pix_stride; int B, h, w, c_main; const float* u; const float* w_tail; const float* tail0;
+                 const float* tail1; const float* tail2; const float* tail3; int n_tail, c_out, act; float* y; } conv_tail_wino;
     } u;
 } bts_op;
 
