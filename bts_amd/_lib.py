@@ -8,26 +8,10 @@ from __future__ import annotations
 import ctypes as C
 import os
 import threading
+from typing import Any, Dict, NamedTuple, Optional, Tuple
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libbts_hip.so")
-
-SYMBOLS = (
-    "bts_hip_abi_version", "bts_hip_error_string", "bts_lpg_fwd_f32", "bts_lpg_bwd_f32", "bts_lpg_fused_fwd_f32",
-    "bts_reduc_fwd_f32", "bts_conv_fwd_f32", "bts_nchw_to_nhwc_f32", "bts_nhwc_to_nchw_f32",
-    "bts_pack_planes_f32", "bts_get_depth_f32", "bts_conv_plan_f32", "bts_conv_plan_ksteps_f32", "bts_maxpool3x3s2_nhwc_f32", "bts_bn_relu_avgpool2_nhwc_f32",
-    "bts_conv_wgrad_f32", "bts_conv_wgrad_plan_f32", "bts_bn_train_ws_floats", "bts_bn_train_stats_f32", "bts_bn_apply_nhwc_f32", "bts_bn_train_bwd_f32",
-    "bts_pack_weights_blocks", "bts_pack_weights_f32", "bts_pack_wino_floats", "bts_pack_wino_f32", "bts_eval_ws_doubles", "bts_eval_depth_metrics_f32",
-    "bts_reduc_lpg_fwd_f32", "bts_plan_run", "bts_upconv_combine_f32",
-    "bts_depth_loss_ws_doubles", "bts_depth_loss_fwd_f32", "bts_depth_loss_bwd_f32",
-    "bts_reduc_bwd_f32", "bts_reduc_bwd_max_waves",
-    "bts_conv_wgrad_batch_table_bytes", "bts_conv_wgrad_batch_plan_f32", "bts_conv_wgrad_batch_f32",
-    "bts_adamw_table_bytes", "bts_adamw_flat_span", "bts_adamw_plan_f32", "bts_adamw_step_f32",
-    "bts_upconv_up9_fwd_f32", "bts_upconv_up9_plan", "bts_conv_tail_bf16_fwd_f32", "bts_conv_tail_bf16_plan",
-    "bts_conv_tail_wino_fwd_f32", "bts_conv_tail_wino_plan",
-    "bts_upconv_dgrad_f32", "bts_upconv_dgrad_plan", "bts_upconv_wgrad_f32", "bts_upconv_wgrad_plan_f32",
-    "bts_upconv_train_pack_blocks", "bts_upconv_train_pack_f32",
-)
 
 ABI_VERSION = 17
 
@@ -88,6 +72,95 @@ class AdamwHyper(C.Structure):
 class AdamwPlanItem(C.Structure):
     """struct bts_adamw_plan_item (include/bts_hip.h)."""
     _fields_ = [("kind", C.c_int), ("reserved", C.c_int), ("first_block", C.c_long), ("n_blocks", C.c_long)]
+
+
+QUERY, LAUNCH = "query", "launch"
+
+
+class Entry(NamedTuple):
+    """One C entry point (include/bts_hip.h).  ``role``: QUERY = host arithmetic only, enqueues nothing; LAUNCH = enqueues
+    work on the stream passed as its last argument.  ``plan``: (BTS_OP_* kind, member of the bts_op union) when
+    bts_plan_run can replay it -- plan.hip and the header spell the same numbers."""
+    restype: Any
+    argtypes: tuple
+    role: str
+    plan: Optional[Tuple[int, str]] = None
+
+
+def _query(restype, *argtypes):
+    return Entry(restype, argtypes, QUERY)
+
+
+def _launch(*argtypes, plan=None):
+    return Entry(C.c_int, argtypes, LAUNCH, plan)
+
+
+_vp, _i, _l64, _f = C.c_void_p, C.c_int, C.c_long, C.c_float
+_pi, _pl, _pvp = C.POINTER(C.c_int), C.POINTER(C.c_long), C.POINTER(C.c_void_p)
+_conv, _wgrad = C.POINTER(ConvDesc), C.POINTER(ConvWgradDesc)
+
+# The whole C ABI, one row per entry point: a new one costs one row here (plus its header prototype, its C function, its
+# plan.hip case when replayable, and its wrapper).  Argument order = the C prototypes.
+ABI: Dict[str, Entry] = {
+    "bts_hip_abi_version": _query(_i),
+    "bts_hip_error_string": _query(C.c_char_p, _i),
+    "bts_lpg_fwd_f32": _launch(_vp, _i, _i, _i, _i, _vp, _vp, _vp, plan=(10, "lpg")),
+    "bts_lpg_bwd_f32": _launch(_vp, _vp, _i, _i, _i, _i, _vp, _vp),
+    "bts_lpg_fused_fwd_f32": _launch(_vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _i, _l64, _vp, _vp, plan=(4, "lpg_fused")),
+    "bts_reduc_fwd_f32": _launch(_vp, _l64, _l64, _i, _i, _vp, _l64, _f, _i, _i, _vp, _vp, plan=(2, "reduc")),
+    "bts_reduc_lpg_fwd_f32": _launch(_vp, _l64, _i, _i, _i, _i, _i, _vp, _l64, _f, _i, _vp, _vp, _vp, _vp, _vp, plan=(3, "reduc_lpg")),
+    "bts_reduc_bwd_f32": _launch(_vp, _l64, _i, _i, _i, _i, _i, _vp, _l64, _vp, _l64, _f, _i, _vp, _vp, _l64, _vp, _vp, _vp),
+    "bts_reduc_bwd_max_waves": _query(_l64, _i, _i, _i),
+    "bts_conv_fwd_f32": _launch(_conv, _vp, plan=(1, "conv")),
+    "bts_upconv_combine_f32": _launch(_vp, _l64, _i, _i, _i, _i, _vp, _vp, _i, _vp, _l64, _vp, plan=(11, "upconv_combine")),
+    "bts_upconv_up9_fwd_f32": _launch(_vp, _l64, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _l64, _vp, plan=(12, "upconv_up9")),
+    "bts_upconv_up9_plan": _query(_i, _i, _i, _i, _i, _i, _i, _pi, _pi, _pl),
+    "bts_conv_tail_bf16_fwd_f32": _launch(_vp, _l64, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _l64, _vp,
+                                          plan=(13, "conv_tail_bf16")),
+    "bts_conv_tail_bf16_plan": _query(_i, _i, _i, _i, _i, _i, _i, _pi, _pl),
+    "bts_conv_tail_wino_fwd_f32": _launch(_vp, _l64, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp,
+                                          plan=(14, "conv_tail_wino")),
+    "bts_conv_tail_wino_plan": _query(_i, _i, _i, _i, _i, _i, _i, _i, _pi, _pi, _pl),
+    "bts_conv_plan_f32": _query(_i, _conv, _pi, _pi, _pi),
+    "bts_conv_plan_ksteps_f32": _query(_i, _conv, _pl, _pl),
+    "bts_conv_wgrad_f32": _launch(_wgrad, _vp),
+    "bts_conv_wgrad_plan_f32": _query(_i, _wgrad, _pi, _pi, _pl, _pl),
+    "bts_conv_wgrad_batch_table_bytes": _query(_l64, _i),
+    "bts_conv_wgrad_batch_plan_f32": _query(_i, _wgrad, _i, _pvp, _pl, _i, _l64, _vp, C.POINTER(ConvWgradBatchItem)),
+    "bts_conv_wgrad_batch_f32": _launch(_vp, _vp, _i, _pvp, _i, _vp, _vp),
+    "bts_upconv_dgrad_f32": _launch(_vp, _l64, _i, _i, _i, _i, _vp, _i, _vp, _l64, _i, _i, _vp, _l64, _vp),
+    "bts_upconv_dgrad_plan": _query(_i, _i, _i, _i, _i, _i, _i, _i, _l64, _pi, _pi, _pi),
+    "bts_upconv_wgrad_f32": _launch(_vp, _l64, _i, _i, _i, _i, _vp, _l64, _i, _vp, _vp, _l64, _vp),
+    "bts_upconv_wgrad_plan_f32": _query(_i, _i, _i, _i, _i, _i, _l64, _pi, _pi, _pl, _pl),
+    "bts_upconv_train_pack_blocks": _query(_l64, _l64, _l64, _l64, _l64),
+    "bts_upconv_train_pack_f32": _launch(_vp, _i, _l64, _vp),
+    "bts_pack_weights_blocks": _query(_l64, _l64, _l64),
+    "bts_pack_weights_f32": _launch(_vp, _i, _l64, _vp),
+    "bts_pack_wino_floats": _query(_l64, _i, _i, _i, _i),
+    "bts_pack_wino_f32": _launch(_vp, _i, _l64, _i, _i, _i, _vp, _vp),
+    "bts_bn_train_ws_floats": _query(_l64, _l64, _i),
+    "bts_bn_train_stats_f32": _launch(_vp, _l64, _l64, _i, _vp, _vp, _f, _f, _vp, _vp, _vp, _l64, _vp, _vp, _vp, _vp, _vp),
+    "bts_bn_apply_nhwc_f32": _launch(_vp, _l64, _l64, _i, _vp, _vp, _i, _vp, _l64, _vp),
+    "bts_bn_train_bwd_f32": _launch(_vp, _l64, _vp, _l64, _l64, _i, _vp, _vp, _vp, _vp, _i, _vp, _l64, _vp, _vp, _vp, _l64, _vp),
+    "bts_nchw_to_nhwc_f32": _launch(_vp, _i, _i, _l64, _vp, _l64, _i, _vp, plan=(5, "nchw_to_nhwc")),
+    "bts_nhwc_to_nchw_f32": _launch(_vp, _l64, _i, _i, _l64, _vp, _vp, plan=(6, "nhwc_to_nchw")),
+    "bts_pack_planes_f32": _launch(_vp, _vp, _vp, _vp, _i, _l64, _vp, _l64, _vp),
+    "bts_maxpool3x3s2_nhwc_f32": _launch(_vp, _l64, _i, _i, _i, _i, _vp, _l64, _vp, _l64, _vp, plan=(7, "maxpool")),
+    "bts_bn_relu_avgpool2_nhwc_f32": _launch(_vp, _l64, _i, _i, _i, _i, _vp, _vp, _vp, _l64, _vp, plan=(8, "avgpool")),
+    "bts_get_depth_f32": _launch(_vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, plan=(9, "get_depth")),
+    "bts_eval_ws_doubles": _query(_l64, _i, _i, _i),
+    "bts_eval_depth_metrics_f32": _launch(_vp, _i, _i, _i, _vp, _i, _i, _i, _i, _f, _f, _i, _i, _i, _i, _vp, _l64, _vp, _vp, _vp),
+    "bts_depth_loss_ws_doubles": _query(_l64, _l64),
+    "bts_depth_loss_fwd_f32": _launch(_vp, _vp, _vp, _f, _l64, _i, _f, _vp, _l64, _vp, _vp, _vp),
+    "bts_depth_loss_bwd_f32": _launch(_vp, _vp, _vp, _f, _l64, _i, _f, _vp, _vp, _vp, _vp),
+    "bts_adamw_table_bytes": _query(_l64, _i),
+    "bts_adamw_flat_span": _query(_l64),
+    "bts_adamw_plan_f32": _query(_i, _vp, _i, _vp, _pl, _vp),
+    "bts_adamw_step_f32": _launch(_vp, _i, _l64, _vp, _i, _vp, _vp),
+    # replays a recorded forward; bts_amd/plan.py refines these pointer types once it has built bts_op / bts_plan_patch
+    "bts_plan_run": _launch(_vp, _i, _vp, _i, _pvp, _i, _vp),
+}
+SYMBOLS = tuple(ABI)
 
 
 class BtsHipError(RuntimeError):
@@ -151,119 +224,11 @@ def load_real():
             "bts_amd: %s not found -- build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "or `make -C bts_amd/csrc`; there is no CPU/PyTorch fallback for the hot path" % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for s in SYMBOLS:
-        if not hasattr(lib, s):
-            raise BtsHipError("bts_amd: symbol %s missing from %s" % (s, LIB_PATH))
-    vp, i, l, f = C.c_void_p, C.c_int, C.c_long, C.c_float
-    lib.bts_hip_abi_version.restype = i
-    lib.bts_hip_abi_version.argtypes = []
-    lib.bts_hip_error_string.restype = C.c_char_p
-    lib.bts_hip_error_string.argtypes = [i]
-    lib.bts_lpg_fwd_f32.restype = i
-    lib.bts_lpg_fwd_f32.argtypes = [vp, i, i, i, i, vp, vp, vp]
-    lib.bts_lpg_bwd_f32.restype = i
-    lib.bts_lpg_bwd_f32.argtypes = [vp, vp, i, i, i, i, vp, vp]
-    lib.bts_lpg_fused_fwd_f32.restype = i
-    lib.bts_lpg_fused_fwd_f32.argtypes = [vp, i, i, i, i, i, f, vp, vp, i, l, vp, vp]
-    lib.bts_reduc_fwd_f32.restype = i
-    lib.bts_reduc_fwd_f32.argtypes = [vp, l, l, i, i, vp, l, f, i, i, vp, vp]
-    lib.bts_reduc_lpg_fwd_f32.restype = i
-    lib.bts_reduc_lpg_fwd_f32.argtypes = [vp, l, i, i, i, i, i, vp, l, f, i, vp, vp, vp, vp, vp]
-    lib.bts_reduc_bwd_f32.restype = i
-    lib.bts_reduc_bwd_f32.argtypes = [vp, l, i, i, i, i, i, vp, l, vp, l, f, i, vp, vp, l, vp, vp, vp]
-    lib.bts_reduc_bwd_max_waves.restype = l
-    lib.bts_reduc_bwd_max_waves.argtypes = [i, i, i]
-    lib.bts_conv_fwd_f32.restype = i
-    lib.bts_conv_fwd_f32.argtypes = [C.POINTER(ConvDesc), vp]
-    lib.bts_conv_wgrad_f32.restype = i
-    lib.bts_conv_wgrad_f32.argtypes = [C.POINTER(ConvWgradDesc), vp]
-    lib.bts_conv_wgrad_plan_f32.restype = i
-    lib.bts_conv_wgrad_plan_f32.argtypes = [C.POINTER(ConvWgradDesc), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_long),
-                                            C.POINTER(C.c_long)]
-    lib.bts_conv_wgrad_batch_table_bytes.restype = l
-    lib.bts_conv_wgrad_batch_table_bytes.argtypes = [i]
-    lib.bts_conv_wgrad_batch_plan_f32.restype = i
-    lib.bts_conv_wgrad_batch_plan_f32.argtypes = [C.POINTER(ConvWgradDesc), i, C.POINTER(vp), C.POINTER(l), i, l, vp,
-                                                  C.POINTER(ConvWgradBatchItem)]
-    lib.bts_conv_wgrad_batch_f32.restype = i
-    lib.bts_conv_wgrad_batch_f32.argtypes = [vp, vp, i, C.POINTER(vp), i, vp, vp]
-    lib.bts_bn_train_ws_floats.restype = l
-    lib.bts_bn_train_ws_floats.argtypes = [l, i]
-    lib.bts_bn_train_stats_f32.restype = i
-    lib.bts_bn_train_stats_f32.argtypes = [vp, l, l, i, vp, vp, f, f, vp, vp, vp, l, vp, vp, vp, vp, vp]
-    lib.bts_bn_apply_nhwc_f32.restype = i
-    lib.bts_bn_apply_nhwc_f32.argtypes = [vp, l, l, i, vp, vp, i, vp, l, vp]
-    lib.bts_bn_train_bwd_f32.restype = i
-    lib.bts_bn_train_bwd_f32.argtypes = [vp, l, vp, l, l, i, vp, vp, vp, vp, i, vp, l, vp, vp, vp, l, vp]
-    lib.bts_pack_weights_blocks.restype = l
-    lib.bts_pack_weights_blocks.argtypes = [l, l]
-    lib.bts_pack_weights_f32.restype = i
-    lib.bts_pack_weights_f32.argtypes = [vp, i, l, vp]
-    lib.bts_pack_wino_floats.restype = l
-    lib.bts_pack_wino_floats.argtypes = [i, i, i, i]
-    lib.bts_pack_wino_f32.restype = i
-    lib.bts_pack_wino_f32.argtypes = [vp, i, l, i, i, i, vp, vp]
-    lib.bts_conv_plan_f32.restype = i
-    lib.bts_conv_plan_f32.argtypes = [C.POINTER(ConvDesc), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    lib.bts_conv_plan_ksteps_f32.restype = i
-    lib.bts_conv_plan_ksteps_f32.argtypes = [C.POINTER(ConvDesc), C.POINTER(C.c_long), C.POINTER(C.c_long)]
-    lib.bts_nchw_to_nhwc_f32.restype = i
-    lib.bts_nchw_to_nhwc_f32.argtypes = [vp, i, i, l, vp, l, i, vp]
-    lib.bts_nhwc_to_nchw_f32.restype = i
-    lib.bts_nhwc_to_nchw_f32.argtypes = [vp, l, i, i, l, vp, vp]
-    lib.bts_maxpool3x3s2_nhwc_f32.restype = i
-    lib.bts_maxpool3x3s2_nhwc_f32.argtypes = [vp, l, i, i, i, i, vp, l, vp, l, vp]
-    lib.bts_bn_relu_avgpool2_nhwc_f32.restype = i
-    lib.bts_bn_relu_avgpool2_nhwc_f32.argtypes = [vp, l, i, i, i, i, vp, vp, vp, l, vp]
-    lib.bts_pack_planes_f32.restype = i
-    lib.bts_pack_planes_f32.argtypes = [vp, vp, vp, vp, i, l, vp, l, vp]
-    lib.bts_get_depth_f32.restype = i
-    lib.bts_get_depth_f32.argtypes = [vp, vp, i, i, i, i, f, vp, vp, vp]
-    lib.bts_upconv_combine_f32.restype = i
-    lib.bts_upconv_combine_f32.argtypes = [vp, l, i, i, i, i, vp, vp, i, vp, l, vp]
-    lib.bts_upconv_up9_fwd_f32.restype = i
-    lib.bts_upconv_up9_fwd_f32.argtypes = [vp, l, i, i, i, i, vp, i, vp, vp, i, vp, l, vp]
-    lib.bts_upconv_up9_plan.restype = i
-    lib.bts_upconv_up9_plan.argtypes = [i, i, i, i, i, i, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_long)]
-    lib.bts_conv_tail_bf16_fwd_f32.restype = i
-    lib.bts_conv_tail_bf16_fwd_f32.argtypes = [vp, l, i, i, i, i, vp, vp, vp, i, i, i, vp, vp, i, vp, l, vp]
-    lib.bts_conv_tail_bf16_plan.restype = i
-    lib.bts_conv_tail_bf16_plan.argtypes = [i, i, i, i, i, i, C.POINTER(C.c_int), C.POINTER(C.c_long)]
-    lib.bts_conv_tail_wino_fwd_f32.restype = i
-    lib.bts_conv_tail_wino_fwd_f32.argtypes = [vp, l, i, i, i, i, vp, vp, vp, vp, vp, vp, i, i, i, vp, vp]
-    lib.bts_conv_tail_wino_plan.restype = i
-    lib.bts_conv_tail_wino_plan.argtypes = [i, i, i, i, i, i, i, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_long)]
-    lib.bts_upconv_dgrad_f32.restype = i
-    lib.bts_upconv_dgrad_f32.argtypes = [vp, l, i, i, i, i, vp, i, vp, l, i, i, vp, l, vp]
-    lib.bts_upconv_dgrad_plan.restype = i
-    lib.bts_upconv_dgrad_plan.argtypes = [i, i, i, i, i, i, i, l, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    lib.bts_upconv_wgrad_f32.restype = i
-    lib.bts_upconv_wgrad_f32.argtypes = [vp, l, i, i, i, i, vp, l, i, vp, vp, l, vp]
-    lib.bts_upconv_wgrad_plan_f32.restype = i
-    lib.bts_upconv_wgrad_plan_f32.argtypes = [i, i, i, i, i, l, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_long),
-                                              C.POINTER(C.c_long)]
-    lib.bts_upconv_train_pack_blocks.restype = l
-    lib.bts_upconv_train_pack_blocks.argtypes = [l, l, l, l]
-    lib.bts_upconv_train_pack_f32.restype = i
-    lib.bts_upconv_train_pack_f32.argtypes = [vp, i, l, vp]
-    lib.bts_eval_ws_doubles.restype = l
-    lib.bts_eval_ws_doubles.argtypes = [i, i, i]
-    lib.bts_eval_depth_metrics_f32.restype = i
-    lib.bts_eval_depth_metrics_f32.argtypes = [vp, i, i, i, vp, i, i, i, i, f, f, i, i, i, i, vp, l, vp, vp, vp]
-    lib.bts_depth_loss_ws_doubles.restype = l
-    lib.bts_depth_loss_ws_doubles.argtypes = [l]
-    lib.bts_depth_loss_fwd_f32.restype = i
-    lib.bts_depth_loss_fwd_f32.argtypes = [vp, vp, vp, f, l, i, f, vp, l, vp, vp, vp]
-    lib.bts_depth_loss_bwd_f32.restype = i
-    lib.bts_depth_loss_bwd_f32.argtypes = [vp, vp, vp, f, l, i, f, vp, vp, vp, vp]
-    lib.bts_adamw_table_bytes.restype = l
-    lib.bts_adamw_table_bytes.argtypes = [i]
-    lib.bts_adamw_flat_span.restype = l
-    lib.bts_adamw_flat_span.argtypes = []
-    lib.bts_adamw_plan_f32.restype = i
-    lib.bts_adamw_plan_f32.argtypes = [vp, i, vp, C.POINTER(l), vp]
-    lib.bts_adamw_step_f32.restype = i
-    lib.bts_adamw_step_f32.argtypes = [vp, i, l, vp, i, vp, vp]
+    for name, e in ABI.items():
+        if not hasattr(lib, name):
+            raise BtsHipError("bts_amd: symbol %s missing from %s" % (name, LIB_PATH))
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = e.restype, list(e.argtypes)
     if lib.bts_hip_abi_version() != ABI_VERSION:
         raise BtsHipError("bts_amd: ABI version mismatch (%d != %d)" % (lib.bts_hip_abi_version(), ABI_VERSION))
     _lib = lib

@@ -39,8 +39,7 @@ __global__ __launch_bounds__(WM * 128, (SB && WM == 2 ? 3 : 2)) void conv1x1_ker
     float* const Bs = As + 2 * A_FLOATS;                           // [2 or 1][BN][LDS_LD]
 
     const int nwg = gridDim.x, bid = blockIdx.x;
-    const int xcd = bid & 7, qq = nwg >> 3, rr = nwg & 7;
-    const int swz = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (bid >> 3);
+    const int swz = xcd_swizzle(bid, nwg);
     const int mt_idx = swz / a.n_ntiles, nt_idx = swz - mt_idx * a.n_ntiles;
     const long m0 = (long)mt_idx * BM;
     const int n0 = nt_idx * BN;

@@ -74,8 +74,7 @@ __global__ __launch_bounds__(512, 2) void conv_halo_emu_kernel(const ConvArgs a)
 
     // ---- tile decode (as conv_halo_kernel)
     const int nwg = gridDim.x, bid = blockIdx.x;
-    const int xcd = bid & 7, qq = nwg >> 3, rr = nwg & 7;
-    const int swz = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (bid >> 3);
+    const int swz = xcd_swizzle(bid, nwg);
     const int cls = a.subpix ? (swz & 3) : 0;
     const int tcl = a.subpix ? (swz >> 2) : swz;
     const int mt_idx = tcl / a.n_ntiles, nt_idx = tcl - mt_idx * a.n_ntiles;

@@ -49,6 +49,26 @@ const ConvKnobs& knobs() {
                                 (int)env_long("BTS_CONV_1X1", 1), (int)env_long("BTS_CONV_HALO_DIL", 1)};
     return k;
 }
+
+// ---- argument checks the opt-in entry points share (bts_upconv_up9 / bts_conv_tail_bf16 / bts_conv_tail_wino)
+// an NHWC input view: non-null, 16-byte aligned, a pixel stride of whole float4s that holds `channels`
+inline bool nhwc_view_ok(const void* p, long pix_stride, int channels) {
+    return p != nullptr && !((uintptr_t)p & 15) && !(pix_stride & 3) && pix_stride >= channels;
+}
+// none / ReLU / ELU, and an e2 affine that is a whole (scale, shift) pair or absent
+inline bool act_e2_ok(int act, const float* e2_scale, const float* e2_shift) {
+    return (e2_scale == nullptr) == (e2_shift == nullptr) && act >= 0 && act <= 2;
+}
+// a 32-bit element offset reaches every one of `elements`
+inline bool fits_u32(double elements) { return elements < 4294967296.0; }
+// what a plan query resolves from its arguments: the caller's fill_frames, else the knob; the caller's precision unless
+// $BTS_CONV_PRECISION overrides every descriptor.  false: fill_frames out of range.
+inline bool resolve_declaration(int fill_frames, int precision, int* ff, int* prec) {
+    if (fill_frames < 0 || fill_frames > 4096) return false;
+    *ff = fill_frames > 0 ? fill_frames : knobs().fill_frames;
+    *prec = knobs().precision >= 0 ? knobs().precision : precision;
+    return true;
+}
 // floats per LDS row (32 + pad), chosen per MFMA shape so that the 16 rows a ds_read_b128 lane group touches
 // land in 16 distinct 16-B bank slots: 36 (slot = 9*row) for the 32x32 lane map, 40 (slot = 10*row + k-quarter)
 // for the 16x16 one -- 36 is 2-way conflicted there (SQ_LDS_BANK_CONFLICT, profiles/r01_pmc_mfma.json)
@@ -145,6 +165,22 @@ template <int ACT> __device__ __forceinline__ float act_fn(float v) {
     else if constexpr (ACT == 2) return elu1(v);
     else if constexpr (ACT == 3) return sigmoid1(v);
     else return v;
+}
+
+// A runtime activation code (0 none / 1 ReLU / 2 ELU; wave-uniform) onto a template parameter: f(integral_constant<int, ACT>).
+// conv_up9_kernel keeps its own three-way `if`: through this helper its machine code changes.
+template <typename F> __device__ __forceinline__ void dispatch_act(int act, F f) {
+    if (act == 2) f(std::integral_constant<int, 2>{});
+    else if (act == 1) f(std::integral_constant<int, 1>{});
+    else f(std::integral_constant<int, 0>{});
+}
+
+// XCD-aware block remap (bijective over the n tile ids of a launch): blocks sharing an XCD (bid % 8) get a contiguous range
+// of tiles, so neighbouring pixel tiles (shared halo rows) and the N tiles of one M tile share an L2.  Every .inc kernel
+// calls it; conv_fwd_kernel below spells the same two lines out, because through the call its machine code changes.
+__device__ __forceinline__ int xcd_swizzle(int bid, int n) {
+    const int xcd = bid & 7, qq = n >> 3, rr = n & 7;
+    return (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (bid >> 3);
 }
 
 // One wave's TM x TN accumulator tiles to NHWC.  Row slot q (0..MF-1) of row tile i is output pixel
@@ -1176,11 +1212,10 @@ extern "C" int bts_conv_plan_ksteps_f32(const bts_conv_desc* d, long* issued, lo
 //      bts_conv_fwd_f32 / bts_conv_plan_f32 answer for every descriptor exactly as they did without it
 extern "C" int bts_upconv_up9_plan(int h, int w, int c_in, int c_out, int precision, int fill_frames, int* bm, int* bn,
                                    long* workgroups) {
-    if (!bm || !bn || !workgroups) return BTS_ERR_INVALID;
-    if (fill_frames < 0 || fill_frames > 4096) return BTS_ERR_INVALID;
-    const int prec_env = knobs().precision;
+    int ff, prec;
+    if (!bm || !bn || !workgroups || !resolve_declaration(fill_frames, precision, &ff, &prec)) return BTS_ERR_INVALID;
     long wgs = 0;
-    const bool ok = up9_eligible(h, w, c_in, c_out, prec_env >= 0 ? prec_env : precision, fill_frames > 0 ? fill_frames : knobs().fill_frames, &wgs);
+    const bool ok = up9_eligible(h, w, c_in, c_out, prec, ff, &wgs);
     *bm = ok ? UP9_WY * UP9_WX : 0; *bn = ok ? 32 : 0; *workgroups = ok ? wgs : 0;
     return 0;
 }
@@ -1190,13 +1225,12 @@ extern "C" int bts_upconv_up9_fwd_f32(const float* x, long x_pix_stride, int B, 
                                       bts_stream_t stream) {
     if (!x || !u || !y || B <= 0 || h <= 0 || w <= 0 || c_in <= 0 || c_out <= 0) return BTS_ERR_INVALID;
     if ((c_in % BK) || (c_out % 32)) return BTS_ERR_UNSUPPORTED;
-    if ((x_pix_stride & 3) || x_pix_stride < c_in || y_pix_stride < c_out) return BTS_ERR_INVALID;
-    if (((uintptr_t)x & 15) || ((uintptr_t)u & 15) || ((uintptr_t)y & 3)) return BTS_ERR_INVALID;
-    if ((e2_scale == nullptr) != (e2_shift == nullptr) || act < 0 || act > 2) return BTS_ERR_INVALID;
+    if (!nhwc_view_ok(x, x_pix_stride, c_in) || y_pix_stride < c_out || ((uintptr_t)u & 15) || ((uintptr_t)y & 3)) return BTS_ERR_INVALID;
+    if (!act_e2_ok(act, e2_scale, e2_shift)) return BTS_ERR_INVALID;
     // the kernel addresses the source map with 32-bit element offsets and decodes tiles with 32-bit arithmetic
     // (and an output row's columns with a 32-bit per-lane offset)
-    if ((double)B * h * w * (double)x_pix_stride >= 4294967296.0 || (double)h * w >= 2147483648.0 ||
-        (double)(2 * w + 64) * (double)y_pix_stride >= 4294967296.0) return BTS_ERR_UNSUPPORTED;
+    if (!fits_u32((double)B * h * w * (double)x_pix_stride) || (double)h * w >= 2147483648.0 ||
+        !fits_u32((double)(2 * w + 64) * (double)y_pix_stride)) return BTS_ERR_UNSUPPORTED;
     Up9Args a;
     a.x = x; a.x_pix_stride = x_pix_stride; a.B = B; a.H = h; a.W = w; a.c_in = c_in;
     a.u = u; a.c_out = c_out; a.e2_scale = e2_scale; a.e2_shift = e2_shift; a.act = act;
@@ -1214,9 +1248,8 @@ extern "C" int bts_upconv_up9_fwd_f32(const float* x, long x_pix_stride, int B, 
 // ---- planar-tail 3x3 convolution with bf16 main operands (conv_tail_bf16.inc): its own opt-in entry point and plan query,
 //      so that bts_conv_fwd_f32 / bts_conv_plan_f32 answer for every descriptor exactly as they did without it
 extern "C" int bts_conv_tail_bf16_plan(int h, int w, int c_main, int c_out, int n_tail, int fill_frames, int* bn, long* workgroups) {
-    if (!bn || !workgroups) return BTS_ERR_INVALID;
-    if (fill_frames < 0 || fill_frames > 4096) return BTS_ERR_INVALID;
-    const int ff = fill_frames > 0 ? fill_frames : knobs().fill_frames;
+    int ff, prec;                                           // the arithmetic is this entry point's own: no precision argument
+    if (!bn || !workgroups || !resolve_declaration(fill_frames, 0, &ff, &prec)) return BTS_ERR_INVALID;
     long wgs = 0;
     const bool ok = tail_bf16_eligible(h, w, c_main, c_out, n_tail, &wgs);
     *bn = ok ? tail_bf16_bn(c_out) : 0; *workgroups = ok ? ff * wgs : 0;
@@ -1232,14 +1265,13 @@ extern "C" int bts_conv_tail_bf16_fwd_f32(const float* x, long x_pix_stride, int
     if (n_tail < 1 || n_tail > 4) return BTS_ERR_INVALID;
     if (n_tail != 1 || (c_main % BK)) return BTS_ERR_UNSUPPORTED;
     if ((c_out_pad & 31) || c_out_pad < c_out) return BTS_ERR_INVALID;
-    if ((x_pix_stride & 3) || x_pix_stride < c_main || y_pix_stride < c_out) return BTS_ERR_INVALID;
-    if (((uintptr_t)x & 15) || ((uintptr_t)w_main & 15) || ((uintptr_t)w_tail & 15) || ((uintptr_t)tail_plane & 3) || ((uintptr_t)y & 3))
-        return BTS_ERR_INVALID;
-    if ((e2_scale == nullptr) != (e2_shift == nullptr) || act < 0 || act > 2) return BTS_ERR_INVALID;
+    if (!nhwc_view_ok(x, x_pix_stride, c_main) || y_pix_stride < c_out || ((uintptr_t)w_main & 15) || ((uintptr_t)w_tail & 15) ||
+        ((uintptr_t)tail_plane & 3) || ((uintptr_t)y & 3)) return BTS_ERR_INVALID;
+    if (!act_e2_ok(act, e2_scale, e2_shift)) return BTS_ERR_INVALID;
     // the kernel addresses both operands with 32-bit element offsets, decodes tiles with 32-bit arithmetic and addresses the
     // pixels of an output tile row with a 32-bit per-lane offset
-    if ((double)B * h * w * (double)x_pix_stride >= 4294967296.0 || (double)B * h * w >= 2147483648.0 ||
-        (double)c_out_pad * 9.0 * c_main >= 4294967296.0 || 64.0 * (double)y_pix_stride >= 4294967296.0) return BTS_ERR_UNSUPPORTED;
+    if (!fits_u32((double)B * h * w * (double)x_pix_stride) || (double)B * h * w >= 2147483648.0 ||
+        !fits_u32((double)c_out_pad * 9.0 * c_main) || !fits_u32(64.0 * (double)y_pix_stride)) return BTS_ERR_UNSUPPORTED;
     TailBf16Args a;
     a.x = x; a.x_pix_stride = x_pix_stride; a.B = B; a.H = h; a.W = w; a.c_main = c_main;
     a.w_main = static_cast<const unsigned short*>(w_main); a.w_tail = w_tail; a.tail = tail_plane;
@@ -1252,12 +1284,10 @@ extern "C" int bts_conv_tail_bf16_fwd_f32(const float* x, long x_pix_stride, int
 //      entry point and plan query, so that bts_conv_fwd_f32 / bts_conv_plan_f32 answer for every descriptor exactly as before
 extern "C" int bts_conv_tail_wino_plan(int h, int w, int c_main, int c_out, int n_tail, int precision, int fill_frames, int* bm,
                                        int* bn, long* workgroups) {
-    if (!bm || !bn || !workgroups) return BTS_ERR_INVALID;
-    if (fill_frames < 0 || fill_frames > 4096) return BTS_ERR_INVALID;
-    const int prec_env = knobs().precision;
+    int ff, prec;
+    if (!bm || !bn || !workgroups || !resolve_declaration(fill_frames, precision, &ff, &prec)) return BTS_ERR_INVALID;
     long wgs = 0;
-    const bool ok = wino_tail_eligible(h, w, c_main, c_out, n_tail, prec_env >= 0 ? prec_env : precision,
-                                       fill_frames > 0 ? fill_frames : knobs().fill_frames, &wgs);
+    const bool ok = wino_tail_eligible(h, w, c_main, c_out, n_tail, prec, ff, &wgs);
     *bm = ok ? WT_WY * WT_WX : 0; *bn = ok ? 32 : 0; *workgroups = ok ? wgs : 0;
     return 0;
 }
@@ -1266,15 +1296,14 @@ extern "C" int bts_conv_tail_wino_fwd_f32(const float* x, long x_pix_stride, int
                                           const float* w_tail, const float* tail0, const float* tail1, const float* tail2,
                                           const float* tail3, int n_tail, int c_out, int act, float* y, bts_stream_t stream) {
     if (!x || !u || !w_tail || !y || B <= 0 || h <= 0 || w <= 0 || c_main <= 0 || c_out <= 0) return BTS_ERR_INVALID;
-    if (n_tail < 0 || n_tail > 4 || act < 0 || act > 2) return BTS_ERR_INVALID;
+    if (n_tail < 0 || n_tail > 4 || !act_e2_ok(act, nullptr, nullptr)) return BTS_ERR_INVALID;
     if (c_main != 32 || c_out != 32) return BTS_ERR_UNSUPPORTED;
-    if ((x_pix_stride & 3) || x_pix_stride < c_main) return BTS_ERR_INVALID;
-    if (((uintptr_t)x & 15) || ((uintptr_t)u & 15) || ((uintptr_t)w_tail & 3) || ((uintptr_t)y & 7)) return BTS_ERR_INVALID;
+    if (!nhwc_view_ok(x, x_pix_stride, c_main) || ((uintptr_t)u & 15) || ((uintptr_t)w_tail & 3) || ((uintptr_t)y & 7)) return BTS_ERR_INVALID;
     const float* const planes[4] = {tail0, tail1, tail2, tail3};
     for (int j = 0; j < n_tail; ++j)
         if (!planes[j] || ((uintptr_t)planes[j] & 3)) return BTS_ERR_INVALID;
     // the kernel addresses x and the planes with 32-bit element offsets and decodes tiles with 32-bit arithmetic
-    if ((double)B * h * w * (double)x_pix_stride >= 4294967296.0 || (double)B * h * w >= 2147483648.0) return BTS_ERR_UNSUPPORTED;
+    if (!fits_u32((double)B * h * w * (double)x_pix_stride) || (double)B * h * w >= 2147483648.0) return BTS_ERR_UNSUPPORTED;
     WinoTailArgs a;
     a.x = x; a.x_pix_stride = x_pix_stride; a.B = B; a.H = h; a.W = w;
     a.u = u; a.w_tail = w_tail; a.n_tail = n_tail; a.act = act; a.y = y;

@@ -92,8 +92,7 @@ __global__ __launch_bounds__(512, 4) void conv_tail_bf16_kernel(const TailBf16Ar
 
     // ---- tile decode (as conv_halo_emu_kernel)
     const int nwg = gridDim.x, bid = blockIdx.x;
-    const int xcd = bid & 7, qq = nwg >> 3, rr = nwg & 7;
-    const int swz = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (bid >> 3);
+    const int swz = xcd_swizzle(bid, nwg);
     const int mt_idx = swz / a.n_ntiles, nt_idx = swz - mt_idx * a.n_ntiles;
     const int n0 = nt_idx * BN;
     const int n_tx = (a.W + TW - 1) / TW, n_ty = (a.H + TH - 1) / TH;
@@ -328,9 +327,7 @@ __global__ __launch_bounds__(512, 4) void conv_tail_bf16_kernel(const TailBf16Ar
         nvalid[i] = y < a.H ? (xleft >= MF ? MF : xleft) : 0;
     }
     const int ncol0 = n0 + cns * TN * MF;
-    if (a.act == 2) tail_bf16_store<2, TM, TN>(a, acc, pix0, nvalid, ncol0, li, lh);
-    else if (a.act == 1) tail_bf16_store<1, TM, TN>(a, acc, pix0, nvalid, ncol0, li, lh);
-    else tail_bf16_store<0, TM, TN>(a, acc, pix0, nvalid, ncol0, li, lh);
+    dispatch_act(a.act, [&](auto act) { tail_bf16_store<decltype(act)::value, TM, TN>(a, acc, pix0, nvalid, ncol0, li, lh); });
 }
 
 // The layers the decoder hands to this kernel (bts_conv_tail_bf16_plan).  From the bf16 halo tile: whole 32-channel chunks

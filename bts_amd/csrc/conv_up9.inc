@@ -101,8 +101,7 @@ __global__ __launch_bounds__(256, 2) void conv_up9_kernel(const Up9Args a) {
     const int nchunks = a.c_in / BK;
     // tile decode (XCD-aware bijective swizzle, as conv_wino_kernel: the channel tiles of one patch stay on one XCD's L2)
     const int bid = blockIdx.x, ntiles = a.ntiles;
-    const int xcd = bid & 7, qq = ntiles >> 3, rr = ntiles & 7;
-    const int swz = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (bid >> 3);
+    const int swz = xcd_swizzle(bid, ntiles);
     const int mt_idx = swz / a.n_ntiles, nt_idx = swz - mt_idx * a.n_ntiles;
     const int bfr = mt_idx / (a.n_tx * a.n_ty);
     const int trem = mt_idx - bfr * (a.n_tx * a.n_ty);

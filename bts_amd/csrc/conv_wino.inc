@@ -92,8 +92,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino_kernel(const ConvArgs a) {
     unsigned inimg = 0, inpatch = 0;
     int n0 = 0, bfr = 0, y0 = 0, x0 = 0;                           // of the tile whose patches are being staged
     auto decode = [&](int bid) {                                   // tile decode (XCD-aware bijective swizzle over the ntiles tile ids)
-        const int xcd = bid & 7, qq = ntiles >> 3, rr = ntiles & 7;
-        const int swz = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (bid >> 3);
+        const int swz = xcd_swizzle(bid, ntiles);
         const int mt_idx = swz / a.n_ntiles, nt_idx = swz - mt_idx * a.n_ntiles;
         n0 = nt_idx * BN;
         bfr = mt_idx / (n_tx * n_ty);

@@ -97,8 +97,7 @@ __global__ __launch_bounds__(256, 2) void conv_wino_tail_kernel(const WinoTailAr
     const int lw = lane & 15, lg = lane >> 4;
     // tile decode (XCD-aware bijective swizzle, as conv_up9_kernel: vertically adjacent tiles share an XCD's L2)
     const int bid = blockIdx.x, ntiles = a.ntiles;
-    const int xcd = bid & 7, qq = ntiles >> 3, rr = ntiles & 7;
-    const int swz = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (bid >> 3);
+    const int swz = xcd_swizzle(bid, ntiles);
     const int bfr = swz / (a.n_tx * a.n_ty);
     const int trem = swz - bfr * (a.n_tx * a.n_ty);
     const int tyi = trem / a.n_tx;
@@ -224,9 +223,7 @@ __global__ __launch_bounds__(256, 2) void conv_wino_tail_kernel(const WinoTailAr
 
     // ---- output transform + activation + NCHW stores, in registers
     const int Y0 = y0 + 2 * wb, X = x0 + 2 * lw, n = 16 * cb + 4 * lg;
-    if (a.act == 2) wino_tail_epilogue<2>(a, acc, tacc, bfr, Y0, X, n);
-    else if (a.act == 1) wino_tail_epilogue<1>(a, acc, tacc, bfr, Y0, X, n);
-    else wino_tail_epilogue<0>(a, acc, tacc, bfr, Y0, X, n);
+    dispatch_act(a.act, [&](auto act) { wino_tail_epilogue<decltype(act)::value>(a, acc, tacc, bfr, Y0, X, n); });
 }
 
 // Host: workgroup tiles of one frame and the share of their pixels that are real (the tile-grid fill)

@@ -200,17 +200,14 @@ def gpu_compute_errors(pred_depth, gt_depth, dataset: str, min_depth_eval: float
     if do_kb_crop and (top < 0 or left < 0 or top + Hp > Hg or left + Wp > Wg):
         raise _lib.BtsHipError("gpu_compute_errors: kb-cropped prediction %dx%d does not fit the %dx%d ground truth" % (Hp, Wp, Hg, Wg))
     y0, y1, x0, x1 = eval_crop_rect(Hg, Wg, dataset, garg_crop, eigen_crop)
-    lib = _lib.load()
-    ws = torch.empty((int(lib.bts_eval_ws_doubles(B, Hg, Wg)),), dtype=torch.float64, device=pred.device)
+    ws = torch.empty((int(_lib.load_real().bts_eval_ws_doubles(B, Hg, Wg)),), dtype=torch.float64, device=pred.device)
     out = torch.empty((B, 10), dtype=torch.float64, device=pred.device)
     if accum is not None and (accum.dtype != torch.float64 or accum.numel() != 10 or accum.device != pred.device
                               or not accum.is_contiguous()):
         raise _lib.BtsHipError("gpu_compute_errors: accum must be a contiguous [10] float64 tensor on the prediction's device")
-    with torch.cuda.device(pred.device):
-        rc = lib.bts_eval_depth_metrics_f32(ops._ptr(pred), B, Hp, Wp, ops._ptr(gt), Hg, Wg, top, left,
-                                            float(min_depth_eval), float(max_depth_eval), y0, y1, x0, x1,
-                                            ops._ptr(ws), ws.numel(), ops._ptr(out), ops._ptr(accum), ops._stream(pred))
-    _lib.check(rc, "bts_eval_depth_metrics_f32")
+    ops._enqueue("bts_eval_depth_metrics_f32", pred,
+                 (ops._ptr(pred), B, Hp, Wp, ops._ptr(gt), Hg, Wg, top, left, float(min_depth_eval), float(max_depth_eval), y0, y1, x0, x1,
+                  ops._ptr(ws), ws.numel(), ops._ptr(out), ops._ptr(accum)))
     return out
 
 

@@ -91,6 +91,60 @@ def _rows2d(t: torch.Tensor, name: str) -> Tuple[int, int]:
     return t.stride(0), t.shape[1]
 
 
+def _enqueue(entry: str, anchor: torch.Tensor, args: Sequence = (), trace=None, run=None):
+    """Enqueue the C entry point ``entry`` on ``anchor``'s device and current stream, and check its return code.
+    ``args``: the prototype's arguments without the stream.  ``run``: a ready closure to call instead (the
+    torch-operator bindings).  ``trace`` = (kernel, tag, flops, bytes, executed flops or None): what a KernelTrace
+    records for the launch; without an active trace the call is made directly."""
+    with torch.cuda.device(anchor.device):
+        if _trace is None or trace is None:
+            rc = run() if run is not None else getattr(_lib.load(), entry)(*args, _stream(anchor))
+        else:
+            if run is None:
+                fn, stream = getattr(_lib.load(), entry), _stream(anchor)
+                run = lambda: fn(*args, stream)
+            rc = _launch(trace[0], trace[1], trace[2], trace[3], run, xflops=trace[4])
+    _lib.check(rc, entry)
+
+
+def _check_act3(act: int, who: str):
+    if act not in (ACT_NONE, ACT_RELU, ACT_ELU):
+        raise BtsHipError("%s: act must be none, ReLU or ELU" % who)
+
+
+def _e2_vectors(e2, n: int, who: str):
+    """The (scale, shift) pair of an e2 affine over ``n`` channels, checked; (None, None) when absent."""
+    if e2 is None:
+        return None, None
+    es, eb = e2
+    _need(es, who)
+    _need(eb, who)
+    if es.numel() < n or eb.numel() < n:
+        raise BtsHipError("%s: e2 vectors need %d elements" % (who, n))
+    return es, eb
+
+
+def _dense_planes(planes, npix: int, who: str, at_most: int = 4) -> list:
+    """One-channel maps given as separate tensors (a planar tail, pack_planes' sources): at most ``at_most`` contiguous
+    fp32 maps of ``npix`` floats each."""
+    planes = list(planes) if planes else []
+    if len(planes) > at_most:
+        raise BtsHipError("%s: at most %d planes" % (who, at_most))
+    for t in planes:
+        _need(t, who)
+        if t.numel() != npix or not t.is_contiguous():
+            raise BtsHipError("%s: every plane must be one contiguous map of %d floats" % (who, npix))
+    return planes
+
+
+class TilePlan(tuple):
+    """(bm, bn, workgroups per frame) of a fused kernel's plan query; all 0 = the layer stays on its default kernel."""
+    bm = property(lambda self: self[0])
+    bn = property(lambda self: self[1])
+    workgroups = property(lambda self: self[2])
+    eligible = property(lambda self: self[0] > 0)
+
+
 # ------------------------------------------------------------------------------ binding of the hot-path operators
 # The hot-path operators (LPG, reduction_1x1, reduction -> LPG, the fused convolution) are TORCH OPERATORS:
 # torch.ops.bts_hip.* (csrc/torch_ops.cpp, a TORCH_LIBRARY shell over the C ABI -- what the reference's native side does
@@ -188,9 +242,7 @@ def lpg_forward(plane_eq: torch.Tensor, upratio: int, abs_min: Optional[torch.Te
     B, _, h, w = plane_eq.shape
     k = int(upratio)
     out = torch.empty((B, h * k, w * k), dtype=torch.float32, device=plane_eq.device)
-    with torch.cuda.device(plane_eq.device):
-        rc = _lib.load().bts_lpg_fwd_f32(_ptr(plane_eq), B, h, w, k, _ptr(out), _ptr(abs_min), _stream(plane_eq))
-    _lib.check(rc, "bts_lpg_fwd_f32")
+    _enqueue("bts_lpg_fwd_f32", plane_eq, (_ptr(plane_eq), B, h, w, k, _ptr(out), _ptr(abs_min)))
     return out
 
 
@@ -205,9 +257,7 @@ def lpg_backward(plane_eq: torch.Tensor, grad_depth: torch.Tensor, upratio: int)
     if tuple(grad_depth.shape) != (B, h * k, w * k):
         raise BtsHipError("lpg_backward: grad_depth must be [B,h*k,w*k]")
     g = torch.empty_like(plane_eq)
-    with torch.cuda.device(plane_eq.device):
-        rc = _lib.load().bts_lpg_bwd_f32(_ptr(plane_eq), _ptr(grad_depth), B, h, w, k, _ptr(g), _stream(plane_eq))
-    _lib.check(rc, "bts_lpg_bwd_f32")
+    _enqueue("bts_lpg_bwd_f32", plane_eq, (_ptr(plane_eq), _ptr(grad_depth), B, h, w, k, _ptr(g)))
     return g
 
 
@@ -233,16 +283,13 @@ _LOSS_KINDS = {"silog": 0, "l1": 1, 0: 0, 1: 1}
 
 def _depth_loss_fwd(est, gt, mask, gt_min, kind, param):
     """ctypes binding of bts_depth_loss_fwd_f32 on checked, contiguous tensors: (loss 0-d fp32, stats [4] fp64)."""
-    lib = _lib.load()
     npix = est.numel()
-    nws = lib.bts_depth_loss_ws_doubles(npix)
+    nws = _lib.load_real().bts_depth_loss_ws_doubles(npix)
     ws = torch.empty(nws, dtype=torch.float64, device=est.device)
     stats = torch.empty(4, dtype=torch.float64, device=est.device)
     loss = torch.empty((), dtype=torch.float32, device=est.device)
-    with torch.cuda.device(est.device):
-        rc = lib.bts_depth_loss_fwd_f32(_ptr(est), _ptr(gt), _ptr(mask), gt_min, npix, kind, param, _ptr(ws), nws, _ptr(stats),
-                                        _ptr(loss), _stream(est))
-    _lib.check(rc, "bts_depth_loss_fwd_f32")
+    _enqueue("bts_depth_loss_fwd_f32", est, (_ptr(est), _ptr(gt), _ptr(mask), gt_min, npix, kind, param, _ptr(ws), nws, _ptr(stats),
+                                             _ptr(loss)))
     return loss, stats
 
 
@@ -250,10 +297,8 @@ def _depth_loss_bwd(est, gt, mask, gt_min, kind, param, stats, grad_loss):
     # the gradient starts at est's offset from a 16-byte line, so that the kernel can store 16 bytes per lane next to its loads
     off = (est.data_ptr() & 15) >> 2
     g = torch.empty(est.numel() + off, dtype=torch.float32, device=est.device)[off:].view(est.shape)
-    with torch.cuda.device(est.device):
-        rc = _lib.load().bts_depth_loss_bwd_f32(_ptr(est), _ptr(gt), _ptr(mask), gt_min, est.numel(), kind, param, _ptr(stats),
-                                                _ptr(grad_loss), _ptr(g), _stream(est))
-    _lib.check(rc, "bts_depth_loss_bwd_f32")
+    _enqueue("bts_depth_loss_bwd_f32", est, (_ptr(est), _ptr(gt), _ptr(mask), gt_min, est.numel(), kind, param, _ptr(stats),
+                                             _ptr(grad_loss), _ptr(g)))
     return g
 
 
@@ -324,13 +369,10 @@ def lpg_fused_forward(plane4: torch.Tensor, B: int, h: int, w: int, upratio: int
     if depth_scaled.numel() != B * h * k * w * k or not depth_scaled.is_contiguous():
         raise BtsHipError("lpg_fused_forward: depth_scaled must be contiguous [B,1,h*k,w*k]")
     nbytes = 4.0 * (4 * B * h * w + B * h * k * w * k + (B * h * k * w * k // (ds_factor * ds_factor) if ds_out is not None else 0))
-    with torch.cuda.device(plane4.device):
-        rc = _launch("lpg_fwd_kernel<%d,fused>" % k, "lpg", 8.0 * B * h * k * w * k, nbytes,
-                     lambda: _lib.load().bts_lpg_fused_fwd_f32(_ptr(plane4), B, h, w, k, int(bool(normalize)),
-                                                               float(max_depth), _ptr(depth_scaled), _ptr(ds_out),
-                                                               int(ds_factor), int(ds_pix_stride), _ptr(abs_min),
-                                                               _stream(plane4)))
-    _lib.check(rc, "bts_lpg_fused_fwd_f32")
+    _enqueue("bts_lpg_fused_fwd_f32", plane4,
+             (_ptr(plane4), B, h, w, k, int(bool(normalize)), float(max_depth), _ptr(depth_scaled), _ptr(ds_out), int(ds_factor),
+              int(ds_pix_stride), _ptr(abs_min)),
+             trace=("lpg_fwd_kernel<%d,fused>" % k, "lpg", 8.0 * B * h * k * w * k, nbytes, None))
     return depth_scaled
 
 
@@ -480,16 +522,14 @@ def reduc_forward_nhwc(x2d: torch.Tensor, c_in: int, c_first_out: int, w_frag: t
     macs = sum(ci * (co if co > 0 else (1 if is_final else 3)) for ci, co in chain)
     nbytes = 4.0 * (npix * (c_in + (1 if is_final else 4)) + macs)
     tops = torch_ops()
+    run = None
     if tops is not None:
         run = lambda: _op(lambda: tops.reduction_1x1(x2d, int(c_in), int(c_first_out), w_frag, float(max_depth), bool(is_final),
                                                      bool(normalize), out))
-    else:
-        run = lambda: _lib.load().bts_reduc_fwd_f32(_ptr(x2d), stride, npix, int(c_in), int(c_first_out),
-                                                    _ptr(w_frag), w_frag.numel(), float(max_depth),
-                                                    int(bool(is_final)), int(bool(normalize)), _ptr(out), _stream(x2d))
-    with torch.cuda.device(x2d.device):
-        rc = _launch("reduc_fwd_kernel<%d,%d>" % (c_in, c_first_out), "reduc", 2.0 * npix * macs, nbytes, run)
-    _lib.check(rc, "bts_reduc_fwd_f32")
+    _enqueue("bts_reduc_fwd_f32", x2d,
+             (_ptr(x2d), stride, npix, int(c_in), int(c_first_out), _ptr(w_frag), w_frag.numel(), float(max_depth), int(bool(is_final)),
+              int(bool(normalize)), _ptr(out)),
+             trace=("reduc_fwd_kernel<%d,%d>" % (c_in, c_first_out), "reduc", 2.0 * npix * macs, nbytes, None), run=run)
     return out
 
 
@@ -518,17 +558,15 @@ def reduc_lpg_forward(x2d: torch.Tensor, B: int, h: int, w: int, c_in: int, c_fi
     macs = sum(ci * (co if co > 0 else 3) for ci, co in chain)
     nbytes = 4.0 * (npix * c_in + macs + npix * k * k + (npix * 4 if ds_out is not None else 0))
     tops = torch_ops()
+    run = None
     if tops is not None:
         run = lambda: _op(lambda: tops.reduc_lpg(x2d, B, h, w, int(c_in), int(c_first_out), w_frag, float(max_depth), k,
                                                  depth_scaled, ds_out, abs_min, plane4))
-    else:
-        run = lambda: _lib.load().bts_reduc_lpg_fwd_f32(_ptr(x2d), stride, B, h, w, int(c_in), int(c_first_out),
-                                                        _ptr(w_frag), w_frag.numel(), float(max_depth), k,
-                                                        _ptr(plane4), _ptr(depth_scaled), _ptr(ds_out),
-                                                        _ptr(abs_min), _stream(x2d))
-    with torch.cuda.device(x2d.device):
-        rc = _launch("reduc_lpg_kernel<%d,%d,k%d>" % (c_in, c_first_out, k), "reduc_lpg", 2.0 * npix * macs + 8.0 * npix * k * k, nbytes, run)
-    _lib.check(rc, "bts_reduc_lpg_fwd_f32")
+    _enqueue("bts_reduc_lpg_fwd_f32", x2d,
+             (_ptr(x2d), stride, B, h, w, int(c_in), int(c_first_out), _ptr(w_frag), w_frag.numel(), float(max_depth), k, _ptr(plane4),
+              _ptr(depth_scaled), _ptr(ds_out), _ptr(abs_min)),
+             trace=("reduc_lpg_kernel<%d,%d,k%d>" % (c_in, c_first_out, k), "reduc_lpg", 2.0 * npix * macs + 8.0 * npix * k * k, nbytes, None),
+             run=run)
     return depth_scaled
 
 
@@ -589,16 +627,15 @@ def reduc_backward(x2d: torch.Tensor, B: int, h: int, w: int, c_in: int, c_first
     macs = sum(ci * co for ci, (_, co) in zip([c for c, _ in reduc_chain(c_in, c_first_out)], cols))
     nbytes = 4.0 * (npix * (c_in + yc + (yc + 4 if G is not None else 0) + (c_in if dx2d is not None else 0) + max(k * k, 1)) + 2 * macs)
     tops = torch_ops()
+    run = None
     if tops is not None:
         run = lambda: _op(lambda: tops.reduc_bwd(x2d, B, h, w, int(c_in), int(c_first_out), w_frag_wide, wt_frag, float(max_depth), k,
                                                  grad_out, dx2d, G, Y))
-    else:
-        run = lambda: _lib.load().bts_reduc_bwd_f32(_ptr(x2d), stride, B, h, w, int(c_in), int(c_first_out), _ptr(w_frag_wide),
-                                                    w_frag_wide.numel(), _ptr(wt_frag), wt_frag.numel(), float(max_depth), k,
-                                                    _ptr(grad_out), _ptr(dx2d), dxs, _ptr(G), _ptr(Y), _stream(x2d))
-    with torch.cuda.device(x2d.device):
-        rc = _launch("reduc_bwd_kernel<%d,%d,k%d>" % (c_in, c_first_out, k), "reduc_bwd", 4.0 * npix * macs + 12.0 * npix * k * k, nbytes, run)
-    _lib.check(rc, "bts_reduc_bwd_f32")
+    _enqueue("bts_reduc_bwd_f32", x2d,
+             (_ptr(x2d), stride, B, h, w, int(c_in), int(c_first_out), _ptr(w_frag_wide), w_frag_wide.numel(), _ptr(wt_frag),
+              wt_frag.numel(), float(max_depth), k, _ptr(grad_out), _ptr(dx2d), dxs, _ptr(G), _ptr(Y)),
+             trace=("reduc_bwd_kernel<%d,%d,k%d>" % (c_in, c_first_out, k), "reduc_bwd", 4.0 * npix * macs + 12.0 * npix * k * k, nbytes, None),
+             run=run)
 
 
 class BatchCache:
@@ -793,10 +830,8 @@ def nchw_to_nhwc(src: torch.Tensor, dst2d: torch.Tensor, relu: bool = False):
     B, Cc, H, W = src.shape
     if cview != Cc or dst2d.shape[0] != B * H * W:
         raise BtsHipError("nchw_to_nhwc: destination view shape mismatch")
-    with torch.cuda.device(src.device):
-        rc = _launch("nchw_to_nhwc_kernel", "layout", 0.0, 8.0 * src.numel(),
-                     lambda: _lib.load().bts_nchw_to_nhwc_f32(_ptr(src), B, Cc, H * W, _ptr(dst2d), stride, int(bool(relu)), _stream(src)))
-    _lib.check(rc, "bts_nchw_to_nhwc_f32")
+    _enqueue("bts_nchw_to_nhwc_f32", src, (_ptr(src), B, Cc, H * W, _ptr(dst2d), stride, int(bool(relu))),
+             trace=("nchw_to_nhwc_kernel", "layout", 0.0, 8.0 * src.numel(), None))
     return dst2d
 
 
@@ -805,9 +840,7 @@ def nhwc_to_nchw(src2d: torch.Tensor, B: int, H: int, W: int) -> torch.Tensor:
     if src2d.shape[0] != B * H * W:
         raise BtsHipError("nhwc_to_nchw: source view shape mismatch")
     dst = torch.empty((B, Cc, H, W), dtype=torch.float32, device=src2d.device)
-    with torch.cuda.device(src2d.device):
-        rc = _lib.load().bts_nhwc_to_nchw_f32(_ptr(src2d), stride, B, Cc, H * W, _ptr(dst), _stream(src2d))
-    _lib.check(rc, "bts_nhwc_to_nchw_f32")
+    _enqueue("bts_nhwc_to_nchw_f32", src2d, (_ptr(src2d), stride, B, Cc, H * W, _ptr(dst)))
     return dst
 
 
@@ -909,19 +942,10 @@ def upconv_combine(taps2d: torch.Tensor, B: int, h: int, w: int, c: int, y2d: to
     if tc < 9 * c or yc != c or c % 4 or taps2d.shape[0] != B * h * w or y2d.shape[0] != 4 * B * h * w:
         raise BtsHipError("upconv_combine: views %s / %s do not fit B=%d %dx%d c=%d"
                           % (tuple(taps2d.shape), tuple(y2d.shape), B, h, w, c))
-    es = eb = None
-    if e2 is not None:
-        es, eb = e2
-        _need(es, "upconv_combine")
-        _need(eb, "upconv_combine")
-        if es.numel() < c or eb.numel() < c:
-            raise BtsHipError("upconv_combine: e2 vectors need %d elements" % c)
+    es, eb = _e2_vectors(e2, c, "upconv_combine")
     npx = B * h * w
-    with torch.cuda.device(taps2d.device):
-        rc = _launch("upconv_combine_kernel", tag, 0.0, 4.0 * (9 * npx * c + 4 * npx * c),
-                     lambda: _lib.load().bts_upconv_combine_f32(_ptr(taps2d), ts, B, h, w, c, _ptr(es), _ptr(eb), int(act),
-                                                                _ptr(y2d), ys, _stream(taps2d)))
-    _lib.check(rc, "bts_upconv_combine_f32")
+    _enqueue("bts_upconv_combine_f32", taps2d, (_ptr(taps2d), ts, B, h, w, c, _ptr(es), _ptr(eb), int(act), _ptr(y2d), ys),
+             trace=("upconv_combine_kernel", tag, 0.0, 4.0 * (9 * npx * c + 4 * npx * c), None))
     return y2d
 
 
@@ -1013,24 +1037,13 @@ def upconv_up9_reference(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     return out[:, :, 1:2 * H + 1, 1:2 * W + 1].contiguous()
 
 
-class Up9Plan(tuple):
-    """(bm, bn, workgroups per frame) of bts_upconv_up9_plan; all 0 = the layer stays on the sub-pixel path."""
-    bm = property(lambda self: self[0])
-    bn = property(lambda self: self[1])
-    workgroups = property(lambda self: self[2])
-    eligible = property(lambda self: self[0] > 0)
+Up9Plan = TilePlan            # of bts_upconv_up9_plan; all 0 = the layer stays on the sub-pixel path
 
 
 def upconv_up9_plan(h: int, w: int, c_in: int, c_out: int, precision=None, fill_frames: Optional[int] = None) -> Up9Plan:
     """Should this upconv take upconv_up9_forward?  Host-only query (bts_upconv_up9_plan); ``precision`` / ``fill_frames``
     default to the launch_config in force."""
-    ff, pr = current_launch_config()
-    if precision is not None:
-        if precision not in _PRECISIONS:
-            raise BtsHipError("upconv_up9_plan: precision must be 'fp32' / 0, 'bf16x3' / 1 or 'bf16' / 2")
-        pr = _PRECISIONS[precision]
-    if fill_frames is not None:
-        ff = int(fill_frames)
+    ff, pr = _resolve_launch(precision, fill_frames, "upconv_up9_plan")
     bm, bn, wgs = C.c_int(0), C.c_int(0), C.c_long(0)
     _lib.check(_lib.load_real().bts_upconv_up9_plan(int(h), int(w), int(c_in), int(c_out), int(pr), int(ff), C.byref(bm), C.byref(bn),
                                                      C.byref(wgs)), "bts_upconv_up9_plan")
@@ -1051,15 +1064,8 @@ def upconv_up9_forward(x2d: torch.Tensor, B: int, h: int, w: int, u: torch.Tenso
                           % (tuple(x2d.shape), tuple(y2d.shape), B, h, w, c_in, c_out))
     if u.numel() != 36 * c_in * c_out or not u.is_contiguous():
         raise BtsHipError("upconv_up9_forward: u must come from pack_upconv_up9 (36 * c_in * c_out floats)")
-    if act not in (ACT_NONE, ACT_RELU, ACT_ELU):
-        raise BtsHipError("upconv_up9_forward: act must be none, ReLU or ELU")
-    es = eb = None
-    if e2 is not None:
-        es, eb = e2
-        _need(es, "upconv_up9_forward")
-        _need(eb, "upconv_up9_forward")
-        if es.numel() < c_out or eb.numel() < c_out:
-            raise BtsHipError("upconv_up9_forward: e2 vectors need %d elements" % c_out)
+    _check_act3(act, "upconv_up9_forward")
+    es, eb = _e2_vectors(e2, c_out, "upconv_up9_forward")
     kern, flops, nbytes, xflops = "conv", 0.0, 0.0, None
     if _trace is not None:
         cin = c_in_real if c_in_real is not None else c_in
@@ -1069,14 +1075,11 @@ def upconv_up9_forward(x2d: torch.Tensor, B: int, h: int, w: int, u: torch.Tenso
         nbytes = 4.0 * (B * h * w * cin + 4 * B * h * w * c_out + 9 * c_out * cin)
         xflops = 2.0 * 9 * (B * n_ty * n_tx * 32) * (4 * c_out) * c_in              # what the kernel issues, ragged tiles included
     tops = torch_ops()
+    run = None
     if tops is not None:
         run = lambda: _op(lambda: tops.upconv_up9(x2d, u, es, eb, y2d, [B, h, w, c_in, c_out, int(act)]))
-    else:
-        run = lambda: _lib.load().bts_upconv_up9_fwd_f32(_ptr(x2d), xs, B, h, w, c_in, _ptr(u), c_out, _ptr(es), _ptr(eb), int(act),
-                                                         _ptr(y2d), ys, _stream(x2d))
-    with torch.cuda.device(x2d.device):
-        rc = _launch(kern, tag, flops, nbytes, run, xflops=xflops)
-    _lib.check(rc, "bts_upconv_up9_fwd_f32")
+    _enqueue("bts_upconv_up9_fwd_f32", x2d, (_ptr(x2d), xs, B, h, w, c_in, _ptr(u), c_out, _ptr(es), _ptr(eb), int(act), _ptr(y2d), ys),
+             trace=(kern, tag, flops, nbytes, xflops), run=run)
     return y2d
 
 
@@ -1111,7 +1114,7 @@ class TailBf16Plan(tuple):
 def conv_tail_bf16_plan(h: int, w: int, c_main: int, c_out: int, n_tail: int = 1, fill_frames: Optional[int] = None) -> TailBf16Plan:
     """Should this planar-tail layer take conv_tail_bf16_forward?  Host-only query (bts_conv_tail_bf16_plan);
     ``fill_frames`` defaults to the launch_config in force."""
-    ff = current_launch_config()[0] if fill_frames is None else int(fill_frames)
+    ff, _ = _resolve_launch(None, fill_frames, "conv_tail_bf16_plan")
     bn, wgs = C.c_int(0), C.c_long(0)
     _lib.check(_lib.load_real().bts_conv_tail_bf16_plan(int(h), int(w), int(c_main), int(c_out), int(n_tail), int(ff), C.byref(bn),
                                                          C.byref(wgs)), "bts_conv_tail_bf16_plan")
@@ -1130,7 +1133,6 @@ def conv_tail_bf16_forward(x2d: torch.Tensor, B: int, h: int, w: int, w_main: to
     xs, xc = _rows2d(x2d, name)
     ys, yc = _rows2d(y2d, name)
     _need(w_tail, name)
-    _need(tail_plane, name)
     if not isinstance(w_main, torch.Tensor) or not w_main.is_cuda or w_main.dtype != torch.bfloat16:
         raise BtsHipError("conv_tail_bf16_forward: w_main must be a bfloat16 CUDA/ROCm tensor (pack_conv_tail_bf16)")
     if c_main % 32 or xc < c_main or yc != c_out or x2d.shape[0] != B * h * w or y2d.shape[0] != B * h * w:
@@ -1141,17 +1143,9 @@ def conv_tail_bf16_forward(x2d: torch.Tensor, B: int, h: int, w: int, w_main: to
     cout_pad = w_main.shape[0]
     if w_tail.numel() != 36 * cout_pad or not w_tail.is_contiguous():
         raise BtsHipError("conv_tail_bf16_forward: w_tail must be contiguous [c_out_pad, 9, 4] (pack_conv_tail_bf16)")
-    if tail_plane.numel() != B * h * w or not tail_plane.is_contiguous():
-        raise BtsHipError("conv_tail_bf16_forward: tail_plane must be one contiguous map of B*h*w floats")
-    if act not in (ACT_NONE, ACT_RELU, ACT_ELU):
-        raise BtsHipError("conv_tail_bf16_forward: act must be none, ReLU or ELU")
-    es = eb = None
-    if e2 is not None:
-        es, eb = e2
-        _need(es, name)
-        _need(eb, name)
-        if es.numel() < c_out or eb.numel() < c_out:
-            raise BtsHipError("conv_tail_bf16_forward: e2 vectors need %d elements" % c_out)
+    _dense_planes([tail_plane], B * h * w, name, at_most=1)
+    _check_act3(act, name)
+    es, eb = _e2_vectors(e2, c_out, name)
     kern, flops, nbytes, xflops = "conv", 0.0, 0.0, None
     if _trace is not None:
         cin = c_in_real if c_in_real is not None else c_main + 1
@@ -1162,14 +1156,12 @@ def conv_tail_bf16_forward(x2d: torch.Tensor, B: int, h: int, w: int, w_main: to
         tiles = B * ((h + 3) // 4) * ((w + 31) // 32)
         xflops = 2.0 * 9 * (tiles * 128) * (round_up(c_out, bn)) * (c_main + 1)     # ragged tiles included
     tops = torch_ops()
+    run = None
     if tops is not None:
         run = lambda: _op(lambda: tops.conv_tail_bf16(x2d, w_main, w_tail, tail_plane, es, eb, y2d, [B, h, w, c_main, c_out, int(act)]))
-    else:
-        run = lambda: _lib.load().bts_conv_tail_bf16_fwd_f32(_ptr(x2d), xs, B, h, w, c_main, _ptr(w_main), _ptr(w_tail), _ptr(tail_plane), 1,
-                                                             c_out, cout_pad, _ptr(es), _ptr(eb), int(act), _ptr(y2d), ys, _stream(x2d))
-    with torch.cuda.device(x2d.device):
-        rc = _launch(kern, tag, flops, nbytes, run, xflops=xflops)
-    _lib.check(rc, "bts_conv_tail_bf16_fwd_f32")
+    _enqueue("bts_conv_tail_bf16_fwd_f32", x2d,
+             (_ptr(x2d), xs, B, h, w, c_main, _ptr(w_main), _ptr(w_tail), _ptr(tail_plane), 1, c_out, cout_pad, _ptr(es), _ptr(eb),
+              int(act), _ptr(y2d), ys), trace=(kern, tag, flops, nbytes, xflops), run=run)
     return y2d
 
 
@@ -1249,25 +1241,14 @@ def conv_tail_wino_reference(x: torch.Tensor, planes: torch.Tensor, w: torch.Ten
     return out.contiguous()
 
 
-class TailWinoPlan(tuple):
-    """(bm, bn, workgroups per frame) of bts_conv_tail_wino_plan; all 0 = the layer stays on bts_conv_fwd_f32."""
-    bm = property(lambda self: self[0])
-    bn = property(lambda self: self[1])
-    workgroups = property(lambda self: self[2])
-    eligible = property(lambda self: self[0] > 0)
+TailWinoPlan = TilePlan       # of bts_conv_tail_wino_plan; all 0 = the layer stays on bts_conv_fwd_f32
 
 
 def conv_tail_wino_plan(h: int, w: int, c_main: int, c_out: int, n_tail: int = 4, precision=None,
                         fill_frames: Optional[int] = None) -> TailWinoPlan:
     """Should this planar-tail layer take conv_tail_wino_forward?  Host-only query (bts_conv_tail_wino_plan);
     ``precision`` / ``fill_frames`` default to the launch_config in force."""
-    ff, pr = current_launch_config()
-    if precision is not None:
-        if precision not in _PRECISIONS:
-            raise BtsHipError("conv_tail_wino_plan: precision must be 'fp32' / 0, 'bf16x3' / 1 or 'bf16' / 2")
-        pr = _PRECISIONS[precision]
-    if fill_frames is not None:
-        ff = int(fill_frames)
+    ff, pr = _resolve_launch(precision, fill_frames, "conv_tail_wino_plan")
     bm, bn, wgs = C.c_int(0), C.c_int(0), C.c_long(0)
     _lib.check(_lib.load_real().bts_conv_tail_wino_plan(int(h), int(w), int(c_main), int(c_out), int(n_tail), int(pr), int(ff),
                                                          C.byref(bm), C.byref(bn), C.byref(wgs)), "bts_conv_tail_wino_plan")
@@ -1286,20 +1267,13 @@ def conv_tail_wino_forward(x2d: torch.Tensor, B: int, h: int, w: int, u: torch.T
     _need(u, name)
     _need(w_tail, name)
     _need(y_nchw, name)
-    planes = list(tail_planes) if tail_planes else []
     if xc < 32 or x2d.shape[0] != B * h * w or tuple(y_nchw.shape) != (B, 32, h, w) or not y_nchw.is_contiguous():
         raise BtsHipError("conv_tail_wino_forward: views %s / %s do not fit B=%d %dx%d, 32 -> 32 channels (NCHW result)"
                           % (tuple(x2d.shape), tuple(y_nchw.shape), B, h, w))
     if u.numel() != 16 * 32 * 32 or not u.is_contiguous() or w_tail.numel() != 2 * 9 * 64 or not w_tail.is_contiguous():
         raise BtsHipError("conv_tail_wino_forward: (u, w_tail) must come from pack_conv_tail_wino")
-    if len(planes) > 4:
-        raise BtsHipError("conv_tail_wino_forward: at most four tail planes")
-    for t in planes:
-        _need(t, name)
-        if t.numel() != B * h * w or not t.is_contiguous():
-            raise BtsHipError("conv_tail_wino_forward: every tail plane must be one contiguous map of B*h*w floats")
-    if act not in (ACT_NONE, ACT_RELU, ACT_ELU):
-        raise BtsHipError("conv_tail_wino_forward: act must be none, ReLU or ELU")
+    planes = _dense_planes(tail_planes, B * h * w, name)
+    _check_act3(act, name)
     kern, flops, nbytes, xflops = "conv", 0.0, 0.0, None
     if _trace is not None:
         kern = conv_plan.tail_wino_kernel_name()
@@ -1308,11 +1282,9 @@ def conv_tail_wino_forward(x2d: torch.Tensor, B: int, h: int, w: int, u: torch.T
         windows = B * ((h + 3) // 4) * ((w + 31) // 32) * 32                        # ragged tiles included
         xflops = 2.0 * windows * 32 * (16 * 32 + 36 * 4)                            # 16 products per window (main) + the direct tail's k-step of 4
     ptrs = [_ptr(planes[j]) if j < len(planes) else C.c_void_p(0) for j in range(4)]
-    run = lambda: _lib.load().bts_conv_tail_wino_fwd_f32(_ptr(x2d), xs, B, h, w, 32, _ptr(u), _ptr(w_tail), ptrs[0], ptrs[1], ptrs[2],
-                                                         ptrs[3], len(planes), 32, int(act), _ptr(y_nchw), _stream(x2d))
-    with torch.cuda.device(x2d.device):
-        rc = _launch(kern, tag, flops, nbytes, run, xflops=xflops)
-    _lib.check(rc, "bts_conv_tail_wino_fwd_f32")
+    _enqueue("bts_conv_tail_wino_fwd_f32", x2d,
+             (_ptr(x2d), xs, B, h, w, 32, _ptr(u), _ptr(w_tail), ptrs[0], ptrs[1], ptrs[2], ptrs[3], len(planes), 32, int(act), _ptr(y_nchw)),
+             trace=(kern, tag, flops, nbytes, xflops))
     return y_nchw
 
 
@@ -1345,20 +1317,28 @@ _cfg_tls = threading.local()
 _PRECISIONS = {"fp32": 0, "bf16x3": 1, "bf16": 2, 0: 0, 1: 1, 2: 2}
 
 
+def _resolve_launch(precision, fill_frames, who: str) -> Tuple[int, int]:
+    """(fill_frames, precision) a call made now runs under: the launch_config in force with the caller's overrides
+    (``None`` keeps the enclosing value); like current_launch_config, $BTS_CONV_PRECISION=1 wins over both."""
+    ff, pr = current_launch_config()
+    if precision is not None:
+        if precision not in _PRECISIONS:
+            raise BtsHipError("%s: precision must be 'fp32' / 0, 'bf16x3' / 1 or 'bf16' / 2" % who)
+        pr = 1 if _ENV_PRECISION else _PRECISIONS[precision]
+    if fill_frames is not None:
+        ff = int(fill_frames)
+        if ff < 0 or ff > 4096:
+            raise BtsHipError("%s: fill_frames must be in 0..4096" % who)
+    return ff, pr
+
+
 class launch_config:
     """``with ops.launch_config(fill_frames=2, precision="bf16x3"): ...`` -- values for every conv_forward call issued by
     this thread inside the block; ``None`` keeps the enclosing value (library defaults outside any block)."""
 
     def __init__(self, fill_frames: Optional[int] = None, precision=None):
-        if fill_frames is not None:
-            fill_frames = int(fill_frames)
-            if fill_frames < 0 or fill_frames > 4096:
-                raise BtsHipError("launch_config: fill_frames must be in 0..4096")
-        if precision is not None:
-            if precision not in _PRECISIONS:
-                raise BtsHipError("launch_config: precision must be 'fp32' / 0, 'bf16x3' / 1 or 'bf16' / 2")
-            precision = _PRECISIONS[precision]
-        self._new = (fill_frames, precision)
+        _resolve_launch(precision, fill_frames, "launch_config")
+        self._new = (None if fill_frames is None else int(fill_frames), None if precision is None else _PRECISIONS[precision])
 
     def __enter__(self):
         self._prev_raw = getattr(_cfg_tls, "value", None)
@@ -1465,8 +1445,7 @@ def pack_wino_weight(w_packed: torch.Tensor, c_in_ld: int, n_tail: int = 0, c_ou
     cop = w_packed.shape[0]
     if w_packed.dim() != 2 or not w_packed.is_contiguous() or w_packed.shape[1] != round_up(9 * c_in_ld, 32):
         raise BtsHipError("pack_wino_weight: needs a packed 3x3 weight [c_out_pad, round_up(9 * c_in_ld, 32)]")
-    lib = _lib.load_real()
-    n = lib.bts_pack_wino_floats(cop, c_in_ld, n_tail, c_out16)
+    n = _lib.load_real().bts_pack_wino_floats(cop, c_in_ld, n_tail, c_out16)
     if n <= 0:
         raise BtsHipError("pack_wino_weight: needs a 3x3 weight whose buffer channels are whole 32-channel chunks"
                           " (and c_out16 a multiple of 16 within the packed rows)")
@@ -1474,9 +1453,7 @@ def pack_wino_weight(w_packed: torch.Tensor, c_in_ld: int, n_tail: int = 0, c_ou
         out = torch.empty(n, dtype=torch.float32, device=w_packed.device)
     elif out.numel() != n or not out.is_contiguous() or out.device != w_packed.device:
         raise BtsHipError("pack_wino_weight: `out` does not fit this weight")
-    with torch.cuda.device(w_packed.device):
-        _lib.check(lib.bts_pack_wino_f32(w_packed.data_ptr(), cop, w_packed.shape[1], c_in_ld, n_tail, c_out16, out.data_ptr(),
-                                         _stream(w_packed)), "bts_pack_wino_f32")
+    _enqueue("bts_pack_wino_f32", w_packed, (w_packed.data_ptr(), cop, w_packed.shape[1], c_in_ld, n_tail, c_out16, out.data_ptr()))
     return out
 
 
@@ -1537,12 +1514,9 @@ def _conv_describe(x2d, B, h_in, w_in, w_packed, c_out, ksize, dil, up, c_in_ld,
     if c_in_ld % 4 or (c_in_ld - (4 if n_tail else 0)) * n_bundles > xc or x2d.shape[0] != B * h_in * w_in:
         raise BtsHipError("conv_forward: bad input view (c_in_ld %d, view %s)" % (c_in_ld, tuple(x2d.shape)))
     if n_tail:
-        if n_tail > 4 or ksize != 3 or stride != 1 or dil != 1 or up != 1 or subpixel or n_bundles > 1:
-            raise BtsHipError("conv_forward: tail_planes need a plain 3x3 / stride 1 / dilation 1 convolution and at most 4 planes")
-        for j, t in enumerate(tail_planes):
-            _need(t, "conv_forward")
-            if t.numel() != B * h_in * w_in or not t.is_contiguous():
-                raise BtsHipError("conv_forward: every tail plane must be a contiguous [B,1,h_in,w_in] map")
+        if ksize != 3 or stride != 1 or dil != 1 or up != 1 or subpixel or n_bundles > 1:
+            raise BtsHipError("conv_forward: tail_planes need a plain 3x3 / stride 1 / dilation 1 convolution")
+        for j, t in enumerate(_dense_planes(tail_planes, B * h_in * w_in, "conv_forward")):
             d.tail_planes[j] = t.data_ptr()
     H, W = conv_out_hw(h_in, w_in, ksize, dil, stride, pad, up)
     d.x, d.w = x2d.data_ptr(), w_packed.data_ptr()
@@ -1678,18 +1652,18 @@ def conv_forward(x2d: torch.Tensor, B: int, h_in: int, w_in: int, w_packed: torc
     d, out, keep = _conv_describe(x2d, B, h_in, w_in, w_packed, c_out, ksize, dil, up, c_in_ld, pre, pre_relu, e1, act, e2,
                                   y2d, y_nchw, stride, pad, y2_2d, subpixel, splitk_ws, res2d, n_bundles, tail_planes)
     wsplit_t, uw_t = _conv_derived_weights(d, w_packed, keep)
-    trace = ("conv", 0.0, 0.0, None) if _trace is None else _conv_trace_accounting(d, c_in_real, algo_flops)
+    trace = None
+    if _trace is not None:
+        kern, flops, nbytes, xflops = _conv_trace_accounting(d, c_in_real, algo_flops)
+        trace = (kern, tag, flops, nbytes, xflops)
     tops = torch_ops()
+    run = None
     if tops is not None:
         geom = [getattr(d, f) for f in _GEOM_FIELDS]
         (pre_s, pre_b), (e1_s, e1_b), (e2_s, e2_b) = (p if p is not None else (None, None) for p in (pre, e1, e2))
         run = lambda: _op(lambda: tops.conv_fwd(x2d, w_packed, pre_s, pre_b, e1_s, e1_b, e2_s, e2_b, out, y2_2d, res2d, splitk_ws,
                                                 list(tail_planes) if tail_planes else [], wsplit_t, uw_t, geom))
-    else:
-        run = lambda: _lib.load().bts_conv_fwd_f32(C.byref(d), _stream(x2d))
-    with torch.cuda.device(x2d.device):
-        rc = _launch(trace[0], tag, trace[1], trace[2], run, xflops=trace[3])
-    _lib.check(rc, "bts_conv_fwd_f32")
+    _enqueue("bts_conv_fwd_f32", x2d, (C.byref(d),), trace=trace, run=run)
     return out
 
 
@@ -1706,7 +1680,7 @@ def _wgrad_desc(B: int, h_in: int, w_in: int, c_in: int, c_out: int, ksize: int,
 def conv_wgrad_plan_desc(d: ConvWgradDesc) -> Tuple[int, int, int, int]:
     """bts_conv_wgrad_plan_f32 on a filled descriptor: (bm, bn, split, pix_per_split).  Host arithmetic only."""
     bm, bn, split, pps = C.c_int(0), C.c_int(0), C.c_long(0), C.c_long(0)
-    _lib.check(_lib.load().bts_conv_wgrad_plan_f32(C.byref(d), C.byref(bm), C.byref(bn), C.byref(split), C.byref(pps)),
+    _lib.check(_lib.load_real().bts_conv_wgrad_plan_f32(C.byref(d), C.byref(bm), C.byref(bn), C.byref(split), C.byref(pps)),
                "bts_conv_wgrad_plan_f32")
     return bm.value, bn.value, split.value, pps.value
 
@@ -1768,9 +1742,7 @@ def conv_wgrad(x2d: torch.Tensor, B: int, h_in: int, w_in: int, c_in: int, dy2d:
     taps = ksize * ksize
     flops = 2.0 * B * H * W * c_out * c_in * taps * max(n_bundles, 1)
     nbytes = 4.0 * (B * h_in * w_in * c_in + B * H * W * c_out + taps * c_out * c_in) * max(n_bundles, 1)
-    with torch.cuda.device(x2d.device):
-        rc = _launch("conv_wgrad_kernel", tag, flops, nbytes, lambda: _lib.load().bts_conv_wgrad_f32(C.byref(d), _stream(x2d)))
-    _lib.check(rc, "bts_conv_wgrad_f32")
+    _enqueue("bts_conv_wgrad_f32", x2d, (C.byref(d),), trace=("conv_wgrad_kernel", tag, flops, nbytes, None))
     return dw
 
 
@@ -1840,7 +1812,7 @@ def upconv_train_pack(weights: Sequence[torch.Tensor], fwd: Sequence[torch.Tenso
     import numpy as np
     if not weights:
         raise BtsHipError("upconv_train_pack: no weights")
-    lib = _lib.load()
+    lib = _lib.load_real()
     dev = weights[0].device
     if table is None:
         rows, first = [], 0
@@ -1856,24 +1828,18 @@ def upconv_train_pack(weights: Sequence[torch.Tensor], fwd: Sequence[torch.Tenso
             first += int(lib.bts_upconv_train_pack_blocks(fs[1], fs[2], ds[0], ds[1]))
         table = (torch.from_numpy(np.asarray(rows, dtype=np.int64)).to(dev), first)
     tab, blocks = table
-    with torch.cuda.device(dev):
-        rc = _launch("upconv_train_pack_kernel", "pack", 0.0, 0.0,
-                     lambda: lib.bts_upconv_train_pack_f32(tab.data_ptr(), tab.shape[0], blocks, _stream(weights[0])))
-    _lib.check(rc, "bts_upconv_train_pack_f32")
+    _enqueue("bts_upconv_train_pack_f32", weights[0], (tab.data_ptr(), tab.shape[0], blocks),
+             trace=("upconv_train_pack_kernel", "pack", 0.0, 0.0, None))
     return table
 
 
 def upconv_dgrad_plan(B: int, h: int, w: int, c_out: int, c_in: int, splitk_ws_floats: int = 0, precision=None,
                       fill_frames: Optional[int] = None) -> Tuple[int, int, int, bool]:
     """Which kernel upconv_dgrad will launch: (bm, bn, kind, splits K).  Host-only (bts_upconv_dgrad_plan)."""
-    ff, pr = current_launch_config()
-    if precision is not None:
-        pr = _PRECISIONS[precision]
-    if fill_frames is not None:
-        ff = int(fill_frames)
+    ff, pr = _resolve_launch(precision, fill_frames, "upconv_dgrad_plan")
     bm, bn, kind = C.c_int(0), C.c_int(0), C.c_int(0)
-    _lib.check(_lib.load().bts_upconv_dgrad_plan(B, h, w, c_out, c_in, int(pr), int(ff), int(splitk_ws_floats), C.byref(bm), C.byref(bn),
-                                                 C.byref(kind)), "bts_upconv_dgrad_plan")
+    _lib.check(_lib.load_real().bts_upconv_dgrad_plan(B, h, w, c_out, c_in, int(pr), int(ff), int(splitk_ws_floats), C.byref(bm),
+                                                      C.byref(bn), C.byref(kind)), "bts_upconv_dgrad_plan")
     return bm.value, bn.value, kind.value & 15, bool(kind.value & 16)
 
 
@@ -1905,12 +1871,8 @@ def upconv_dgrad(dy2d: torch.Tensor, B: int, h: int, w: int, w_dgrad: torch.Tens
         kern = "conv_fwd_kernel<%d,%d,k4s2>%s" % (bm, bn, "+splitk" if sk else "")
     flops = 2.0 * 36 * B * h * w * c_out * c_in               # the reference's 3x3 adjoint on the upsampled map
     nbytes = 4.0 * (4 * B * h * w * c_out + B * h * w * c_in + 16 * c_out * c_in)
-    with torch.cuda.device(dy2d.device):
-        rc = _launch(kern, tag, flops, nbytes,
-                     lambda: _lib.load().bts_upconv_dgrad_f32(_ptr(dy2d), ds, B, h, w, c_out, _ptr(w_dgrad), c_in, _ptr(dx2d), xs, int(pr),
-                                                              int(ff), ws_ptr, ws_n, _stream(dy2d)),
-                     xflops=2.0 * 16 * B * h * w * c_out * c_in)
-    _lib.check(rc, "bts_upconv_dgrad_f32")
+    _enqueue("bts_upconv_dgrad_f32", dy2d, (_ptr(dy2d), ds, B, h, w, c_out, _ptr(w_dgrad), c_in, _ptr(dx2d), xs, int(pr), int(ff), ws_ptr, ws_n),
+             trace=(kern, tag, flops, nbytes, 2.0 * 16 * B * h * w * c_out * c_in))
     return dx2d
 
 
@@ -1918,8 +1880,8 @@ def upconv_wgrad_plan(B: int, h: int, w: int, c_in: int, c_out: int, ws_floats: 
     """Tile and pixel split upconv_wgrad will run under a workspace of ``ws_floats`` floats: (bm, bn, split,
     pix_per_split); the launch writes split * 16 * c_out * c_in floats of it.  Host-only (bts_upconv_wgrad_plan_f32)."""
     bm, bn, split, pps = C.c_int(0), C.c_int(0), C.c_long(0), C.c_long(0)
-    _lib.check(_lib.load().bts_upconv_wgrad_plan_f32(B, h, w, c_in, c_out, int(ws_floats), C.byref(bm), C.byref(bn), C.byref(split),
-                                                     C.byref(pps)), "bts_upconv_wgrad_plan_f32")
+    _lib.check(_lib.load_real().bts_upconv_wgrad_plan_f32(B, h, w, c_in, c_out, int(ws_floats), C.byref(bm), C.byref(bn), C.byref(split),
+                                                          C.byref(pps)), "bts_upconv_wgrad_plan_f32")
     return bm.value, bn.value, split.value, pps.value
 
 
@@ -1941,12 +1903,8 @@ def upconv_wgrad(x2d: torch.Tensor, B: int, h: int, w: int, c_in: int, dy2d: tor
     dw = torch.empty((c_out, 9, c_in), dtype=torch.float32, device=x2d.device)
     flops = 2.0 * 36 * B * h * w * c_out * c_in
     nbytes = 4.0 * (B * h * w * c_in + 4 * B * h * w * c_out + 9 * c_out * c_in)
-    with torch.cuda.device(x2d.device):
-        rc = _launch("upconv_wgrad_kernel", tag, flops, nbytes,
-                     lambda: _lib.load().bts_upconv_wgrad_f32(_ptr(x2d), xs, B, h, w, c_in, _ptr(dy2d), ds, c_out, _ptr(dw), _ptr(ws),
-                                                              ws.numel(), _stream(x2d)),
-                     xflops=2.0 * 16 * B * h * w * c_out * c_in)
-    _lib.check(rc, "bts_upconv_wgrad_f32")
+    _enqueue("bts_upconv_wgrad_f32", x2d, (_ptr(x2d), xs, B, h, w, c_in, _ptr(dy2d), ds, c_out, _ptr(dw), _ptr(ws), ws.numel()),
+             trace=("upconv_wgrad_kernel", tag, flops, nbytes, 2.0 * 16 * B * h * w * c_out * c_in))
     return dw
 
 
@@ -1956,7 +1914,7 @@ def conv_wgrad_batch_plan_descs(descs: Sequence[ConvWgradDesc], bases: Sequence[
     """bts_conv_wgrad_batch_plan_f32 on filled descriptors.  ``bases``: (address, bytes) of the ranges every pointer of
     every descriptor must lie in.  Returns one (bm, bn, split, pix_per_split, ws_offset) per problem, in the order
     given (ws_offset -1: unsplit); with ``with_table`` also the host table.  Host arithmetic only."""
-    lib = _lib.load()
+    lib = _lib.load_real()
     n, nb = len(descs), len(bases)
     arr = (ConvWgradDesc * max(n, 1))(*descs)
     bp = (C.c_void_p * max(nb, 1))(*[int(a) for a, _ in bases])
@@ -2067,17 +2025,14 @@ class WgradBatch:
             if ws.numel() < self.ws_used or not ws.is_contiguous() or ws.device != self.device:
                 raise BtsHipError("WgradBatch.run: the workspace must hold %d floats" % self.ws_used)
         bp = (C.c_void_p * len(bases))(*[b.data_ptr() for b in bases])
-        with torch.cuda.device(self.device):
-            rc = _launch("conv_wgrad_batch_kernel", self.tag, self.flops, self.nbytes,
-                         lambda: _lib.load().bts_conv_wgrad_batch_f32(self._table, self._table_dev.data_ptr(), self.n, bp, len(bases),
-                                                                      _ptr(ws), _stream(bases[0])))
-        _lib.check(rc, "bts_conv_wgrad_batch_f32")
+        _enqueue("bts_conv_wgrad_batch_f32", bases[0], (self._table, self._table_dev.data_ptr(), self.n, bp, len(bases), _ptr(ws)),
+                 trace=("conv_wgrad_batch_kernel", self.tag, self.flops, self.nbytes, None))
         return [bases[j].view(-1)[off:off + int(torch.Size(sh).numel())].view(sh) for j, off, sh in self._dw]
 
 
 # ------------------------------------------------------------------------------ train-mode BN
 def bn_train_ws_floats(npix: int, C: int) -> int:
-    return int(_lib.load().bts_bn_train_ws_floats(npix, C))
+    return int(_lib.load_real().bts_bn_train_ws_floats(npix, C))
 
 
 def bn_train_stats(x2d: torch.Tensor, C: int, gamma, beta, eps: float, momentum: float, running_mean, running_var,
@@ -2096,13 +2051,10 @@ def bn_train_stats(x2d: torch.Tensor, C: int, gamma, beta, eps: float, momentum:
             raise BtsHipError("bn_train_stats: out must be a [4, %d] view with unit channel stride and 16-byte aligned rows" % C)
     _need(ws, "bn_train_stats")
     npix = x2d.shape[0]
-    with torch.cuda.device(x2d.device):
-        rc = _launch("bn_stats_kernel", "bn.stats", 3.0 * npix * C, 4.0 * npix * C,
-                     lambda: _lib.load().bts_bn_train_stats_f32(
-                         x2d.data_ptr(), xs, npix, C, _ptr(gamma), _ptr(beta), float(eps), float(momentum),
-                         _ptr(running_mean), _ptr(running_var), ws.data_ptr(), ws.numel(), out[0].data_ptr(),
-                         out[1].data_ptr(), out[2].data_ptr(), out[3].data_ptr(), _stream(x2d)))
-    _lib.check(rc, "bts_bn_train_stats_f32")
+    _enqueue("bts_bn_train_stats_f32", x2d,
+             (x2d.data_ptr(), xs, npix, C, _ptr(gamma), _ptr(beta), float(eps), float(momentum), _ptr(running_mean), _ptr(running_var),
+              ws.data_ptr(), ws.numel(), out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), out[3].data_ptr()),
+             trace=("bn_stats_kernel", "bn.stats", 3.0 * npix * C, 4.0 * npix * C, None))
     return out[0], out[1], out[2], out[3]
 
 
@@ -2111,12 +2063,8 @@ def bn_apply(x2d: torch.Tensor, C: int, scale: torch.Tensor, shift: torch.Tensor
     xs, _ = _rows2d(x2d, "bn_apply")
     ys, _ = _rows2d(y2d, "bn_apply")
     npix = x2d.shape[0]
-    with torch.cuda.device(x2d.device):
-        rc = _launch("bn_apply_kernel", "bn.apply", 2.0 * npix * C, 8.0 * npix * C,
-                     lambda: _lib.load().bts_bn_apply_nhwc_f32(x2d.data_ptr(), xs, npix, C, scale.data_ptr(),
-                                                               shift.data_ptr(), int(bool(relu)), y2d.data_ptr(), ys,
-                                                               _stream(x2d)))
-    _lib.check(rc, "bts_bn_apply_nhwc_f32")
+    _enqueue("bts_bn_apply_nhwc_f32", x2d, (x2d.data_ptr(), xs, npix, C, scale.data_ptr(), shift.data_ptr(), int(bool(relu)), y2d.data_ptr(), ys),
+             trace=("bn_apply_kernel", "bn.apply", 2.0 * npix * C, 8.0 * npix * C, None))
     return y2d
 
 
@@ -2132,13 +2080,10 @@ def bn_train_backward(x2d: torch.Tensor, dy2d: torch.Tensor, C: int, mean, invst
     dxs = 0
     if dx2d is not None:
         dxs, _ = _rows2d(dx2d, "bn_train_backward")
-    with torch.cuda.device(x2d.device):
-        rc = _launch("bn_bwd_kernels", "bn.bwd", 10.0 * npix * C, 20.0 * npix * C,
-                     lambda: _lib.load().bts_bn_train_bwd_f32(
-                         x2d.data_ptr(), xs, dy2d.data_ptr(), ds, npix, C, mean.data_ptr(), invstd.data_ptr(),
-                         scale.data_ptr(), shift.data_ptr(), int(bool(relu)), ws.data_ptr(), ws.numel(),
-                         g[0].data_ptr(), g[1].data_ptr(), _ptr(dx2d), dxs, _stream(x2d)))
-    _lib.check(rc, "bts_bn_train_bwd_f32")
+    _enqueue("bts_bn_train_bwd_f32", x2d,
+             (x2d.data_ptr(), xs, dy2d.data_ptr(), ds, npix, C, mean.data_ptr(), invstd.data_ptr(), scale.data_ptr(), shift.data_ptr(),
+              int(bool(relu)), ws.data_ptr(), ws.numel(), g[0].data_ptr(), g[1].data_ptr(), _ptr(dx2d), dxs),
+             trace=("bn_bwd_kernels", "bn.bwd", 10.0 * npix * C, 20.0 * npix * C, None))
     return g[0], g[1]
 
 
@@ -2149,15 +2094,8 @@ def pack_planes(planes: Sequence[torch.Tensor], dst2d: torch.Tensor):
     if n != len(planes) or not 1 <= n <= 4:
         raise BtsHipError("pack_planes: need 1..4 planes matching the destination slice")
     npix = dst2d.shape[0]
-    for p in planes:
-        _need(p, "pack_planes")
-        if p.numel() != npix or not p.is_contiguous():
-            raise BtsHipError("pack_planes: plane size mismatch")
-    ptrs = [_ptr(p) for p in planes] + [C.c_void_p(0)] * (4 - n)
-    with torch.cuda.device(dst2d.device):
-        rc = _lib.load().bts_pack_planes_f32(ptrs[0], ptrs[1], ptrs[2], ptrs[3], n, npix, _ptr(dst2d), stride,
-                                             _stream(dst2d))
-    _lib.check(rc, "bts_pack_planes_f32")
+    ptrs = [_ptr(p) for p in _dense_planes(planes, npix, "pack_planes")] + [C.c_void_p(0)] * (4 - n)
+    _enqueue("bts_pack_planes_f32", dst2d, (ptrs[0], ptrs[1], ptrs[2], ptrs[3], n, npix, _ptr(dst2d), stride))
     return dst2d
 
 
@@ -2177,11 +2115,8 @@ def get_depth_forward(iconv1: torch.Tensor, weight: torch.Tensor, max_depth: flo
         out = torch.empty((B, 1, H, W), dtype=torch.float32, device=iconv1.device)
     elif tuple(out.shape) != (B, 1, H, W) or not out.is_contiguous():
         raise BtsHipError("get_depth_forward: out must be contiguous [B,1,H,W]")
-    with torch.cuda.device(iconv1.device):
-        rc = _launch("get_depth_kernel<%d>" % Cc, "get_depth", 2.0 * 9 * Cc * B * H * W, 4.0 * (Cc + 1) * B * H * W,
-                     lambda: _lib.load().bts_get_depth_f32(_ptr(iconv1), _ptr(weight), B, Cc, H, W, float(max_depth),
-                                                           _ptr(focal), _ptr(out), _stream(iconv1)))
-    _lib.check(rc, "bts_get_depth_f32")
+    _enqueue("bts_get_depth_f32", iconv1, (_ptr(iconv1), _ptr(weight), B, Cc, H, W, float(max_depth), _ptr(focal), _ptr(out)),
+             trace=("get_depth_kernel<%d>" % Cc, "get_depth", 2.0 * 9 * Cc * B * H * W, 4.0 * (Cc + 1) * B * H * W, None))
     return out
 
 
@@ -2199,11 +2134,8 @@ def maxpool3x3s2(src2d: torch.Tensor, B: int, h: int, w: int, dst2d: torch.Tenso
             raise BtsHipError("maxpool3x3s2: second destination mismatch")
         d2p = _ptr(dst2_2d)
     nbytes = 4.0 * Cc * (B * h * w + B * ho * wo * (2 if dst2_2d is not None else 1))
-    with torch.cuda.device(src2d.device):
-        rc = _launch("maxpool3x3s2_kernel", "encoder_pool", 0.0, nbytes,
-                     lambda: _lib.load().bts_maxpool3x3s2_nhwc_f32(_ptr(src2d), ss, B, h, w, Cc, _ptr(dst2d), ds, d2p, d2s,
-                                                                   _stream(src2d)))
-    _lib.check(rc, "bts_maxpool3x3s2_nhwc_f32")
+    _enqueue("bts_maxpool3x3s2_nhwc_f32", src2d, (_ptr(src2d), ss, B, h, w, Cc, _ptr(dst2d), ds, d2p, d2s),
+             trace=("maxpool3x3s2_kernel", "encoder_pool", 0.0, nbytes, None))
     return dst2d
 
 
@@ -2216,9 +2148,6 @@ def bn_relu_avgpool2(src2d: torch.Tensor, B: int, h: int, w: int, scale: torch.T
     if dc != Cc or src2d.shape[0] != B * h * w or dst2d.shape[0] != B * (h // 2) * (w // 2) or scale.numel() != Cc:
         raise BtsHipError("bn_relu_avgpool2: shape mismatch")
     nbytes = 4.0 * Cc * (B * h * w + B * (h // 2) * (w // 2))
-    with torch.cuda.device(src2d.device):
-        rc = _launch("bn_relu_avgpool2_kernel", "encoder_pool", 0.0, nbytes,
-                     lambda: _lib.load().bts_bn_relu_avgpool2_nhwc_f32(_ptr(src2d), ss, B, h, w, Cc, _ptr(scale), _ptr(shift),
-                                                                       _ptr(dst2d), ds, _stream(src2d)))
-    _lib.check(rc, "bts_bn_relu_avgpool2_nhwc_f32")
+    _enqueue("bts_bn_relu_avgpool2_nhwc_f32", src2d, (_ptr(src2d), ss, B, h, w, Cc, _ptr(scale), _ptr(shift), _ptr(dst2d), ds),
+             trace=("bn_relu_avgpool2_kernel", "encoder_pool", 0.0, nbytes, None))
     return dst2d

@@ -131,7 +131,7 @@ class NativeAdamW(torch.optim.Optimizer):
 
     def _plan_launches(self, cache, ptrs, q, device):
         """(Re)fill the host tables from the current pointers and hyper indices and send them to the device."""
-        lib = _lib.load()
+        lib = _lib.load_real()
         items = cache["items"]
         items["p"], items["g"], items["m"], items["v"] = ptrs[:, 0], ptrs[:, 1], ptrs[:, 2], ptrs[:, 3]
         items["hyper"] = q % MAX_HYPER
@@ -218,8 +218,6 @@ class NativeAdamW(torch.optim.Optimizer):
         with torch.cuda.device(device):
             if cache["ptrs"] is None or not np.array_equal(cache["ptrs"], ptrs) or not np.array_equal(cache["q"], q):
                 self._plan_launches(cache, ptrs, q, device)
-            lib = _lib.load()
-            stream = torch.cuda.current_stream(device).cuda_stream
             skip_ptr = skip.data_ptr() if skip is not None else None
             self.launches = 0
             for L in cache["launches"]:
@@ -231,10 +229,8 @@ class NativeAdamW(torch.optim.Optimizer):
                     grp = self.param_groups[gi]
                     hy[k].lr, hy[k].beta1, hy[k].beta2 = float(grp["lr"]), float(grp["betas"][0]), float(grp["betas"][1])
                     hy[k].eps, hy[k].weight_decay, hy[k].step = float(grp["eps"]), float(grp["weight_decay"]), stepv
-                rc = ops._launch("adamw_step_kernel", "optim.adamw", 0.0, 28.0 * int(cache["items"]["numel"].sum()),
-                                 lambda: lib.bts_adamw_step_f32(L["dev"].data_ptr(), L["n"], L["blocks"], C.addressof(hy), len(sel),
-                                                                skip_ptr, stream))
-                _lib.check(rc, "bts_adamw_step_f32")
+                ops._enqueue("bts_adamw_step_f32", L["dev"], (L["dev"].data_ptr(), L["n"], L["blocks"], C.addressof(hy), len(sel), skip_ptr),
+                             trace=("adamw_step_kernel", "optim.adamw", 0.0, 28.0 * int(cache["items"]["numel"].sum()), None))
                 self.launches += 1
         # the kernel wrote through raw pointers: tell autograd, the packer and the eval-mode packs
         before = [p._version for p, _, _ in active]

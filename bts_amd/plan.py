@@ -25,22 +25,7 @@ from . import ops as ops_mod
 from ._lib import BtsHipError, ConvDesc
 
 # entry point -> (BTS_OP_* kind, member name in the bts_op union); argument order = the C prototypes (stream excluded)
-_KINDS = {
-    "bts_conv_fwd_f32": (1, "conv"),
-    "bts_reduc_fwd_f32": (2, "reduc"),
-    "bts_reduc_lpg_fwd_f32": (3, "reduc_lpg"),
-    "bts_lpg_fused_fwd_f32": (4, "lpg_fused"),
-    "bts_nchw_to_nhwc_f32": (5, "nchw_to_nhwc"),
-    "bts_nhwc_to_nchw_f32": (6, "nhwc_to_nchw"),
-    "bts_maxpool3x3s2_nhwc_f32": (7, "maxpool"),
-    "bts_bn_relu_avgpool2_nhwc_f32": (8, "avgpool"),
-    "bts_get_depth_f32": (9, "get_depth"),
-    "bts_lpg_fwd_f32": (10, "lpg"),
-    "bts_upconv_combine_f32": (11, "upconv_combine"),
-    "bts_upconv_up9_fwd_f32": (12, "upconv_up9"),
-    "bts_conv_tail_bf16_fwd_f32": (13, "conv_tail_bf16"),
-    "bts_conv_tail_wino_fwd_f32": (14, "conv_tail_wino"),
-}
+_KINDS = {name: e.plan for name, e in _lib.ABI.items() if e.plan}
 
 _structs: Dict[str, type] = {}
 _BtsOp = None
@@ -105,12 +90,8 @@ class _Proxy:
 
     def __getattr__(self, name):
         real = getattr(self._lib, name)
-        if not name.startswith("bts_") or name in ("bts_hip_error_string", "bts_hip_abi_version", "bts_conv_plan_f32",
-                                                  "bts_conv_wgrad_plan_f32", "bts_conv_wgrad_batch_table_bytes",
-                                                  "bts_conv_wgrad_batch_plan_f32", "bts_eval_ws_doubles", "bts_bn_train_ws_floats", "bts_pack_weights_blocks",
-                                                  "bts_depth_loss_ws_doubles", "bts_adamw_table_bytes", "bts_adamw_flat_span",
-                                                  "bts_adamw_plan_f32", "bts_upconv_up9_plan", "bts_conv_tail_bf16_plan", "bts_conv_tail_wino_plan", "bts_upconv_dgrad_plan",
-                                                  "bts_upconv_wgrad_plan_f32", "bts_upconv_train_pack_blocks"):
+        entry = _lib.ABI.get(name)
+        if not name.startswith("bts_") or (entry is not None and entry.role == _lib.QUERY):    # host arithmetic: nothing to record
             return real
         if name not in _KINDS:
             def passthrough(*args):

@@ -119,7 +119,7 @@ class WeightPacker:
     def _table_for(self, items):
         import numpy as np
         from . import _lib
-        lib = _lib.load()
+        lib = _lib.load_real()
         table, first = [], 0
         for e in items:
             src, dst = e["ptr"], e["dst"].data_ptr()
@@ -130,13 +130,8 @@ class WeightPacker:
         return torch.from_numpy(np.asarray(table, dtype=np.int64)).to(items[0]["dst"].device), first, len(table)
 
     def _launch(self, items, table, blocks, n_rows):
-        from . import _lib
-        dev = items[0]["dst"].device
-        with torch.cuda.device(dev):
-            rc = ops._launch("pack_weights_kernel", "pack", 0.0, 0.0,
-                             lambda: _lib.load().bts_pack_weights_f32(table.data_ptr(), n_rows, blocks,
-                                                                      torch.cuda.current_stream(dev).cuda_stream))
-        _lib.check(rc, "bts_pack_weights_f32")
+        ops._enqueue("bts_pack_weights_f32", items[0]["dst"], (table.data_ptr(), n_rows, blocks),
+                     trace=("pack_weights_kernel", "pack", 0.0, 0.0, None))
         for e in items:
             e["version"] = e["wref"]()._version
             # derived forms cached on the packed buffer (Winograd U, bf16 planes: ops.conv_forward) are now stale

@@ -42,8 +42,7 @@ def test_symbols_are_exported_declared_and_host_only_ones_bypass_the_recorder():
     lib = _lib.load_real()
     for name in NAMES:
         assert hasattr(raw, name), name
-        assert name in _lib.SYMBOLS
-        assert getattr(lib, name).argtypes is not None
+        assert name in _lib.ABI               # the prototypes themselves: test_host_logic's table-driven test
     assert C.sizeof(_lib.AdamwItem) == 112 and C.sizeof(_lib.AdamwPack) == 24 and C.sizeof(_lib.AdamwHyper) == 48
     assert _lib.AdamwItem.packs.offset == 64 and C.sizeof(_lib.AdamwPlanItem) == 24
     from bts_amd import plan

@@ -20,14 +20,11 @@ def _header():
 
 
 def test_exports_prototypes_and_abi_version_unchanged():
+    """(The prototypes themselves: test_host_logic.test_abi_table_matches_every_header_prototype.)"""
     hdr = _header()
     lib = _lib.load_real()
     for name in NAMES:
-        assert name in _lib.SYMBOLS
-        m = re.search(r"\bint\s+%s\s*\(([^;]*?)\)\s*;" % name, hdr, re.S)
-        assert m, name
-        n_params = len([p for p in m.group(1).split(",") if p.strip()])
-        assert n_params == len(getattr(lib, name).argtypes), (name, n_params)
+        assert name in _lib.ABI and re.search(r"\bint\s+%s\s*\(" % name, hdr), name
     assert _lib.ABI_VERSION == 17 and "#define BTS_HIP_ABI_VERSION 17" in hdr
     assert lib.bts_hip_abi_version() == 17
     assert "BTS_OP_CONV_TAIL_BF16 = 13" in hdr

@@ -28,6 +28,191 @@ def test_cabi_exports_every_declared_symbol():
     assert lib.bts_hip_abi_version() == _lib.ABI_VERSION == int(re.search(r"#define BTS_HIP_ABI_VERSION (\d+)", hdr).group(1))
 
 
+def _header_prototypes():
+    """{name: (return type, [parameter type])} of every bts_* function include/bts_hip.h declares, comments stripped."""
+    hdr = open(os.path.join(ROOT, "include", "bts_hip.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
+    hdr = re.sub(r"//[^\n]*", " ", hdr)
+    protos = {}
+    for ret, name, params in re.findall(r"^\s*((?:const\s+)?\w+\s*\*?)\s*\b(bts_[a-z0-9_]+)\s*\(([^;{}]*?)\)\s*;", hdr, re.M | re.S):
+        types = []
+        for p in params.split(","):
+            p = " ".join(p.split())
+            if p in ("", "void"):
+                continue
+            types.append(re.sub(r"\s*\b\w+$", "", p) if not p.endswith("*") else p)    # drop the parameter's name
+        protos[name] = (" ".join(ret.split()), types)
+    return protos
+
+
+def _is_pointer_argtype(t):
+    return t in (ctypes.c_void_p, ctypes.c_char_p) or (isinstance(t, type) and issubclass(t, ctypes._Pointer))
+
+
+def test_abi_table_matches_every_header_prototype():
+    """One row of _lib.ABI per prototype of include/bts_hip.h: parameter count, scalar and pointer kinds, the return type,
+    and the QUERY / LAUNCH role -- taken from the header (LAUNCH = the last parameter is the stream), not from the table."""
+    from bts_amd import _lib
+    protos = _header_prototypes()
+    assert len(protos) >= 54 and set(protos) == set(_lib.ABI) == set(_lib.SYMBOLS)
+    assert _lib.SYMBOLS == tuple(_lib.ABI)
+    scalars = {"int": ctypes.c_int, "long": ctypes.c_long, "float": ctypes.c_float}
+    lib = _lib.load_real()
+    raw = ctypes.CDLL(_lib.LIB_PATH)
+    for name, (ret, params) in protos.items():
+        e = _lib.ABI[name]
+        assert hasattr(raw, name), name
+        assert len(e.argtypes) == len(params), (name, len(e.argtypes), params)
+        for k, (p, t) in enumerate(zip(params, e.argtypes)):
+            if "*" in p or p == "bts_stream_t":
+                assert _is_pointer_argtype(t), (name, k, p, t)
+            else:
+                assert scalars[p] is t, (name, k, p, t)
+        assert e.restype is (ctypes.c_char_p if "*" in ret else scalars[ret]), (name, ret)
+        is_launch = bool(params) and params[-1] == "bts_stream_t"
+        assert e.role == (_lib.LAUNCH if is_launch else _lib.QUERY), (name, e.role)
+        assert not any(p == "bts_stream_t" for p in params[:-1]), name
+        fn = getattr(lib, name)                     # load_real() declared what the table says (bts_plan_run: refined by plan.py)
+        assert fn.argtypes is not None and len(fn.argtypes) == len(e.argtypes) and fn.restype is e.restype, name
+    # what the per-feature tests pinned before the table existed
+    assert lib.bts_depth_loss_ws_doubles.restype is ctypes.c_long
+    assert len(lib.bts_depth_loss_fwd_f32.argtypes) == 12 and len(lib.bts_depth_loss_bwd_f32.argtypes) == 11
+
+
+PARENT_KINDS = {
+    "bts_conv_fwd_f32": (1, "conv"),
+    "bts_reduc_fwd_f32": (2, "reduc"),
+    "bts_reduc_lpg_fwd_f32": (3, "reduc_lpg"),
+    "bts_lpg_fused_fwd_f32": (4, "lpg_fused"),
+    "bts_nchw_to_nhwc_f32": (5, "nchw_to_nhwc"),
+    "bts_nhwc_to_nchw_f32": (6, "nhwc_to_nchw"),
+    "bts_maxpool3x3s2_nhwc_f32": (7, "maxpool"),
+    "bts_bn_relu_avgpool2_nhwc_f32": (8, "avgpool"),
+    "bts_get_depth_f32": (9, "get_depth"),
+    "bts_lpg_fwd_f32": (10, "lpg"),
+    "bts_upconv_combine_f32": (11, "upconv_combine"),
+    "bts_upconv_up9_fwd_f32": (12, "upconv_up9"),
+    "bts_conv_tail_bf16_fwd_f32": (13, "conv_tail_bf16"),
+    "bts_conv_tail_wino_fwd_f32": (14, "conv_tail_wino"),
+}
+# the names plan._Proxy used to pass through by a hard-coded list: every one is a host query
+FORMER_PASS_THROUGH = ("bts_hip_error_string", "bts_hip_abi_version", "bts_conv_plan_f32", "bts_conv_wgrad_plan_f32",
+                       "bts_conv_wgrad_batch_table_bytes", "bts_conv_wgrad_batch_plan_f32", "bts_eval_ws_doubles",
+                       "bts_bn_train_ws_floats", "bts_pack_weights_blocks", "bts_depth_loss_ws_doubles", "bts_adamw_table_bytes",
+                       "bts_adamw_flat_span", "bts_adamw_plan_f32", "bts_upconv_up9_plan", "bts_conv_tail_bf16_plan",
+                       "bts_conv_tail_wino_plan", "bts_upconv_dgrad_plan", "bts_upconv_wgrad_plan_f32", "bts_upconv_train_pack_blocks")
+
+
+def test_plan_kinds_are_the_parent_commits_dictionary():
+    from bts_amd import _lib, plan
+    assert plan._KINDS == PARENT_KINDS
+    assert all(_lib.ABI[name].role == _lib.LAUNCH for name in plan._KINDS)
+    hdr = open(os.path.join(ROOT, "include", "bts_hip.h")).read()
+    for name, (kind, member) in plan._KINDS.items():          # the header spells the same numbers and member names
+        assert re.search(r"\bBTS_OP_\w+ = %d\b" % kind, hdr), (name, kind)
+        assert re.search(r"\b%s;" % member, hdr), (name, member)
+    for name in FORMER_PASS_THROUGH:
+        assert _lib.ABI[name].role == _lib.QUERY, name
+    # the three host queries the list had forgotten
+    for name in ("bts_conv_plan_ksteps_f32", "bts_pack_wino_floats", "bts_reduc_bwd_max_waves"):
+        assert _lib.ABI[name].role == _lib.QUERY, name
+
+
+def test_recording_proxy_forwards_queries_records_plan_entries_and_flags_other_launches():
+    """plan._Proxy over a stub library, no GPU: QUERY names come back as the library's own functions and leave the
+    recorder alone, every _KINDS name is recorded with its arguments, any other LAUNCH name is reported as foreign."""
+    from bts_amd import _lib, plan
+
+    class Stub:
+        def __init__(self):
+            self.called = []
+            for name in _lib.ABI:
+                setattr(self, name, self._make(name))
+            self.other_attribute = object()
+
+        def _make(self, name):
+            def fn(*args):
+                self.called.append(name)
+                return 0
+            return fn
+
+    stub, rec = Stub(), plan._Recorder()
+    proxy = plan._Proxy(stub, rec)
+    assert proxy.other_attribute is stub.other_attribute
+    queries = [n for n, e in _lib.ABI.items() if e.role == _lib.QUERY]
+    assert len(queries) >= 22
+    for name in queries:
+        assert getattr(proxy, name) is getattr(stub, name), name
+    assert rec.calls == [] and rec.foreign == [] and stub.called == []
+    for name in plan._KINDS:
+        n_args = len(_lib.ABI[name].argtypes)
+        args = [ctypes.byref(_lib.ConvDesc())] if name == "bts_conv_fwd_f32" else [0] * (n_args - 1)
+        assert getattr(proxy, name)(*args, ctypes.c_void_p(7)) == 0
+        assert rec.calls[-1][0] == name and rec.calls[-1][2] == 7 and stub.called[-1] == name
+    assert [c[0] for c in rec.calls] == list(plan._KINDS) and rec.foreign == []
+    foreign = [n for n, e in _lib.ABI.items() if e.role == _lib.LAUNCH and n not in plan._KINDS]
+    assert "bts_conv_wgrad_f32" in foreign and "bts_pack_weights_f32" in foreign and "bts_plan_run" in foreign
+    for name in foreign:
+        assert getattr(proxy, name)() == 0 and stub.called[-1] == name
+    assert rec.foreign == foreign and len(rec.calls) == len(plan._KINDS)
+
+
+def test_resolve_launch():
+    from bts_amd import ops
+    from bts_amd._lib import BtsHipError
+    for bad in ("fp16", 3, -1, "BF16"):
+        with pytest.raises(BtsHipError, match="some_plan: precision"):
+            ops._resolve_launch(bad, None, "some_plan")
+    for bad in (-1, 4097, 5000):
+        with pytest.raises(BtsHipError, match="some_plan: fill_frames"):
+            ops._resolve_launch(None, bad, "some_plan")
+    assert ops._resolve_launch(None, 0, "p")[0] == 0 and ops._resolve_launch(None, 4096, "p")[0] == 4096
+    env = ops._ENV_PRECISION
+    assert ops._resolve_launch(None, None, "p") == ops.current_launch_config() == (0, env)
+    with ops.launch_config(fill_frames=3, precision="bf16"):
+        assert ops._resolve_launch(None, None, "p") == ops.current_launch_config() == (3, 1 if env else 2)     # None keeps the scope
+        assert ops._resolve_launch("fp32", None, "p") == (3, 1 if env else 0)
+        assert ops._resolve_launch(None, 16, "p") == (16, 1 if env else 2)
+        assert ops._resolve_launch(1, 7, "p") == (7, 1)
+    # every wrapper that takes the overrides raises the same error type, its own name in the message
+    for fn, args in ((ops.upconv_up9_plan, (44, 152, 128, 128)), (ops.conv_tail_wino_plan, (352, 1216, 32, 32)),
+                     (ops.upconv_dgrad_plan, (1, 8, 8, 32, 32))):
+        with pytest.raises(BtsHipError, match=fn.__name__):
+            fn(*args, precision="fp16")
+        with pytest.raises(BtsHipError, match=fn.__name__):
+            fn(*args, fill_frames=5000)
+    with pytest.raises(BtsHipError, match="conv_tail_bf16_plan"):
+        ops.conv_tail_bf16_plan(88, 304, 224, 128, fill_frames=-1)
+    with pytest.raises(BtsHipError, match="launch_config"):
+        ops.launch_config(precision="fp16")
+    with pytest.raises(BtsHipError, match="launch_config"):
+        ops.launch_config(fill_frames=4097)
+
+
+def test_resolve_launch_env_precision_wins(monkeypatch):
+    """BTS_CONV_PRECISION=1 (read once at import as ops._ENV_PRECISION) overrides scope and argument alike, as
+    current_launch_config documents."""
+    from bts_amd import ops
+    monkeypatch.setattr(ops, "_ENV_PRECISION", 1)
+    assert ops._resolve_launch(None, None, "p") == (0, 1)
+    assert ops._resolve_launch("fp32", 4, "p") == (4, 1) and ops._resolve_launch("bf16", None, "p") == (0, 1)
+    with ops.launch_config(fill_frames=2, precision="fp32"):
+        assert ops._resolve_launch(None, None, "p") == ops.current_launch_config() == (2, 1)
+        assert ops._resolve_launch(2, None, "p") == (2, 1)
+
+
+def test_tile_plan_tuples():
+    from bts_amd import ops
+    assert ops.Up9Plan is ops.TilePlan and ops.TailWinoPlan is ops.TilePlan
+    for cls in (ops.Up9Plan, ops.TailWinoPlan):
+        none = cls((0, 0, 0))
+        assert not none.eligible and tuple(none) == (0, 0, 0)
+        p = cls((32, 64, 3344))
+        assert p.eligible and (p.bm, p.bn, p.workgroups) == (p[0], p[1], p[2]) == (32, 64, 3344) and len(p) == 3
+    b = ops.TailBf16Plan((128, 96))
+    assert b.eligible and (b.bn, b.workgroups) == (b[0], b[1]) == (128, 96) and not ops.TailBf16Plan((0, 0)).eligible
+
+
 def test_conv_desc_layout_matches_header():
     from bts_amd._lib import ConvDesc
     assert ctypes.sizeof(ConvDesc) == 272

@@ -67,7 +67,7 @@ def test_column_tables_match_chain(chain):
 
 def test_library_exports_reduc_bwd_and_abi_17():
     hdr = open(os.path.join(ROOT, "include", "bts_hip.h")).read()
-    assert "bts_reduc_bwd_f32" in _lib.SYMBOLS
+    assert "bts_reduc_bwd_f32" in _lib.ABI
     lib = ctypes.CDLL(_lib.LIB_PATH)
     assert hasattr(lib, "bts_reduc_bwd_f32") and hasattr(lib, "bts_reduc_bwd_max_waves")
     lib.bts_hip_abi_version.restype = ctypes.c_int

@@ -143,17 +143,20 @@ def test_exports_bindings_and_abi_version():
     names = ("bts_upconv_dgrad_f32", "bts_upconv_dgrad_plan", "bts_upconv_wgrad_f32", "bts_upconv_wgrad_plan_f32",
              "bts_upconv_train_pack_blocks", "bts_upconv_train_pack_f32")
     lib = _lib.load_real()
-    for name in names:
-        assert name in _lib.SYMBOLS and re.search(r"\b%s\s*\(" % name, hdr), name
-        fn = getattr(lib, name)
-        proto = re.search(r"\b%s\s*\(([^;]*)\)\s*;" % name, hdr).group(1)
-        assert len(fn.argtypes) == proto.count(",") + 1, (name, "argtypes do not match the header's parameter list")
+    for name in names:                        # the prototypes themselves: test_host_logic's table-driven test
+        assert name in _lib.ABI and re.search(r"\b%s\s*\(" % name, hdr), name
     assert _lib.ABI_VERSION == 17 and "#define BTS_HIP_ABI_VERSION 17" in hdr and lib.bts_hip_abi_version() == 17
     # host-only queries pass through a plan recording untouched; the launches are foreign to a recorded forward
     from bts_amd import plan
-    src = open(os.path.join(ROOT, "bts_amd", "plan.py")).read()
+    rec = plan._Recorder()
+    proxy = plan._Proxy(lib, rec)
     for name in ("bts_upconv_dgrad_plan", "bts_upconv_wgrad_plan_f32", "bts_upconv_train_pack_blocks"):
-        assert '"%s"' % name in src and name not in plan._KINDS
+        assert _lib.ABI[name].role == _lib.QUERY and name not in plan._KINDS
+        assert getattr(proxy, name) is getattr(lib, name), name
+    for name in ("bts_upconv_dgrad_f32", "bts_upconv_wgrad_f32", "bts_upconv_train_pack_f32"):
+        assert _lib.ABI[name].role == _lib.LAUNCH and name not in plan._KINDS
+        assert getattr(proxy, name) is not getattr(lib, name), name
+    assert rec.calls == [] and rec.foreign == []
 
 
 def test_switch_defaults_off():

@@ -112,8 +112,8 @@ def test_entry_point_rejects_bad_arguments_on_the_host():
 
 def test_exports_and_abi_version_unchanged():
     hdr = open(os.path.join(ROOT, "include", "bts_hip.h")).read()
-    for name in ("bts_upconv_up9_fwd_f32", "bts_upconv_up9_plan"):
-        assert name in _lib.SYMBOLS and re.search(r"\b%s\s*\(" % name, hdr)
+    for name in ("bts_upconv_up9_fwd_f32", "bts_upconv_up9_plan"):              # prototypes: test_host_logic's table-driven test
+        assert name in _lib.ABI and re.search(r"\b%s\s*\(" % name, hdr)
     assert _lib.ABI_VERSION == 17 and "#define BTS_HIP_ABI_VERSION 17" in hdr
     assert "BTS_OP_UPCONV_UP9 = 12" in hdr
     from bts_amd import plan
