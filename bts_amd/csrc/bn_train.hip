@@ -5,8 +5,10 @@
 // HBM-bound streaming passes: a block covers up to 128 channels x 8 pixel rows per step with 16-byte lanes
 // (fewer lanes, more rows for narrow tensors), several independent loads in flight per thread.  The per-channel reductions go through a two-level tree (thread ->
 // block -> a finalize kernel that walks the block partials in a fixed order): deterministic, no atomics.
-//   forward : bn_stats (Chan-merged (n, mean, M2) partials, shifted sums)  ->  bn_stats_finalize (mean, invstd,
-//             fused scale/shift, running-stat update)  ->  bn_apply (y = [relu](x*scale + shift))
+//   forward : bn_stats (per chunk: the plain sum, and Chan-merged (mean, M2) partials of x - x[row 0] -- one shift per
+//             channel for the whole tensor, so the sums AND every merge of two partial means work on the small shifted
+//             values)  ->  bn_stats_finalize (mean, invstd, fused scale/shift, running-stat update)  ->  bn_apply
+//             (y = [relu](x*scale + shift))
 //   backward: bn_bwd_reduce (sum dy', sum dy'*xhat; dy' = dy masked by the fused ReLU)  ->  finalize
 //             ->  bn_bwd_apply (dx = gamma*invstd*(dy' - mean(dy') - xhat*mean(dy'*xhat)))
 #include "common.h"
@@ -24,7 +26,8 @@ __device__ __forceinline__ void chan_merge(float& n, float& mean, float& m2, flo
     n = nt;
 }
 
-// partial (n, mean, M2) of one pixel chunk for LX*4 channels -> ws[(chunk*3 + {0,1,2})*C + c].
+// partial (sum x, mean of x - x[0][c], M2) of one pixel chunk for LX*4 channels -> ws[(chunk*3 + {0,1,2})*C + c]; the
+// chunk's row count is a function of (chunk, npix, rows_per_chunk) and is not stored.
 // LX = float4 lanes per pixel row (32 / 16 / 8 for wide / 64.. / narrow tensors), 256/LX rows per block step.
 template <int LX>
 __global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__ x, long xs, long npix, int C,
@@ -35,44 +38,55 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__
     const bool active = c4 < C;
     const long p0 = (long)blockIdx.y * rows_per_chunk;
     const long p1 = min(npix, p0 + rows_per_chunk);
-    f32x4 s = (f32x4)(0.f), q = (f32x4)(0.f), x0 = (f32x4)(0.f);
+    f32x4 s = (f32x4)(0.f), q = (f32x4)(0.f), raw = (f32x4)(0.f), x0 = (f32x4)(0.f);
     float n = 0.f;
     if (active) {
-        x0 = *reinterpret_cast<const f32x4*>(x + p0 * xs + c4);      // shift: kills the sum-of-squares cancellation
+        // shift by the tensor's first row: kills the sum-of-squares cancellation, and -- the same shift in every thread
+        // and chunk -- lets the partial means merge without being rounded at the data's magnitude first (a mean near
+        // 1000 carries 6e-5 of rounding; under a std of 0.01 the merged M2 lost three digits to it)
+        x0 = *reinterpret_cast<const f32x4*>(x + c4);
         long p = p0 + ry;
         for (; p + 3 * RYv < p1; p += 4 * RYv) {                      // four independent 16-byte loads in flight
-            const f32x4 v0 = *reinterpret_cast<const f32x4*>(x + p * xs + c4) - x0;
-            const f32x4 v1 = *reinterpret_cast<const f32x4*>(x + (p + RYv) * xs + c4) - x0;
-            const f32x4 v2 = *reinterpret_cast<const f32x4*>(x + (p + 2 * RYv) * xs + c4) - x0;
-            const f32x4 v3 = *reinterpret_cast<const f32x4*>(x + (p + 3 * RYv) * xs + c4) - x0;
+            const f32x4 a0 = *reinterpret_cast<const f32x4*>(x + p * xs + c4);
+            const f32x4 a1 = *reinterpret_cast<const f32x4*>(x + (p + RYv) * xs + c4);
+            const f32x4 a2 = *reinterpret_cast<const f32x4*>(x + (p + 2 * RYv) * xs + c4);
+            const f32x4 a3 = *reinterpret_cast<const f32x4*>(x + (p + 3 * RYv) * xs + c4);
+            const f32x4 v0 = a0 - x0, v1 = a1 - x0, v2 = a2 - x0, v3 = a3 - x0;
+            raw += (a0 + a1) + (a2 + a3);
             s += (v0 + v1) + (v2 + v3);
             q += (v0 * v0 + v1 * v1) + (v2 * v2 + v3 * v3);
             n += 4.f;
         }
         for (; p < p1; p += RYv) {
-            const f32x4 v = *reinterpret_cast<const f32x4*>(x + p * xs + c4) - x0;
+            const f32x4 a = *reinterpret_cast<const f32x4*>(x + p * xs + c4);
+            const f32x4 v = a - x0;
+            raw += a;
             s += v;
             q += v * v;
             n += 1.f;
         }
     }
-    __shared__ float red[RYv][CGv][3];
+    __shared__ float red[RYv][CGv][4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const float mean = n > 0.f ? s[j] / n : 0.f;
         red[ry][cx * 4 + j][0] = n;
-        red[ry][cx * 4 + j][1] = x0[j] + mean;
+        red[ry][cx * 4 + j][1] = mean;
         red[ry][cx * 4 + j][2] = n > 0.f ? q[j] - s[j] * mean : 0.f;
+        red[ry][cx * 4 + j][3] = raw[j];
     }
     __syncthreads();
     if (threadIdx.x < CGv) {
         const int c = blockIdx.x * CGv + threadIdx.x;
         if (c < C) {
-            float nn = 0.f, mean = 0.f, m2 = 0.f;
+            float nn = 0.f, mean = 0.f, m2 = 0.f, sum = 0.f;
 #pragma unroll 8
-            for (int r = 0; r < RYv; ++r) chan_merge(nn, mean, m2, red[r][threadIdx.x][0], red[r][threadIdx.x][1], red[r][threadIdx.x][2]);
+            for (int r = 0; r < RYv; ++r) {
+                chan_merge(nn, mean, m2, red[r][threadIdx.x][0], red[r][threadIdx.x][1], red[r][threadIdx.x][2]);
+                sum += red[r][threadIdx.x][3];
+            }
             float* o = ws + (size_t)blockIdx.y * 3 * C;
-            o[c] = nn;
+            o[c] = sum;
             o[C + c] = mean;
             o[2 * C + c] = m2;
         }
@@ -81,7 +95,13 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__
 
 // Finalize kernels: a block owns 32 channels; 8 lanes per channel walk the chunk partials (strided, loads unrolled
 // so they are independent of the merge chain), then one lane merges the 8 results in a fixed order.
+// The mean has two estimates: x[0][c] + the merged shifted mean (rounded at the size of mean - x[0][c]) and the plain
+// sum / n (rounded at the size of the data).  The one with the smaller rounding scale is stored: a mean near 1000 under
+// a std of 0.01 comes from the first (and a constant channel comes out exactly), a mean of 0.4 under a std of 1.7 whose
+// first row happened to hold 5.0 from the second.
 __global__ __launch_bounds__(256) void bn_stats_finalize_kernel(const float* __restrict__ ws, int nchunks, int C,
+                                                                const float* __restrict__ x, long npix,
+                                                                long rows_per_chunk,
                                                                 const float* __restrict__ gamma,
                                                                 const float* __restrict__ beta, float eps, float momentum,
                                                                 float* __restrict__ running_mean,
@@ -91,29 +111,42 @@ __global__ __launch_bounds__(256) void bn_stats_finalize_kernel(const float* __r
     const int cl = threadIdx.x & 31, lane = threadIdx.x >> 5;
     const int c = blockIdx.x * 32 + cl;
     const int cc = c < C ? c : C - 1;
-    float n = 0.f, mean = 0.f, m2 = 0.f;
+    auto rows_of = [&](int chunk) __attribute__((always_inline)) {
+        const long a = (long)chunk * rows_per_chunk;
+        return (float)(min(npix, a + rows_per_chunk) - a);
+    };
+    float n = 0.f, mean = 0.f, m2 = 0.f, sum = 0.f;
     int k = lane;
     for (; k + 24 < nchunks; k += 32) {
-        float pn[4], pm[4], pq[4];
+        float ps[4], pm[4], pq[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const float* p = ws + (size_t)(k + 8 * u) * 3 * C;
-            pn[u] = p[cc]; pm[u] = p[C + cc]; pq[u] = p[2 * C + cc];
+            ps[u] = p[cc]; pm[u] = p[C + cc]; pq[u] = p[2 * C + cc];
         }
 #pragma unroll
-        for (int u = 0; u < 4; ++u) chan_merge(n, mean, m2, pn[u], pm[u], pq[u]);
+        for (int u = 0; u < 4; ++u) {
+            chan_merge(n, mean, m2, rows_of(k + 8 * u), pm[u], pq[u]);
+            sum += ps[u];
+        }
     }
     for (; k < nchunks; k += 8) {
         const float* p = ws + (size_t)k * 3 * C;
-        chan_merge(n, mean, m2, p[cc], p[C + cc], p[2 * C + cc]);
+        chan_merge(n, mean, m2, rows_of(k), p[C + cc], p[2 * C + cc]);
+        sum += p[cc];
     }
-    __shared__ float red[8][32][3];
-    red[lane][cl][0] = n; red[lane][cl][1] = mean; red[lane][cl][2] = m2;
+    __shared__ float red[8][32][4];
+    red[lane][cl][0] = n; red[lane][cl][1] = mean; red[lane][cl][2] = m2; red[lane][cl][3] = sum;
     __syncthreads();
     if (lane != 0 || c >= C) return;
-    n = 0.f; mean = 0.f; m2 = 0.f;
+    n = 0.f; mean = 0.f; m2 = 0.f; sum = 0.f;
 #pragma unroll
-    for (int r = 0; r < 8; ++r) chan_merge(n, mean, m2, red[r][cl][0], red[r][cl][1], red[r][cl][2]);
+    for (int r = 0; r < 8; ++r) {
+        chan_merge(n, mean, m2, red[r][cl][0], red[r][cl][1], red[r][cl][2]);
+        sum += red[r][cl][3];
+    }
+    const float plain = sum / n;
+    mean = fabsf(mean) <= fabsf(plain) ? x[c] + mean : plain;
     const float var = m2 / n;                                   // biased: what normalisation uses
     const float invstd = 1.f / sqrtf(var + eps);
     const float g = gamma ? gamma[c] : 1.f, b = beta ? beta[c] : 0.f;
@@ -300,7 +333,8 @@ extern "C" int bts_bn_train_stats_f32(const float* x, long x_pix_stride, long np
     if (lx == 32) hipLaunchKernelGGL(bn_stats_kernel<32>, grid, dim3(256), 0, s, x, x_pix_stride, npix, C, rows, ws);
     else if (lx == 16) hipLaunchKernelGGL(bn_stats_kernel<16>, grid, dim3(256), 0, s, x, x_pix_stride, npix, C, rows, ws);
     else hipLaunchKernelGGL(bn_stats_kernel<8>, grid, dim3(256), 0, s, x, x_pix_stride, npix, C, rows, ws);
-    hipLaunchKernelGGL(bn_stats_finalize_kernel, dim3((C + 31) / 32), dim3(256), 0, s, ws, nchunks, C, gamma, beta, eps,
+    hipLaunchKernelGGL(bn_stats_finalize_kernel, dim3((C + 31) / 32), dim3(256), 0, s, ws, nchunks, C, x, npix, rows, gamma, beta,
+                       eps,
                        momentum, running_mean, running_var, mean, invstd, scale, shift);
     return (int)hipGetLastError();
 }

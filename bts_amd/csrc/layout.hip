@@ -3,6 +3,7 @@
 // version/error helpers.  32x32 tiles through LDS: both the global read and the global write
 // are 128-byte coalesced.  HBM-bound (8 B moved per element).
 #include <hip/hip_runtime.h>
+#include <stdint.h>
 #include "common.h"
 
 namespace {
@@ -34,16 +35,17 @@ __global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const float* __restri
 }
 
 // src [B][C<=4][HW] -> dst [B*HW][stride]: one thread per pixel, planar coalesced reads, one 16-byte store
-// (the 3-channel image: the 32x32 tile kernel would leave 29 of 32 lanes idle on the write side)
+// (the 3-channel image: the 32x32 tile kernel would leave 29 of 32 lanes idle on the write side).
+// vec4: C == 4 and every destination pixel is 16-byte aligned (the host decides); otherwise scalar stores.
 __global__ __launch_bounds__(256) void nchw_to_nhwc_c4_kernel(const float* __restrict__ src, int C, long HW, long total,
-                                                              float* __restrict__ dst, long stride, int relu) {
+                                                              float* __restrict__ dst, long stride, int relu, int vec4) {
     for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (long)gridDim.x * blockDim.x) {
         const long b = p / HW, q = p - b * HW;
         const float* s = src + b * C * HW + q;
         float v[4] = {0.f, 0.f, 0.f, 0.f};
         for (int c = 0; c < C; ++c) v[c] = relu ? fmaxf(s[c * HW], 0.f) : s[c * HW];
         float* d = dst + p * stride;
-        if (C == 4) *reinterpret_cast<float4*>(d) = make_float4(v[0], v[1], v[2], v[3]);
+        if (vec4) *reinterpret_cast<float4*>(d) = make_float4(v[0], v[1], v[2], v[3]);
         else for (int c = 0; c < C; ++c) d[c] = v[c];
     }
 }
@@ -82,8 +84,10 @@ extern "C" int bts_nchw_to_nhwc_f32(const float* src, int B, int C, long HW, flo
         const long total = (long)B * HW;
         long blocks = (total + 255) / 256;
         if (blocks > 256L * 16) blocks = 256L * 16;
+        // a channel slice at an odd offset, or an odd pixel stride, cannot take the 16-byte store
+        const int vec4 = C == 4 && !((uintptr_t)dst & 15) && !(dst_pix_stride & 3);
         hipLaunchKernelGGL(nchw_to_nhwc_c4_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, src, C, HW,
-                           total, dst, dst_pix_stride, relu);
+                           total, dst, dst_pix_stride, relu, vec4);
         return (int)hipGetLastError();
     }
     if (B > 65535 || (C + 31) / 32 > 65535) return BTS_ERR_UNSUPPORTED;

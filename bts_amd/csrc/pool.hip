@@ -80,6 +80,7 @@ extern "C" int bts_maxpool3x3s2_nhwc_f32(const float* src, long src_pix_stride, 
                                          long dst_pix_stride, float* dst2, long dst2_pix_stride, bts_stream_t stream) {
     if (!src || !dst || B <= 0 || h <= 0 || w <= 0 || C <= 0 || (C & 3)) return BTS_ERR_INVALID;
     if ((src_pix_stride & 3) || (dst_pix_stride & 3) || (dst2 && (dst2_pix_stride & 3))) return BTS_ERR_INVALID;
+    if (src_pix_stride < C || dst_pix_stride < C || (dst2 && dst2_pix_stride < C)) return BTS_ERR_INVALID;
     if (((uintptr_t)src & 15) || ((uintptr_t)dst & 15) || ((uintptr_t)dst2 & 15)) return BTS_ERR_INVALID;
     const long total = (long)B * ((h + 1) / 2) * ((w + 1) / 2) * (C / 4);
     hipLaunchKernelGGL(maxpool3x3s2_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, src, src_pix_stride,
@@ -93,6 +94,7 @@ extern "C" int bts_bn_relu_avgpool2_nhwc_f32(const float* src, long src_pix_stri
     if (!src || !dst || !scale || !shift || B <= 0 || h <= 0 || w <= 0 || C <= 0 || (C & 3) || (h & 1) || (w & 1))
         return BTS_ERR_INVALID;
     if ((src_pix_stride & 3) || (dst_pix_stride & 3)) return BTS_ERR_INVALID;
+    if (src_pix_stride < C || dst_pix_stride < C) return BTS_ERR_INVALID;
     if (((uintptr_t)src & 15) || ((uintptr_t)dst & 15) || ((uintptr_t)scale & 15) || ((uintptr_t)shift & 15))
         return BTS_ERR_INVALID;
     const long total = (long)B * (h / 2) * (w / 2) * (C / 4);

@@ -91,6 +91,31 @@ def _rows2d(t: torch.Tensor, name: str) -> Tuple[int, int]:
     return t.stride(0), t.shape[1]
 
 
+def _rows2d_c(t: torch.Tensor, C: int, npix: int, name: str) -> int:
+    """The pixel stride of a _rows2d view that a kernel walks as ``npix`` rows of ``C`` channels, 16 bytes per lane:
+    C a positive multiple of 4 within the view's width, exactly npix rows, 16-byte aligned rows."""
+    stride, width = _rows2d(t, name)
+    if C <= 0 or C % 4 or C > width:
+        raise BtsHipError("bts_amd.%s: C must be a positive multiple of 4 within the view (%d/%d)" % (name, C, width))
+    if t.shape[0] != npix:
+        raise BtsHipError("bts_amd.%s: view has %d rows, expected %d" % (name, t.shape[0], npix))
+    if stride % 4 or t.data_ptr() % 16:
+        raise BtsHipError("bts_amd.%s: rows must be 16-byte aligned (pixel stride %d, a multiple of 4 floats)" % (name, stride))
+    return stride
+
+
+def _channel_vec(v: Optional[torch.Tensor], C: int, name: str, what: str, aligned: bool = True):
+    """A per-channel fp32 vector a kernel reads (or writes) C elements of: contiguous, at least C long, and -- for the
+    kernels that take it 16 bytes per lane -- 16-byte aligned."""
+    _need(v, name)
+    if v.dim() != 1 or v.numel() < C or (v.numel() > 1 and v.stride(0) != 1):
+        raise BtsHipError("bts_amd.%s: %s must be a contiguous vector of at least %d elements, got %s"
+                          % (name, what, C, tuple(v.shape)))
+    if aligned and v.data_ptr() % 16:
+        raise BtsHipError("bts_amd.%s: %s must be 16-byte aligned" % (name, what))
+    return v
+
+
 def _enqueue(entry: str, anchor: torch.Tensor, args: Sequence = (), trace=None, run=None):
     """Enqueue the C entry point ``entry`` on ``anchor``'s device and current stream, and check its return code.
     ``args``: the prototype's arguments without the stream.  ``run``: a ready closure to call instead (the
@@ -2050,6 +2075,9 @@ def bn_train_stats(x2d: torch.Tensor, C: int, gamma, beta, eps: float, momentum:
         if tuple(out.shape) != (4, C) or out.stride(1) != 1 or out.stride(0) % 4 or out.data_ptr() % 16:
             raise BtsHipError("bn_train_stats: out must be a [4, %d] view with unit channel stride and 16-byte aligned rows" % C)
     _need(ws, "bn_train_stats")
+    for v, what in ((gamma, "gamma"), (beta, "beta"), (running_mean, "running_mean"), (running_var, "running_var")):
+        if v is not None:
+            _channel_vec(v, C, "bn_train_stats", what, aligned=False)
     npix = x2d.shape[0]
     _enqueue("bts_bn_train_stats_f32", x2d,
              (x2d.data_ptr(), xs, npix, C, _ptr(gamma), _ptr(beta), float(eps), float(momentum), _ptr(running_mean), _ptr(running_var),
@@ -2060,9 +2088,11 @@ def bn_train_stats(x2d: torch.Tensor, C: int, gamma, beta, eps: float, momentum:
 
 def bn_apply(x2d: torch.Tensor, C: int, scale: torch.Tensor, shift: torch.Tensor, relu: bool, y2d: torch.Tensor):
     """y = [relu](x*scale + shift) over NHWC rows (bts_bn_apply_nhwc_f32)."""
-    xs, _ = _rows2d(x2d, "bn_apply")
-    ys, _ = _rows2d(y2d, "bn_apply")
-    npix = x2d.shape[0]
+    npix = x2d.shape[0] if isinstance(x2d, torch.Tensor) and x2d.dim() == 2 else 0
+    xs = _rows2d_c(x2d, C, npix, "bn_apply")
+    ys = _rows2d_c(y2d, C, npix, "bn_apply")
+    _channel_vec(scale, C, "bn_apply", "scale")
+    _channel_vec(shift, C, "bn_apply", "shift")
     _enqueue("bts_bn_apply_nhwc_f32", x2d, (x2d.data_ptr(), xs, npix, C, scale.data_ptr(), shift.data_ptr(), int(bool(relu)), y2d.data_ptr(), ys),
              trace=("bn_apply_kernel", "bn.apply", 2.0 * npix * C, 8.0 * npix * C, None))
     return y2d
@@ -2071,15 +2101,16 @@ def bn_apply(x2d: torch.Tensor, C: int, scale: torch.Tensor, shift: torch.Tensor
 def bn_train_backward(x2d: torch.Tensor, dy2d: torch.Tensor, C: int, mean, invstd, scale, shift, relu: bool,
                       ws: torch.Tensor, dx2d: Optional[torch.Tensor]):
     """Backward of batch-statistic BN (+ fused ReLU): returns (dgamma, dbeta); dx2d (or None) is filled in place."""
-    xs, _ = _rows2d(x2d, "bn_train_backward")
-    ds, _ = _rows2d(dy2d, "bn_train_backward")
-    npix = x2d.shape[0]
-    if dy2d.shape[0] != npix:
-        raise BtsHipError("bn_train_backward: gradient rows %d != input rows %d" % (dy2d.shape[0], npix))
-    g = torch.empty((2, C), dtype=torch.float32, device=x2d.device)
+    npix = x2d.shape[0] if isinstance(x2d, torch.Tensor) and x2d.dim() == 2 else 0
+    xs = _rows2d_c(x2d, C, npix, "bn_train_backward")
+    ds = _rows2d_c(dy2d, C, npix, "bn_train_backward")
+    for v, what in ((mean, "mean"), (invstd, "invstd"), (scale, "scale"), (shift, "shift")):
+        _channel_vec(v, C, "bn_train_backward", what)
+    _need(ws, "bn_train_backward")
     dxs = 0
     if dx2d is not None:
-        dxs, _ = _rows2d(dx2d, "bn_train_backward")
+        dxs = _rows2d_c(dx2d, C, npix, "bn_train_backward")
+    g = torch.empty((2, C), dtype=torch.float32, device=x2d.device)
     _enqueue("bts_bn_train_bwd_f32", x2d,
              (x2d.data_ptr(), xs, dy2d.data_ptr(), ds, npix, C, mean.data_ptr(), invstd.data_ptr(), scale.data_ptr(), shift.data_ptr(),
               int(bool(relu)), ws.data_ptr(), ws.numel(), g[0].data_ptr(), g[1].data_ptr(), _ptr(dx2d), dxs),

@@ -542,7 +542,7 @@ int bts_pack_wino_f32(const float* w_packed, int c_out_pad, long k_pad, int c_in
 /* Batch-statistic BatchNorm over NHWC rows [npix][C] (nn.BatchNorm2d in train() mode: pytorch/bts.py:69-76,
  * 182-202 and the DenseNet norm layers), C % 4 == 0, row strides % 4 == 0 and >= C (channel slices work in place).
  *
- * bts_bn_train_stats_f32 : per-channel batch mean and biased variance (deterministic tree of Chan-merged partials)
+ * bts_bn_train_stats_f32 : per-channel batch mean and biased variance (deterministic tree of Chan-merged partials of x minus its first row)
  *     -> mean, invstd = 1/sqrt(var+eps), scale = gamma*invstd, shift = beta - mean*scale; running_mean/var (may be
  *     NULL) updated as PyTorch does: r = (1-momentum)*r + momentum*{mean | unbiased var}.  gamma/beta NULL = 1/0.
  *     ws: scratch of bts_bn_train_ws_floats(npix, C) floats.
@@ -566,6 +566,8 @@ int bts_bn_train_bwd_f32(const float* x, long x_pix_stride, const float* dy, lon
  * Layout movers between the NCHW boundary (pytorch/bts.py:347-349 tensors) and the NHWC
  * interior.  dst/src NHWC element (p,c) lives at base[p*pix_stride + c].
  *   relu != 0 applies max(v,0) on the way (bts.py:225: dense_features = ReLU(features[5])).
+ *   No alignment demand on dst: C == 4 stores 16 bytes per pixel when dst is 16-byte aligned and
+ *   dst_pix_stride % 4 == 0, and four scalars otherwise.
  */
 int bts_nchw_to_nhwc_f32(const float* src, int B, int C, long HW, float* dst, long dst_pix_stride,
                          int relu, bts_stream_t stream);
@@ -584,7 +586,8 @@ int bts_pack_planes_f32(const float* p0, const float* p1, const float* p2, const
  * AvgPool2d(2,2); the encoder is the caller side of the hot path, pytorch/bts.py:295-338).
  * maxpool: [B,h,w,C] -> [B,ceil(h/2),ceil(w/2),C], optionally to two destinations.
  * bn_relu_avgpool2: dst = mean_{2x2} relu(src*scale + shift)  (transition norm+relu+pool; its 1x1 conv
- * commutes with the mean and runs afterwards on the pooled map).  C % 4 == 0, strides % 4 == 0.
+ * commutes with the mean and runs afterwards on the pooled map).  C % 4 == 0, strides % 4 == 0 and
+ * >= C, pointers 16-byte aligned; anything else is BTS_ERR_INVALID before any GPU work.
  */
 int bts_maxpool3x3s2_nhwc_f32(const float* src, long src_pix_stride, int B, int h, int w, int C, float* dst,
                               long dst_pix_stride, float* dst2, long dst2_pix_stride, bts_stream_t stream);
