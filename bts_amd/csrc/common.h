@@ -23,6 +23,19 @@ __device__ __forceinline__ f32x16 mfma32x2(float a, float b, f32x16 c) {
 __device__ __forceinline__ float elu1(float x) { return x > 0.f ? x : __expf(x) - 1.f; }
 __device__ __forceinline__ float sigmoid1(float x) { return __frcp_rn(1.f + __expf(-x)); }
 
+// Table-driven launches (weight packs, batched weight gradients, AdamW): a device table holds one record per problem with
+// a prefix sum of workgroups in the member `first`; the record whose range holds this workgroup is the last one with
+// first <= blockIdx.x.  Uniform per workgroup: integer code on scalar registers.
+template <typename T>
+__device__ __forceinline__ int bts_table_find(const T* __restrict__ table, int n, long T::*first) {
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (table[mid].*first <= (long)blockIdx.x) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
 // Raise a kernel's dynamic-LDS limit above the 64 KB default.  hipFuncAttributeMaxDynamicSharedMemorySize is a property
 // of (function, DEVICE): a process that drives several GPUs (nn.DataParallel: one Python thread per device,
 // bts_test.py:91) must set it on each of them.  `done` is one bit per device ordinal, owned by the kernel

@@ -4,7 +4,7 @@
 // are still on the chip.
 //
 // Launch shape (the idiom of pack_weights_kernel / conv_wgrad_batch_kernel): a device table holds one record per parameter
-// with a `first_block` prefix sum; a workgroup finds its record by binary search over blockIdx.x and derives its chunk or
+// with a `first_block` prefix sum; a workgroup finds its record with bts_table_find (common.h) and derives its chunk or
 // tile from its rank inside the record.  Hyper-parameters come BY VALUE, up to 8 records, every table record names one.
 // Nothing is read from the host during the launch; no allocation, no synchronisation; hipGraph-capturable.
 //
@@ -178,12 +178,7 @@ __global__ __launch_bounds__(AW_THREADS) void adamw_step_kernel(const AdamwRec* 
         const float s = *skip;
         if (!(s == 0.f)) return;                    // non-zero or NaN: leave every byte untouched
     }
-    int lo = 0, hi = n - 1;                         // the record whose block range holds blockIdx.x
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (table[mid].first_block <= (long)blockIdx.x) lo = mid; else hi = mid - 1;
-    }
-    const AdamwRec e = table[lo];
+    const AdamwRec e = table[bts_table_find(table, n, &AdamwRec::first_block)];
     const long rank = (long)blockIdx.x - e.first_block;
     if (rank < 0 || rank >= e.n_blocks) return;     // a grid larger than the plan's: nothing to do (uniform per block)
     const AdamwHyperDev h = hy.h[e.hyper & (AW_MAX_HYPER - 1)];

@@ -217,6 +217,32 @@ def test_wgrad_fp32_products_within_the_summation_bound(name):
     assert bool((err <= bound).all()), (name, ratio)
 
 
+@pytest.mark.parametrize("name", ["t32_s16", "t64_s160"])
+def test_dw_is_the_documented_fixed_order_fold_of_the_partials(name):
+    """Float operands, where the summation order shows: after the launch the workspace holds the class partials as
+    [split][class][c_out][4*c_in]; dw[co][3*ky+kx][ci] has the bits of ((r0 + r1) + r2) + r3, r_cls = wgrad_cases.sum_splits
+    over the splits of class cls = 2*py + px at its tap (tau_py(ky), tau_px(kx)), tau_0 = (0,1,1), tau_1 = (0,0,1).
+    16 splits stay in the one-at-a-time loop, 160 run the four-at-a-time loop and its tail."""
+    from wgrad_cases import sum_splits
+    c = uc.BY_NAME[name]
+    g = _gen(name)
+    bm, bn, split, pps = uc.plan_of(c)
+    assert split == int(name.rsplit("_s", 1)[1])
+    x = torch.randn((c.B, c.c_in, c.h, c.w), generator=g)
+    dy = torch.randn((c.B, c.c_out, 2 * c.h, 2 * c.w), generator=g)
+    ws = torch.full((c.ws_floats,), SENTINEL, device="cuda")
+    dw = _run_wgrad(c, x, dy, ws)().cpu()
+    p = ws[:split * 16 * c.c_out * c.c_in].cpu().numpy().reshape(split, 4, c.c_out, 4, c.c_in)
+    tau = ops._SUBPIX_TAU
+    want = np.empty((c.c_out, 9, c.c_in), np.float32)
+    for ky in range(3):
+        for kx in range(3):
+            r = [sum_splits(p[:, cls, :, 2 * tau[cls >> 1][ky] + tau[cls & 1][kx], :]) for cls in range(4)]
+            want[:, 3 * ky + kx, :] = ((r[0] + r[1]) + r[2]) + r[3]
+    want = torch.from_numpy(want)
+    assert torch.equal(dw, want), "%s, split %d: %d of %d elements differ" % (name, split, int((dw != want).sum()), dw.numel())
+
+
 # ------------------------------------------------------------------------------------------------- node and path
 def _upconv_module(cin, cout, wt):
     from bts_amd import bts as M

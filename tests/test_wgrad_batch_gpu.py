@@ -216,6 +216,32 @@ def test_fp32_products_within_the_summation_bound(name):
         assert bool((err <= bound).all()), (c.name, ratio)
 
 
+@pytest.mark.parametrize("name", ["t64_geometries", "mixed"])
+def test_dw_is_the_documented_fixed_order_sum_of_the_partials(name):
+    """Float operands, where the summation order shows: after the launch each split problem's partials sit at its plan's
+    ws_offset as [split][bundle][c_out][N], and its dw has the bits of wc.sum_splits over them.  t64_geometries splits up
+    to 615 ways (the four-at-a-time loop), mixed 6 to 25 ways beside an unsplit problem; the workspace outside the planned
+    regions -- all of it, for an unsplit problem -- keeps its sentinel."""
+    ws_floats, cases = bc.BATCHES[name]
+    problems, bases = _build(name, False)
+    batch = ops.WgradBatch(problems, bases, ws_floats)
+    splits = [p[2] for p in batch.plan]
+    assert min(splits) == 1 and max(splits) > (64 if name == "t64_geometries" else 16)
+    ws = torch.full((ws_floats,), SENTINEL, device="cuda")
+    dws = batch.run(bases, ws)
+    planned = torch.zeros(ws_floats, dtype=torch.bool, device="cuda")
+    for c, dw, (_, _, split, _, off) in zip(cases, dws, batch.plan):
+        if split == 1:
+            assert off == -1
+            continue
+        n = bc.dw_floats(c)
+        planned[off:off + split * n] = True
+        want = torch.from_numpy(wc.sum_splits(ws[off:off + split * n].cpu().numpy().reshape(split, n))).reshape(dw.shape)
+        got = dw.cpu()
+        assert torch.equal(got, want), "%s / %s, split %d: %d of %d elements differ" % (name, c.name, split, int((got != want).sum()), n)
+    assert bool((ws[~planned] == SENTINEL).all()), "the launch wrote workspace outside the split problems' regions"
+
+
 def test_one_table_serves_buffers_at_other_addresses_without_a_sync():
     name = "mixed_small_ws"
     ws_floats, cases = bc.BATCHES[name]

@@ -148,6 +148,25 @@ def test_wgrad_fp32_products_within_the_summation_bound(name):
     assert bool((err <= bound).all()), (name, ratio)
 
 
+@pytest.mark.parametrize("name", wc.FLOAT_CASES)
+def test_dw_is_the_documented_fixed_order_sum_of_the_partials(name):
+    """Float operands, where the summation order shows: after a split launch the workspace still holds the partials as
+    [split][bundle][c_out][N]; dw has the bits of wc.sum_splits over them.  The splits (16, 126, 84, 7, 768) reach fewer
+    splits than lanes, the one-at-a-time loop alone and the four-at-a-time loop with a tail."""
+    c = wc.BY_NAME[name]
+    g = _gen(c)
+    H, W = wc.out_hw(c)
+    bm, bn, split, pps = wc.plan_of(c)
+    assert split > 1
+    x = torch.randn(c.B, c.h, c.w, c.c_in, generator=g)
+    dy = torch.randn(c.B, H, W, c.c_out, generator=g)
+    ws = torch.full((c.ws_floats,), SENTINEL, device="cuda")
+    dw = _run(c, x, dy, None, None, ws)().cpu()
+    partials = ws[:split * dw.numel()].cpu().numpy().reshape(split, -1)
+    want = torch.from_numpy(wc.sum_splits(partials)).reshape(dw.shape)
+    assert torch.equal(dw, want), "%s, split %d: %d of %d elements differ" % (name, split, int((dw != want).sum()), dw.numel())
+
+
 @pytest.mark.parametrize("tile,c", wc.PATH_CASES, ids=lambda v: v.name if hasattr(v, "name") else "%dx%d" % v)
 def test_training_path_hands_wgrad_the_same_problem(tile, c):
     """train.conv2d(...).backward gives the same weight.grad bits as ops.conv_wgrad on the same views with a workspace

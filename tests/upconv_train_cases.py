@@ -30,12 +30,14 @@ WGRAD_CASES = [
     _c("t64_unsplit_1step", 3, 5, 7, 128, 64, (64, 64), False),                       # M 105, three frames
     _c("t64_s2", 1, 13, 20, 128, 32, (64, 64), True, ws_floats=16 * 32 * 128 * 2),    # M 260: 4 pixels in the last K-step
     _c("t64_w1_h1", 5, 1, 1, 16, 8, (64, 64), False),                                 # a 1x1 map: every tap but one is padding
+    _c("t64_s160", 4, 64, 80, 16, 8, (64, 64), True, ws_floats=4 * MI),               # M 20480: 160 splits of 128 pixels, the
+                                                                                      # fold's four-at-a-time loop plus its tail
 ]
 
 BY_NAME = {c.name: c for c in WGRAD_CASES}
 
-# float-valued test: one split case per tile
-WGRAD_FLOAT_CASES = ["t128_s4", "t64x128_s2", "t32_s16", "t64_s2"]
+# float-valued test: one split case per tile, and the 160-split case (the only one in the fold's four-at-a-time loop)
+WGRAD_FLOAT_CASES = ["t128_s4", "t64x128_s2", "t32_s16", "t64_s2", "t64_s160"]
 
 # input gradient: (B, h, w, c_in, c_out)
 DGRAD_CASES = [

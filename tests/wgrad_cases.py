@@ -82,6 +82,30 @@ PATH_CASES = [
 ]
 
 
+def sum_splits(p):
+    """The documented fixed-order sum of split partials (csrc/wgrad.hip: sum_splits + the 16-lane finish), restated in
+    numpy float32.  p: [split, ...] float32.  Lane j of 16 starts at split j, adds four at a time as
+    (p[s] + p[s+16]) + (p[s+32] + p[s+48]) while s + 48 < split, then one at a time in steps of 16; the 16 lane sums are
+    added left to right."""
+    import numpy as np
+    assert p.dtype == np.float32
+    split = p.shape[0]
+    lanes = []
+    for j in range(16):
+        v, s = np.zeros(p.shape[1:], np.float32), j
+        while s + 48 < split:
+            v = v + ((p[s] + p[s + 16]) + (p[s + 32] + p[s + 48]))
+            s += 64
+        while s < split:
+            v = v + p[s]
+            s += 16
+        lanes.append(v)
+    r = lanes[0]
+    for v in lanes[1:]:
+        r = r + v
+    return r
+
+
 def out_hw(c):
     H = (c.h * c.up + 2 * c.pad - c.dil * (c.ksize - 1) - 1) // c.stride + 1
     W = (c.w * c.up + 2 * c.pad - c.dil * (c.ksize - 1) - 1) // c.stride + 1
