@@ -1,5 +1,6 @@
-// Halo-tile convolution in the "fp32 emulated on the bf16 matrix cores" arithmetic (bts_conv_desc.precision = 1; included by
-// conv_mfma.hip inside its anonymous namespace, after conv_halo.inc).
+// The bf16 halo tile: the producer and the consumer body of conv_halo_emu_kernel (below: bts_conv_desc.precision = 1 and 2)
+// and of conv_tail_bf16_kernel (conv_tail_bf16.inc).  Included by conv_mfma.hip inside its anonymous namespace, after
+// conv_halo.inc.
 //
 // The arithmetic is conv_fwd_kernel's PREC mode (split_store: every fp32 operand = three bf16 pieces h + m + l by
 // truncation, six v_mfma_f32_32x32x16_bf16 per 16 k of a 32x32 block -- hh, hm, mh, hl, lh, mm -- accumulated in fp32;
@@ -15,222 +16,251 @@
 //     unpadded 64-byte rows whose four 16-byte chunks are XOR-swizzled with bits 2-3 of the row (the swizzle is applied
 //     to the per-lane SOURCE address; the reader applies it again: conflict-free ds_read_b128, emu_off's layout).
 //
-// Eight waves in two ROLES.  Waves 0..3 (one per SIMD) are CONSUMERS: 2 (patch-row pairs) x 2 (channel halves), each a
-// 64-pixel x BN/2-channel tile -- LDS fragment reads and MFMAs only, 12 ds_read_b128 per 24 MFMAs.  Waves 4..7 (their SIMD
-// partners) are PRODUCERS: they issue the weight DMA, load the next chunk's patch, split it and write it to LDS.  In the
-// first version every wave did both, in lockstep with its SIMD partner: DMA issue (~100 cycles per wave instruction),
-// split arithmetic and waits then stopped BOTH waves of a SIMD at once and the matrix pipe idled through them (188 ->
-// see DESIGN 3b for the measured steps).  THREE weight stages: the DMA for step s+2 is issued at the start of step s into the stage that step s-1 read (the barrier that ended
-// step s-1 protects it); before the barrier that ends step s every wave waits, with a COUNTED vmcnt, for everything but
-// its own operations of step s -- so the tile of step s+1 has landed and the tile of s+2 stays in flight across the
-// barrier (raw s_barrier: __syncthreads() would drain the DMA, cdna_hip_programming.md "Pipelining across barriers").
-// Every vector-memory operation of the loop is unconditional (clamped), so the counts are compile-time constants.  The
-// next chunk's patch trickles in one 64-pixel pass per tap-step: loaded in step t by loads the compiler does not track
-// (load_untracked), split and written in step t+1 behind a counted wait.
-// LDS image of the patch: three bf16 planes of UNPADDED 64-byte pixel rows (32 channels); the four 16-byte chunks of a row
+// NP = 1 is the bf16 mode (bts_conv_desc.precision = 2): the same tile with ONE plane -- the patch rounded to nearest even
+// on its way to LDS (rne_store), the weights pre-rounded offline (ops.round_bf16, [class][1][c_out_pad][k_pad]) -- and one
+// v_mfma_f32_32x32x16_bf16 per 16 k of a 32x32 block instead of six.  A third of the LDS and of the weight DMA.
+//
+// Eight waves in two ROLES.  Waves 0..3 (one per SIMD) are CONSUMERS (halo_emu_consume): 2 (patch-row pairs) x 2 (channel
+// halves), each a 64-pixel x BN/2-channel tile -- LDS fragment reads and MFMAs only, 12 ds_read_b128 per 24 MFMAs.  Waves
+// 4..7 (their SIMD partners) are PRODUCERS (halo_emu_produce): they issue the weight DMA, load the next chunk's patch,
+// split it and write it to LDS.  In the first version every wave did both, in lockstep with its SIMD partner: DMA issue
+// (~100 cycles per wave instruction), split arithmetic and waits then stopped BOTH waves of a SIMD at once and the matrix
+// pipe idled through them (see DESIGN 3b for the measured steps).
+//
+// THREE weight stages: the DMA for step s+2 is issued at the start of step s into the stage that step s-1 read (the
+// barrier that ended step s-1 protects it); before the barrier that ends step s every wave waits, with a COUNTED vmcnt,
+// for everything but its own operations of step s -- so the tile of step s+1 has landed and the tile of s+2 stays in flight
+// across the barrier (raw s_barrier: __syncthreads() would drain the DMA, cdna_hip_programming.md "Pipelining across
+// barriers").  Every vector-memory operation of the loop is unconditional (clamped), so the counts are compile-time
+// constants.  The next chunk's patch trickles in one 32-pixel pass (two with KS 2) per tap-step: loaded in step t by loads
+// the compiler does not track (load_untracked), converted and written in step t+1 behind a counted wait.
+//
+// LDS image of the patch: NP bf16 planes of UNPADDED 64-byte pixel rows (32 channels); the four 16-byte chunks of a row
 // are XOR-swizzled with bits 2-3 of the pixel index.  A ds_read_b128 lane group covers 16 pixels that are distinct mod
 // 16 whatever uniform shift the tap adds (base + {0-3, 12-15, 20-27}), so (pixel & 3, chunk ^ (pixel >> 2 & 3)) -- the
 // 16-byte bank slot -- is distinct too: conflict-free for every tap.  The swizzle makes a tap's address non-additive, so
 // the KS*KS x 2 fragment addresses of a lane are computed once, before the loop (they do not depend on the chunk).
-//
-// NP = 1 is the bf16 mode (bts_conv_desc.precision = 2): the same tile with ONE plane -- the patch rounded to nearest even
-// on its way to LDS (rne_store), the weights pre-rounded offline (ops.round_bf16, [class][1][c_out_pad][k_pad]) -- and one
-// v_mfma_f32_32x32x16_bf16 per 16 k of a 32x32 block instead of six.  A third of the LDS and of the weight DMA.
 __device__ __forceinline__ int emu_a_off(int pix, int chunk16) { return pix * EMU_ROW_BYTES + (((chunk16 ^ (pix >> 2)) & 3) << 4); }
 
+// Sizes of one tile: the input patch of 4 x 32 outputs under a KS x KS kernel, and its LDS image -- As [2][NP planes][NPIX]
+// [64 B], then Bs [3 stages][NP planes][BN][64 B]
 template <int BN, int KS, int NP>
-constexpr int halo_emu_lds_bytes() {
-    return 2 * NP * ((4 + KS - 1) * (32 + KS - 1)) * EMU_ROW_BYTES + 3 * NP * BN * EMU_ROW_BYTES;
-}
-
-// global_load_dwordx4 whose result the compiler does not track: beside LDS-DMA traffic hipcc waits vmcnt(0) at the first
-// use of any ordinary load's result, which would drain the weight ring every step.  The consumer passes the registers
-// through wait_vm<N>() first (a counted s_waitcnt the value depends on).
-__device__ __forceinline__ void load_untracked(f32x4& dst, const float* p) {
-    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(dst) : "v"(p) : "memory");
-}
-template <int N> __device__ __forceinline__ void wait_vm(f32x4& v0, f32x4& v1, f32x4& v2) {
-    asm volatile("s_waitcnt vmcnt(%3)" : "+v"(v0), "+v"(v1), "+v"(v2) : "n"(N) : "memory");
-}
-
-template <int BN, int KS, int NP>
-__global__ __launch_bounds__(512, 2) void conv_halo_emu_kernel(const ConvArgs a) {
+struct HaloEmuGeom {
+    static constexpr int TW = 32, TH = 4, PH = TH + KS - 1, PW = TW + KS - 1, NPIX = PH * PW, T = KS * KS;
+    static constexpr int A_PLANE = NPIX * EMU_ROW_BYTES, A_BUF = NP * A_PLANE;
+    static constexpr int B_PLANE = BN * EMU_ROW_BYTES, B_STAGE = NP * B_PLANE;
+    static constexpr int LDS_BYTES = 2 * A_BUF + 3 * B_STAGE;
     static_assert(NP == 3 || NP == 1, "NP: 3 bf16x3 planes (precision 1) or one bf16 plane (precision 2)");
-    constexpr int MF = 32, TM = 2, TN = BN / 2 / MF;      // consumer wave tile: 2 patch rows (64 pixels) x BN/2 channels
-    constexpr int TW = 32, TH = 4, PH = TH + KS - 1, PW = TW + KS - 1, NPIX = PH * PW, T = KS * KS;
-    constexpr int RPP = 256 / 8;                         // patch pixels staged per pass by the 256 producer threads
-    constexpr int PA = (NPIX + RPP - 1) / RPP;           // passes over the patch: 7 (3x3), 6 (2x2)
-    constexpr int PPS = (PA + T - 2) / (T - 1);          // passes per tap-step: 1 (3x3), 2 (2x2)
-    constexpr int A_PLANE = NPIX * EMU_ROW_BYTES, A_BUF = NP * A_PLANE;
-    constexpr int B_PLANE = BN * EMU_ROW_BYTES, B_STAGE = NP * B_PLANE;
-    constexpr int NI = NP * BN / 16;                     // DMA wave-instructions per weight stage (16 rows x 64 B each)
-    constexpr int NIW = NI / 4;                          // ... per producer wave: 6 / 3 (BN 128 / 64, NP 3), 2 / 1 (NP 1)
-    static_assert(NI % 4 == 0 && PPS * (T - 1) >= PA, "producer work divides evenly");
-    static_assert(A_PLANE % 16 == 0 && TN >= 1, "layout");
-    typedef float acc_t __attribute__((ext_vector_type(16)));
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    char* const As = smem_raw;                            // [2][NP planes][NPIX][64 B]
-    char* const Bs = smem_raw + 2 * A_BUF;                // [3 stages][NP planes][BN][64 B]
+};
 
-    // ---- tile decode (as conv_halo_kernel)
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int swz = xcd_swizzle(bid, nwg);
-    const int cls = a.subpix ? (swz & 3) : 0;
-    const int tcl = a.subpix ? (swz >> 2) : swz;
-    const int mt_idx = tcl / a.n_ntiles, nt_idx = tcl - mt_idx * a.n_ntiles;
-    const int n0 = nt_idx * BN;
-    const int n_tx = (a.W + TW - 1) / TW, n_ty = (a.H + TH - 1) / TH;
+// 4 x 32 output tiles of one H x W frame, and the share of that tile grid that is real pixels
+inline long tiles_4x32(int H, int W, double* fill = nullptr) {
+    const long n = (long)((H + 3) / 4) * ((W + 31) / 32);
+    if (fill) *fill = (double)H * W / (double)(n * 128);
+    return n;
+}
+
+// Tile `tcl` of a launch (or of its parity class) -> channel tile n0, frame, top-left output pixel (as conv_halo_kernel)
+struct Tile4x32 { int n0, bfr, y0, x0; };
+template <int BN>
+__device__ __forceinline__ Tile4x32 decode_tile_4x32(int tcl, int n_ntiles, int H, int W) {
+    const int mt_idx = tcl / n_ntiles, nt_idx = tcl - mt_idx * n_ntiles;
+    const int n_tx = (W + 31) / 32, n_ty = (H + 3) / 4;
     const int bfr = mt_idx / (n_tx * n_ty);
     const int trem = mt_idx - bfr * (n_tx * n_ty);
     const int tyi = trem / n_tx;
-    const int y0 = tyi * TH, x0 = (trem - tyi * n_tx) * TW;
-    const int spy = cls >> 1, spx = cls & 1;
-    const int pad_y = a.subpix ? 1 - spy : a.pad, pad_x = a.subpix ? 1 - spx : a.pad;
+    return Tile4x32{nt_idx * BN, bfr, tyi * 4, (trem - tyi * n_tx) * 32};
+}
 
-    const int tid = threadIdx.x;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-    const int nchunks = a.c_in_ld / BK;                   // host: c_in_ld % 32 == 0
-    const int nsteps = nchunks * T;
+// One patch pass of a producer thread in flight: four channels of one pixel and, with AFFINE, their prologue scale and
+// shift.  Without AFFINE the two do not exist: a "+v" operand would keep their registers alive.
+template <bool AFFINE> struct PatchRegs { f32x4 v = {0.f, 0.f, 0.f, 0.f}, ps = {1.f, 1.f, 1.f, 1.f}, pb = {0.f, 0.f, 0.f, 0.f}; };
+template <> struct PatchRegs<false> { f32x4 v = {0.f, 0.f, 0.f, 0.f}; };
 
-    if (wv >= 4) {
-        // =============================================================== PRODUCER waves 4..7 (one per SIMD)
-        const int ptid = tid - 256;
-        const int lrow = ptid >> 3, lk = (ptid & 7) * 4;
-        // patch elements of this thread (pass p: patch pixel p*RPP + lrow, channels lk..lk+3 of the chunk)
-        unsigned abase[PA];
-        int awr[PA];                                      // LDS byte offset of this thread's 8 bytes inside a plane
-        unsigned inimg = 0, inpatch = 0;
+// global_load_dwordx4 whose result the compiler does not track: beside LDS-DMA traffic hipcc waits vmcnt(0) at the first
+// use of any ordinary load's result, which would drain the weight ring every step.  The consumer passes the registers
+// through wait_vm<N>() first (a counted s_waitcnt the values depend on).
+__device__ __forceinline__ void load_untracked(f32x4& dst, const float* p) {
+    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(dst) : "v"(p) : "memory");
+}
+template <int N, bool AFFINE> __device__ __forceinline__ void wait_vm(PatchRegs<AFFINE>& r) {
+    if constexpr (AFFINE) asm volatile("s_waitcnt vmcnt(%3)" : "+v"(r.v), "+v"(r.ps), "+v"(r.pb) : "n"(N) : "memory");
+    else asm volatile("s_waitcnt vmcnt(%1)" : "+v"(r.v) : "n"(N) : "memory");
+}
+// ... with `k` patch passes (LPP loads each) and BASE other operations younger than r's loads; k is a constant once the
+// step loop is unrolled.  k <= 3: the later pass of the same step and the two of the next (KS 2).
+template <int BASE, int LPP, bool AFFINE> __device__ __forceinline__ void wait_vm_passes(int k, PatchRegs<AFFINE>& r) {
+    switch (k) {
+        case 0: wait_vm<BASE>(r); break;
+        case 1: wait_vm<BASE + LPP>(r); break;
+        case 2: wait_vm<BASE + 2 * LPP>(r); break;
+        case 3: wait_vm<BASE + 3 * LPP>(r); break;
+        default: wait_vm<0>(r); break;
+    }
+}
+// The raw barrier between tap-steps, behind the wait that says what has to be complete by then: every LDS operation of the
+// wave and all but its VM youngest vector-memory operations (NO_VM: a consumer has none)
+constexpr int NO_VM = -1;
+template <int VM> __device__ __forceinline__ void wait_then_barrier() {
+    if constexpr (VM == NO_VM) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" :: "n"(VM) : "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+}
+
+// What a producer reads
+struct HaloEmuSource {
+    const float* x; unsigned x_pix_stride; int H, W, bfr, y0, x0, pad_y, pad_x;      // NHWC input, the tile, the padding
+    const float* pre_scale; const float* pre_shift; bool has_pre; int pre_relu;      // AFFINE: scale / shift per input channel
+                                                                                     // (any readable address without has_pre)
+    const unsigned short* w; int w_rows, w_ld;     // bf16 weights [NP planes][w_rows][w_ld], k = tap * tap_stride + channel
+    int tap_stride;
+    int n0, nchunks;                               // first output channel of the tile; 32-channel chunks of the K axis
+};
+
+// PRODUCER waves 4..7 (one per SIMD), from the start of the kernel to the end of the K loop.  `before_first_barrier` runs
+// once the patch of chunk 0 is stored.
+template <int BN, int KS, int NP, bool AFFINE, typename Extra>
+__device__ __forceinline__ void halo_emu_produce(const HaloEmuSource& in, char* const As, char* const Bs, int tid, int wv,
+                                                 Extra&& before_first_barrier) {
+    using G = HaloEmuGeom<BN, KS, NP>;
+    constexpr int PW = G::PW, NPIX = G::NPIX, T = G::T;
+    constexpr int RPP = 256 / 8;                         // patch pixels staged per pass by the 256 producer threads
+    constexpr int PA = (NPIX + RPP - 1) / RPP;           // passes over the patch: 7 (3x3), 6 (2x2)
+    constexpr int PPS = (PA + T - 2) / (T - 1);          // passes per tap-step: 1 (3x3), 2 (2x2)
+    constexpr int LPP = AFFINE ? 3 : 1;                  // loads per pass: the values, and their scale and shift
+    constexpr int NI = NP * BN / 16;                     // DMA wave-instructions per weight stage (16 rows x 64 B each)
+    constexpr int NIW = NI / 4;                          // ... per producer wave: 6 / 3 (BN 128 / 64, NP 3), 2 / 1 (NP 1)
+    static_assert(NI % 4 == 0 && PPS * (T - 1) >= PA && PPS <= 2, "producer work divides evenly");
+    typedef PatchRegs<AFFINE> regs_t;
+    const int ptid = tid - 256, lane = tid & 63;
+    const int lrow = ptid >> 3, lk = (ptid & 7) * 4;
+    const int nsteps = in.nchunks * T;
+    // patch elements of this thread (pass p: patch pixel p*RPP + lrow, channels lk..lk+3 of the chunk)
+    unsigned abase[PA];
+    int awr[PA];                                      // LDS byte offset of this thread's 8 bytes inside a plane
+    unsigned inimg = 0, inpatch = 0;
+#pragma unroll
+    for (int p = 0; p < PA; ++p) {
+        const int pix = p * RPP + lrow;
+        const int pyy = pix / PW, pxx = pix - pyy * PW;
+        const int gy = in.y0 - in.pad_y + pyy, gx = in.x0 - in.pad_x + pxx;
+        const bool inp = pix < NPIX;
+        const bool ok = inp && (unsigned)gy < (unsigned)in.H && (unsigned)gx < (unsigned)in.W;
+        const int yc = min(max(gy, 0), in.H - 1), xc = min(max(gx, 0), in.W - 1);
+        abase[p] = ((unsigned)in.bfr * (unsigned)(in.H * in.W) + (unsigned)(yc * in.W + xc)) * in.x_pix_stride + (unsigned)lk;
+        awr[p] = emu_a_off(inp ? pix : 0, lk >> 3) + (lk & 7) * 2;
+        inimg |= (ok ? 1u : 0u) << p;
+        inpatch |= (inp ? 1u : 0u) << p;
+    }
+    auto load_a = [&](int p, int chunk, regs_t& r) {
+        const unsigned cs = (unsigned)(chunk * BK);
+        load_untracked(r.v, in.x + (abase[p] + cs));
+        if constexpr (AFFINE) {
+            load_untracked(r.ps, in.pre_scale + (cs + lk));
+            load_untracked(r.pb, in.pre_shift + (cs + lk));
+        }
+    };
+    auto store_a = [&](int p, char* dstbuf, regs_t r) {
+        if (!((inpatch >> p) & 1u)) return;
+        f32x4 v = r.v;
+        if constexpr (AFFINE) {
+            if (in.has_pre) v = v * r.ps + r.pb;
+            if (in.pre_relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+        }
+        const bool ok = (inimg >> p) & 1u;                               // zero padding AFTER the prologue
+        v.x = ok ? v.x : 0.f; v.y = ok ? v.y : 0.f; v.z = ok ? v.z : 0.f; v.w = ok ? v.w : 0.f;
+        plane_store<NP>(dstbuf, G::A_PLANE, awr[p], v);
+    };
+    // weight DMA: producer wave pw sends wave-instructions q = pw + 4u: rows [16 rb, 16 rb + 16) of plane q / (BN/16)
+    const int pw = wv - 4;
+    unsigned wsrc[NIW];                               // per-lane source element offset (without the step's k offset)
+    int wdst[NIW];                                    // wave-uniform LDS byte offset inside a stage
+#pragma unroll
+    for (int u = 0; u < NIW; ++u) {
+        const int q = pw + 4 * u;
+        const int plane = q / (BN / 16), rb = q - plane * (BN / 16);
+        const int r = rb * 16 + (lane >> 2);
+        const int chunk = (lane & 3) ^ ((r >> 2) & 3);     // source-side swizzle (the reader XORs again)
+        int n = in.n0 + r;
+        n = n < in.w_rows ? n : in.w_rows - 1;              // rows past the last feed outputs that are never stored
+        wsrc[u] = ((unsigned)plane * (unsigned)in.w_rows + (unsigned)n) * (unsigned)in.w_ld + (unsigned)(chunk * 8);
+        wdst[u] = plane * G::B_PLANE + rb * 1024;
+    }
+    auto dma_b = [&](int step, int stage_idx) {        // the weight tile of `step` (clamped: a repeat goes to a stage nobody reads)
+        const int sc = step < nsteps ? step : nsteps - 1;
+        const int chunk = sc / T, tap = sc - chunk * T;
+        const unsigned koff = (unsigned)(tap * in.tap_stride + chunk * BK);
+        char* const stage = Bs + stage_idx * G::B_STAGE;
+#pragma unroll
+        for (int u = 0; u < NIW; ++u)
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(in.w + (wsrc[u] + koff)),
+                                             (__attribute__((address_space(3))) void*)(stage + wdst[u]), 16, 0, 0);
+    };
+
+    // prologue: weight tiles of steps 0 and 1 in flight, the whole patch of chunk 0
+    dma_b(0, 0);
+    dma_b(1, 1);
+    {
+        regs_t ra[PA];
+#pragma unroll
+        for (int p = 0; p < PA; ++p) load_a(p, 0, ra[p]);
 #pragma unroll
         for (int p = 0; p < PA; ++p) {
-            const int pix = p * RPP + lrow;
-            const int pyy = pix / PW, pxx = pix - pyy * PW;
-            const int gy = y0 - pad_y + pyy, gx = x0 - pad_x + pxx;
-            const bool inp = pix < NPIX;
-            const bool ok = inp && (unsigned)gy < (unsigned)a.H && (unsigned)gx < (unsigned)a.W;
-            const int yc = min(max(gy, 0), a.H - 1), xc = min(max(gx, 0), a.W - 1);
-            abase[p] = ((unsigned)bfr * (unsigned)(a.H * a.W) + (unsigned)(yc * a.W + xc)) * (unsigned)a.x_pix_stride + (unsigned)lk;
-            awr[p] = emu_a_off(inp ? pix : 0, lk >> 3) + (lk & 7) * 2;
-            inimg |= (ok ? 1u : 0u) << p;
-            inpatch |= (inp ? 1u : 0u) << p;
+            wait_vm<0>(ra[p]);
+            store_a(p, As, ra[p]);
         }
-        const bool has_pre = a.pre_scale != nullptr;
-        const float* const psrc = has_pre ? a.pre_scale : a.w;       // always a valid address: the loads are unconditional
-        const float* const bsrc = has_pre ? a.pre_shift : a.w;
-        auto load_a = [&](int p, int chunk, f32x4& v, f32x4& ps, f32x4& pb) {
-            const unsigned cs = (unsigned)(chunk * BK);
-            load_untracked(v, a.x + (abase[p] + cs));
-            load_untracked(ps, psrc + (cs + lk));
-            load_untracked(pb, bsrc + (cs + lk));
-        };
-        auto store_a = [&](int p, char* dstbuf, f32x4 v, f32x4 ps, f32x4 pb) {
-            if (!((inpatch >> p) & 1u)) return;
-            if (has_pre) v = v * ps + pb;
-            if (a.pre_relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
-            const bool ok = (inimg >> p) & 1u;                               // zero padding AFTER the prologue
-            v.x = ok ? v.x : 0.f; v.y = ok ? v.y : 0.f; v.z = ok ? v.z : 0.f; v.w = ok ? v.w : 0.f;
-            plane_store<NP>(dstbuf, A_PLANE, awr[p], v);
-        };
-        // weight DMA: producer wave pw sends wave-instructions q = pw + 4u: rows [16 rb, 16 rb + 16) of plane q / (BN/16)
-        const int pw = wv - 4;
-        const unsigned short* const wq = reinterpret_cast<const unsigned short*>(a.w_split) + (size_t)cls * NP * a.c_out_pad * a.k_pad;
-        unsigned wsrc[NIW];                               // per-lane source element offset (without the step's k offset)
-        int wdst[NIW];                                    // wave-uniform LDS byte offset inside a stage
-#pragma unroll
-        for (int u = 0; u < NIW; ++u) {
-            const int q = pw + 4 * u;
-            const int plane = q / (BN / 16), rb = q - plane * (BN / 16);
-            const int r = rb * 16 + (lane >> 2);
-            const int chunk = (lane & 3) ^ ((r >> 2) & 3);     // source-side swizzle (the reader XORs again)
-            int n = n0 + r;
-            n = n < a.c_out_pad ? n : a.c_out_pad - 1;          // rows past c_out_pad feed outputs that are never stored
-            wsrc[u] = ((unsigned)plane * (unsigned)a.c_out_pad + (unsigned)n) * (unsigned)a.k_pad + (unsigned)(chunk * 8);
-            wdst[u] = plane * B_PLANE + rb * 1024;
-        }
-        auto dma_b = [&](int step, int stage_idx) {        // the weight tile of `step` (clamped: a repeat goes to a stage nobody reads)
-            const int sc = step < nsteps ? step : nsteps - 1;
-            const int chunk = sc / T, tap = sc - chunk * T;
-            const unsigned koff = (unsigned)(tap * a.c_in_ld + chunk * BK);
-            char* const stage = Bs + stage_idx * B_STAGE;
-#pragma unroll
-            for (int u = 0; u < NIW; ++u)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(wq + (wsrc[u] + koff)),
-                                                 (__attribute__((address_space(3))) void*)(stage + wdst[u]), 16, 0, 0);
-        };
+    }
+    before_first_barrier();
+    wait_then_barrier<0>();
 
-        // prologue: weight tiles of steps 0 and 1 in flight, the whole patch of chunk 0
-        dma_b(0, 0);
-        dma_b(1, 1);
-        {
-            f32x4 va[PA], ps[PA], pb[PA];
+    // Per step: DMA of step s+2 (NIW ops), then the loads of this step's patch passes (LPP ops each, PPS passes while any
+    // are left); the passes loaded in step t-1 are converted and written now, behind a counted wait.  Every operation is
+    // unconditional (clamped), so all counts are compile-time constants.
+    auto npass = [](int t) { return t * PPS < PA ? (t * PPS + PPS <= PA ? PPS : PA - t * PPS) : 0; };      // passes loaded in step t
+    regs_t ra[2][PPS];                                 // two sets: step t's loads fly while step t-1's are written
+    int stage3 = 0;                                    // s % 3 (uniform)
+    for (int chunk = 0; chunk < in.nchunks; ++chunk) {
+        char* nxtA = As + ((chunk + 1) & 1) * G::A_BUF;
+        const bool more_chunks = chunk + 1 < in.nchunks;
+        const int nchunk_c = more_chunks ? chunk + 1 : chunk;      // clamped: the loads are unconditional
 #pragma unroll
-            for (int p = 0; p < PA; ++p) load_a(p, 0, va[p], ps[p], pb[p]);
+        for (int t = 0; t < T; ++t) {
+            const int s = chunk * T + t;
+            const int nload = npass(t);
+            dma_b(s + 2, stage3 == 0 ? 2 : stage3 - 1);           // into the stage step s-1 read ((s+2) % 3)
 #pragma unroll
-            for (int p = 0; p < PA; ++p) {
-                wait_vm<0>(va[p], ps[p], pb[p]);
-                store_a(p, As, va[p], ps[p], pb[p]);
-            }
-        }
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-
-        // Per step: DMA of step s+2 (NIW ops), then the loads of this step's patch passes (3 ops each, PPS passes while any
-        // are left); the passes loaded in step t-1 are split and written now, behind a counted wait.  Every operation is
-        // unconditional (clamped), so all counts are compile-time constants.
-        f32x4 va[2][PPS], ps[2][PPS], pb[2][PPS];          // two sets: step t's loads fly while step t-1's are written
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int u = 0; u < PPS; ++u) { va[i][u] = f32x4{0.f, 0.f, 0.f, 0.f}; ps[i][u] = f32x4{1.f, 1.f, 1.f, 1.f}; pb[i][u] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-        int stage3 = 0;                                    // s % 3 (uniform)
-        for (int chunk = 0; chunk < nchunks; ++chunk) {
-            char* nxtA = As + ((chunk + 1) & 1) * A_BUF;
-            const bool more_chunks = chunk + 1 < nchunks;
-            const int nchunk_c = more_chunks ? chunk + 1 : chunk;      // clamped: the loads are unconditional
-#pragma unroll
-            for (int t = 0; t < T; ++t) {
-                const int s = chunk * T + t;
-                constexpr int dummy = 0; (void)dummy;
-                // passes loaded in this step: t*PPS + u < PA (compile-time after unrolling)
-                const int nload = (t * PPS < PA) ? ((t * PPS + PPS <= PA) ? PPS : PA - t * PPS) : 0;
-                dma_b(s + 2, stage3 == 0 ? 2 : stage3 - 1);           // into the stage step s-1 read ((s+2) % 3)
+            for (int u = 0; u < PPS; ++u)
+                if (t * PPS + u < PA) load_a(t * PPS + u, nchunk_c, ra[t & 1][u]);
+            if (t >= 1) {
 #pragma unroll
                 for (int u = 0; u < PPS; ++u)
-                    if (t * PPS + u < PA) load_a(t * PPS + u, nchunk_c, va[t & 1][u], ps[t & 1][u], pb[t & 1][u]);
-                if (t >= 1) {
-#pragma unroll
-                    for (int u = 0; u < PPS; ++u)
-                        if ((t - 1) * PPS + u < PA) {                  // loaded in step t-1: younger ops = the later passes of
-                            // step t-1 (3 each), this step's DMA (NIW) and loads (3 * nload)
-                            const int younger = 3 * ((((t - 1) * PPS + PPS <= PA) ? PPS : PA - (t - 1) * PPS) - 1 - u) + NIW + 3 * nload;
-                            switch (younger) {                          // compile-time after unrolling
-                                case NIW: wait_vm<NIW>(va[(t - 1) & 1][u], ps[(t - 1) & 1][u], pb[(t - 1) & 1][u]); break;
-                                case NIW + 3: wait_vm<NIW + 3>(va[(t - 1) & 1][u], ps[(t - 1) & 1][u], pb[(t - 1) & 1][u]); break;
-                                case NIW + 6: wait_vm<NIW + 6>(va[(t - 1) & 1][u], ps[(t - 1) & 1][u], pb[(t - 1) & 1][u]); break;
-                                case NIW + 9: wait_vm<NIW + 9>(va[(t - 1) & 1][u], ps[(t - 1) & 1][u], pb[(t - 1) & 1][u]); break;
-                                default: wait_vm<0>(va[(t - 1) & 1][u], ps[(t - 1) & 1][u], pb[(t - 1) & 1][u]); break;
-                            }
-                            if (more_chunks) store_a((t - 1) * PPS + u, nxtA, va[(t - 1) & 1][u], ps[(t - 1) & 1][u], pb[(t - 1) & 1][u]);
-                        }
-                }
-                // the weight tile of step s+1 (DMA issued in step s-1) has landed once all but this step's own ops are done
-                switch (nload) {
-                    case 0: asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" :: "n"(NIW) : "memory"); break;
-                    case 1: asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" :: "n"(NIW + 3) : "memory"); break;
-                    default: asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" :: "n"(NIW + 6) : "memory"); break;
-                }
-                __builtin_amdgcn_s_barrier();
-                asm volatile("" ::: "memory");
-                stage3 = stage3 == 2 ? 0 : stage3 + 1;
+                    if ((t - 1) * PPS + u < PA) {
+                        // loaded in step t-1: younger ops = this step's DMA (NIW), and LPP for each later pass of step t-1
+                        // and each pass of this step
+                        regs_t& r = ra[(t - 1) & 1][u];
+                        wait_vm_passes<NIW, LPP>(npass(t - 1) - 1 - u + nload, r);
+                        if (more_chunks) store_a((t - 1) * PPS + u, nxtA, r);
+                    }
             }
+            // the weight tile of step s+1 (DMA issued in step s-1) has landed once all but this step's own ops are done
+            switch (nload) {                                        // compile-time after unrolling
+                case 0: wait_then_barrier<NIW>(); break;
+                case 1: wait_then_barrier<NIW + LPP>(); break;
+                default: wait_then_barrier<NIW + 2 * LPP>(); break;
+            }
+            stage3 = stage3 == 2 ? 0 : stage3 + 1;
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              // the clamped repeats of the last two steps
-        return;
     }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              // the clamped repeats of the last two steps
+}
 
-    // =================================================================== CONSUMER waves 0..3 (one per SIMD): LDS reads + MFMA only
-    const int cm = wv >> 1, cn = wv & 1;
-    const int li = lane & 31, lh = lane >> 5;
+// CONSUMER waves 0..3 (one per SIMD), from the producers' prologue to the last MFMA: LDS fragment reads + MFMA only.
+// acc[i][j]: patch row cm*TM + i (32 pixels) x channels (cn*TN + j)*32 .. +31 of the tile.
+template <int NP, int TM, int TN, int KS, int A_PLANE, int B_PLANE, typename AccT>
+__device__ __forceinline__ void halo_emu_consume(const char* const As, const char* const Bs, int nchunks, int cm, int cn, int li, int lh,
+                                                 AccT (&acc)[TM][TN]) {
+    constexpr int PW = 32 + KS - 1, T = KS * KS, A_BUF = NP * A_PLANE, B_STAGE = NP * B_PLANE;
     int a_addr[T][TM][2];                                 // fragment byte offsets inside a plane, per (tap, patch row, k16 step)
 #pragma unroll
     for (int t = 0; t < T; ++t)
@@ -243,16 +273,7 @@ __global__ __launch_bounds__(512, 2) void conv_halo_emu_kernel(const ConvArgs a)
     const int sw = (li >> 2) & 3;
     const int b_off0 = (cn * TN * 32 + li) * EMU_ROW_BYTES + (((0 + lh) ^ sw) << 4);      // ks = 0
     const int b_off1 = (cn * TN * 32 + li) * EMU_ROW_BYTES + (((2 + lh) ^ sw) << 4);      // ks = 1
-    acc_t acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();                                    // the producers' prologue
-    asm volatile("" ::: "memory");
+    wait_then_barrier<NO_VM>();                                      // the producers' prologue
 
     constexpr int PA_[6] = {0, 0, 1, 0, 2, 1}, PB_[6] = {0, 1, 0, 2, 0, 1};      // hh, hm, mh, hl, lh, mm (NP 1: the first)
     constexpr int NQ = NP == 3 ? 6 : 1;                                            // products per k16 block
@@ -278,26 +299,65 @@ __global__ __launch_bounds__(512, 2) void conv_halo_emu_kernel(const ConvArgs a)
     };
     // Software pipeline by half a step: the second k16 block of step s-1 runs AFTER the barrier that ends step s-1 (its
     // fragments are in registers), covering the LDS latency of step s's first fragment reads.
-    {
-        int stage3 = 0;
-        for (int chunk = 0; chunk < nchunks; ++chunk) {
-            const char* curA = As + (chunk & 1) * A_BUF;
+    int stage3 = 0;
+    for (int chunk = 0; chunk < nchunks; ++chunk) {
+        const char* curA = As + (chunk & 1) * A_BUF;
 #pragma unroll
-            for (int t = 0; t < T; ++t) {
-                const int s = chunk * T + t;
-                const char* curB = Bs + stage3 * B_STAGE;
-                read_frags(curA, curB, a_addr[t], 0, b_off0, fa0, fb0);
-                if (s > 0) mfmas(fa1, fb1);                           // (s-1, k16 block 1)
-                read_frags(curA, curB, a_addr[t], 1, b_off1, fa1, fb1);
-                mfmas(fa0, fb0);                                      // (s, k16 block 0)
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");    // this step's fragments are in registers: its stage / patch may be overwritten
-                __builtin_amdgcn_s_barrier();
-                asm volatile("" ::: "memory");
-                stage3 = stage3 == 2 ? 0 : stage3 + 1;
-            }
+        for (int t = 0; t < T; ++t) {
+            const int s = chunk * T + t;
+            const char* curB = Bs + stage3 * B_STAGE;
+            read_frags(curA, curB, a_addr[t], 0, b_off0, fa0, fb0);
+            if (s > 0) mfmas(fa1, fb1);                           // (s-1, k16 block 1)
+            read_frags(curA, curB, a_addr[t], 1, b_off1, fa1, fb1);
+            mfmas(fa0, fb0);                                      // (s, k16 block 0)
+            wait_then_barrier<NO_VM>();       // this step's fragments are in registers: its stage / patch may be overwritten
+            stage3 = stage3 == 2 ? 0 : stage3 + 1;
         }
-        mfmas(fa1, fb1);                                              // (last step, k16 block 1)
     }
+    mfmas(fa1, fb1);                                              // (last step, k16 block 1)
+}
+
+// ---- the bf16x3 (NP 3) and bf16 (NP 1) halo-tile convolution of bts_conv_fwd_f32: stride-1 3x3 and sub-pixel 2x2 -----------
+template <int BN, int KS, int NP>
+__global__ __launch_bounds__(512, 2) void conv_halo_emu_kernel(const ConvArgs a) {
+    using G = HaloEmuGeom<BN, KS, NP>;
+    constexpr int MF = 32, TM = 2, TN = BN / 2 / MF;      // consumer wave tile: 2 patch rows (64 pixels) x BN/2 channels
+    static_assert(G::A_PLANE % 16 == 0 && TN >= 1, "layout");
+    typedef float acc_t __attribute__((ext_vector_type(16)));
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    char* const As = smem_raw;
+    char* const Bs = smem_raw + 2 * G::A_BUF;
+
+    const int swz = xcd_swizzle(blockIdx.x, gridDim.x);
+    const int cls = a.subpix ? (swz & 3) : 0;
+    const Tile4x32 tile = decode_tile_4x32<BN>(a.subpix ? (swz >> 2) : swz, a.n_ntiles, a.H, a.W);
+    const int n0 = tile.n0, bfr = tile.bfr, y0 = tile.y0, x0 = tile.x0;
+    const int spy = cls >> 1, spx = cls & 1;
+
+    const int tid = threadIdx.x;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    const int nchunks = a.c_in_ld / BK;                   // host: c_in_ld % 32 == 0
+
+    if (wv >= 4) {
+        const bool has_pre = a.pre_scale != nullptr;      // without: a.w, always a valid address (the loads are unconditional)
+        const HaloEmuSource src = {a.x, (unsigned)a.x_pix_stride, a.H, a.W, bfr, y0, x0, a.subpix ? 1 - spy : a.pad, a.subpix ? 1 - spx : a.pad,
+                                   has_pre ? a.pre_scale : a.w, has_pre ? a.pre_shift : a.w, has_pre, a.pre_relu,
+                                   reinterpret_cast<const unsigned short*>(a.w_split) + (size_t)cls * NP * a.c_out_pad * a.k_pad,
+                                   a.c_out_pad, a.k_pad, a.c_in_ld, n0, nchunks};
+        halo_emu_produce<BN, KS, NP, true>(src, As, Bs, tid, wv, [] {});
+        return;
+    }
+
+    const int cm = wv >> 1, cn = wv & 1;
+    const int li = lane & 31, lh = lane >> 5;
+    acc_t acc[TM][TN];
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    halo_emu_consume<NP, TM, TN, KS, G::A_PLANE, G::B_PLANE>(As, Bs, nchunks, cm, cn, li, lh, acc);
 
     // ---------------------------------------------------------------- epilogue (NHWC; conv_mfma.hip's compact paths)
     {
@@ -356,15 +416,14 @@ inline bool halo_emu_eligible(const ConvArgs& a, bool nchw) {
 template <int BN, int KS, int NP = 3>
 int launch_halo_emu(const ConvArgs& a0, hipStream_t s) {
     ConvArgs a = a0;
-    constexpr int TW = 32, TH = 4;
-    const long n_mtiles = (long)a.B * ((a.H + TH - 1) / TH) * ((a.W + TW - 1) / TW);
+    const long n_mtiles = (long)a.B * tiles_4x32(a.H, a.W);
     a.n_ntiles = (a.c_out + BN - 1) / BN;
     a.tiles_per_class = (int)(n_mtiles * a.n_ntiles);
     a.ksplit = 1;
     const long nwg = n_mtiles * a.n_ntiles * a.n_classes;
     if (nwg > 0x7fffffffL) return BTS_ERR_INVALID;
     if (g_dry) { *g_dry = ConvChoice{NP == 3 ? BTS_CONV_KIND_HALO_EMU : BTS_CONV_KIND_HALO_BF16, 128, BN, 1}; return 0; }
-    constexpr size_t lds = (size_t)halo_emu_lds_bytes<BN, KS, NP>();
+    constexpr size_t lds = (size_t)HaloEmuGeom<BN, KS, NP>::LDS_BYTES;
     static_assert(lds <= 160 * 1024, "LDS");
     auto k = conv_halo_emu_kernel<BN, KS, NP>;
     static std::atomic<unsigned long long> lds_set{0};

@@ -1096,7 +1096,7 @@ int conv_dispatch(const bts_conv_desc* d, bts_stream_t stream, bool even_ok) {
         // stride-1 3x3 / sub-pixel 2x2 convolutions on maps that tile well, whole 32-channel chunks, pre-split weights:
         // the bf16x3 halo-tile kernel (conv_halo_emu.inc)
         if ((bn == 128 || bn == 64) && halo_emu_eligible(a, nchw)) {
-            const long halo_wgs = (long)a.fill_frames * ((a.H + 3) / 4) * ((a.W + 31) / 32) * ((a.c_out + bn - 1) / bn) * a.n_classes;
+            const long halo_wgs = (long)a.fill_frames * tiles_4x32(a.H, a.W) * ((a.c_out + bn - 1) / bn) * a.n_classes;
             if (geometry_kernel_ok(a, bn, wsf, halo_wgs)) {
                 if (a.subpix) return bn == 128 ? launch_halo_emu<128, 2>(a, s) : launch_halo_emu<64, 2>(a, s);
                 return bn == 128 ? launch_halo_emu<128, 3>(a, s) : launch_halo_emu<64, 3>(a, s);
@@ -1117,7 +1117,7 @@ int conv_dispatch(const bts_conv_desc* d, bts_stream_t stream, bool even_ok) {
         if (bn == 48) bn = 64;                       // no 48-wide bf16 tile: pad DenseNet's growth convs to 64, as precision 1
         // stride-1 3x3 / sub-pixel 2x2 on maps that tile well, pre-rounded weights: the one-plane halo tile (conv_halo_emu.inc)
         if ((bn == 128 || bn == 64) && halo_emu_eligible(a, nchw)) {
-            const long halo_wgs = (long)a.fill_frames * ((a.H + 3) / 4) * ((a.W + 31) / 32) * ((a.c_out + bn - 1) / bn) * a.n_classes;
+            const long halo_wgs = (long)a.fill_frames * tiles_4x32(a.H, a.W) * ((a.c_out + bn - 1) / bn) * a.n_classes;
             if (geometry_kernel_ok(a, bn, wsf, halo_wgs)) {
                 if (a.subpix) return bn == 128 ? launch_halo_emu<128, 2, 1>(a, s) : launch_halo_emu<64, 2, 1>(a, s);
                 return bn == 128 ? launch_halo_emu<128, 3, 1>(a, s) : launch_halo_emu<64, 3, 1>(a, s);

@@ -143,6 +143,9 @@ CASES = [
     _c("emu_halo64_k3_cout48", 2, 7, 30, 64, 48, 3, precision="bf16x3", **GEN),      # no 48-wide twin: padded to 64
     _c("emu_halo128_k2", 1, 4, 31, 32, 128, 3, subpixel=True, precision="bf16x3", **EPI),
     _c("emu_halo64_k2_gen_b3", 3, 7, 30, 32, 40, 3, subpixel=True, precision="bf16x3", **GEN),
+    # three 32-channel chunks: the next chunk's patch trickles into the buffer the consumers are not reading, twice over
+    _c("emu_halo128_k3_chunks3", 2, 7, 30, 96, 128, 3, precision="bf16x3", **EPI, **PRE),
+    _c("emu_halo64_k2_chunks3", 1, 4, 31, 96, 64, 3, subpixel=True, precision="bf16x3", **GEN),
     _c("emu_row64x64_k1", 1, 5, 7, 32, 64, 1, precision="bf16x3", **EPI),
     _c("emu_row128x128_nchw", 1, 33, 63, 32, 1024, 1, precision="bf16x3", nchw=True),
     _c("emu_row128x32_gen", 3, 15, 11, 36, 24, 3, precision="bf16x3", **GEN),
@@ -153,6 +156,8 @@ CASES = [
     _c("bf16_halo64_k3_gen_b3", 3, 7, 30, 64, 48, 3, precision="bf16", y_extra=8, **GEN, **PRE),
     _c("bf16_halo128_k2_gen", 2, 7, 30, 32, 100, 3, subpixel=True, precision="bf16", **GEN),
     _c("bf16_halo64_k2", 1, 4, 31, 32, 64, 3, subpixel=True, precision="bf16", **EPI),
+    _c("bf16_halo64_k3_chunks3", 2, 7, 30, 96, 64, 3, precision="bf16", **GEN, **PRE),
+    _c("bf16_halo128_k2_chunks3", 1, 4, 31, 96, 128, 3, subpixel=True, precision="bf16", **EPI),
     _c("bf16_row128x128", 1, 33, 63, 32, 1000, 1, precision="bf16", **EPI),
     _c("bf16_row64x128_nchw", 1, 5, 7, 32, 100, 1, precision="bf16", nchw=True),
     _c("bf16_row128x64_gen", 1, 51, 65, 32, 300, 1, precision="bf16", **GEN),

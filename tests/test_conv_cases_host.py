@@ -204,6 +204,12 @@ def _coverage_items():
     for fm in (F.ROW, F.HALO, F.HALO_TAIL, F.WINO, F.WIDE_1X1, F.STEM, F.HALO_EMU):
         items.append(("%s with y2" % fm.name, both(fam(fm), lambda f: f["case"].y2)))
         items.append(("%s into a slice of a wider buffer" % fm.name, both(fam(fm), lambda f: f["case"].y_extra > 0)))
+    # halo-emu / halo-bf16 with at least three chunks, for each of KS 3 and KS 2: only from the third chunk on does the
+    # patch trickle into a buffer that an earlier chunk has already used
+    for fm in (F.HALO_EMU, F.HALO_BF16):
+        for what, ks in (("k3", k3), ("k2 (sub-pixel)", sub)):
+            items.append(("%s %s with at least three 32-channel chunks" % (fm.name, what),
+                          both(fam(fm), lambda f, ks=ks: ks(f) and f["case"].c_in >= 96)))
     # precision 1 and 2 off their own kernels
     items.append(("the stem under bf16x3 on the row tiles", lambda f: f["case"].precision == "bf16x3" and f["case"].ksize == 7 and f["plan"].family == F.ROW))
     items.append(("the stem under bf16 still on the stem kernel", lambda f: f["case"].precision == "bf16" and f["plan"].family == F.STEM))
