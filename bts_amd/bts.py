@@ -716,6 +716,13 @@ class BtsModel(nn.Module):
         self.use_plans = False              # True: record each (shape, slot) forward once, replay it with ONE library
                                             # call per forward afterwards (bts_amd/plan.py, bts_plan_run): the eager
                                             # B=1 loop of bts_test.py:127-147 without ~120 ctypes crossings per frame
+        self.grouped_conv = "bundles"       # ResNeXt's grouped 3x3 (eval forward, fp32 only): "bundles" = dense >= 32-channel
+                                            # bundles on bts_conv_fwd_f32; "auto" = the native grouped kernel
+                                            # (ops.conv_grouped_forward) where ops.conv_grouped_plan finds the layer eligible;
+                                            # "native" = on every layer it supports (stride 1, <= 16 channels per group,
+                                            # width % 64 == 0).  Stride-2 blocks, 32 / 64-channel groups, conv_precision
+                                            # "bf16" / "bf16x3" and the training graph stay on bundles in every mode.  A plan
+                                            # cannot replay the native launch: with use_plans the forward raises BtsHipError
         self._plans = PlanCache()
         self._fp_state = [0, None, -1]      # workspace.tensor_fingerprint: [structure token, cached tensor list, its token]
         self._origin = [self]               # reaches DataParallel replicas through replicate()'s shallow __dict__ copy
@@ -783,6 +790,8 @@ class BtsModel(nn.Module):
             plan._src = src_base
             self._enc_plans[str(x.device)] = plan
         plan.bind(base, key_module=src_base)
+        if cls is ResNetHip:
+            plan.grouped_conv = self.grouped_conv
         plan._ws.max_entries = max(plan._ws.max_entries, 2 * int(self.sub_batches))
         B, _, H, W = x.shape
         dec = self.decoder

@@ -70,6 +70,12 @@ def tail_bf16_kernel_name(bn: int) -> str:
     return "conv_tail_bf16_kernel<%d>" % bn
 
 
+def grouped_kernel_name(cg: int) -> str:
+    """The kernel bts_conv_grouped_fwd_f32 launches for ``cg`` channels per group (its own entry point: no bts_conv_plan_f32
+    kind), as KernelTrace records it."""
+    return "conv_grouped_kernel<%d>" % cg
+
+
 def round_up(v: int, m: int) -> int:
     return (v + m - 1) // m * m
 

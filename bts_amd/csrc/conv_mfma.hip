@@ -824,6 +824,7 @@ thread_local ConvChoice* g_dry = nullptr;
 #include "conv_wino.inc"
 #include "conv_up9.inc"
 #include "conv_wino_tail.inc"
+#include "conv_grouped.inc"
 #include "conv_tail_bf16.inc"
 #include "conv_1x1.inc"
 #include "conv_stem.inc"
@@ -1314,6 +1315,47 @@ extern "C" int bts_conv_tail_wino_fwd_f32(const float* x, long x_pix_stride, int
     if (nwg > 0x7fffffffL) return BTS_ERR_UNSUPPORTED;
     a.ntiles = (int)nwg;
     hipLaunchKernelGGL(conv_wino_tail_kernel<32>, dim3((unsigned)nwg), dim3(256), 0, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
+}
+
+// ---- ResNeXt's grouped 3x3 on the multi-block fp32 MFMA (conv_grouped.inc): its own opt-in entry point and plan query, so
+//      that bts_conv_fwd_f32 / bts_conv_plan_f32 answer for every descriptor (bundles included) exactly as before
+extern "C" int bts_conv_grouped_plan(int h, int w, int c, int groups, int precision, int fill_frames, int* bm, int* bn,
+                                     long* workgroups) {
+    int ff, prec;
+    if (!bm || !bn || !workgroups || !resolve_declaration(fill_frames, precision, &ff, &prec)) return BTS_ERR_INVALID;
+    long wgs = 0;
+    const bool ok = grouped_eligible(h, w, c, groups, prec, ff, &wgs);
+    *bm = ok ? GR_TH * GR_TW : 0; *bn = ok ? 64 : 0; *workgroups = ok ? wgs : 0;
+    return 0;
+}
+
+extern "C" int bts_conv_grouped_fwd_f32(const float* x, long x_pix_stride, int B, int h, int w, int c, int groups,
+                                        const float* w_packed, const float* e1_scale, const float* e1_shift, int act, float* y,
+                                        long y_pix_stride, bts_stream_t stream) {
+    if (!x || !w_packed || !y || B <= 0 || h <= 0 || w <= 0 || c <= 0 || groups <= 0 || (c % groups)) return BTS_ERR_INVALID;
+    if (!act_e2_ok(act, e1_scale, e1_shift)) return BTS_ERR_INVALID;
+    if (!grouped_supported(c, groups)) return BTS_ERR_UNSUPPORTED;
+    if (!nhwc_view_ok(x, x_pix_stride, c) || !nhwc_view_ok(y, y_pix_stride, c) || ((uintptr_t)w_packed & 15) ||
+        ((uintptr_t)e1_scale & 15) || ((uintptr_t)e1_shift & 15)) return BTS_ERR_INVALID;
+    // the kernel counts pixels and tiles in 32 bits (addresses are 64-bit)
+    if ((double)B * h * w >= 2147483648.0) return BTS_ERR_UNSUPPORTED;
+    GroupedArgs a;
+    a.x = x; a.x_pix_stride = x_pix_stride; a.B = B; a.H = h; a.W = w; a.w = w_packed;
+    a.e1_scale = e1_scale; a.e1_shift = e1_shift; a.act = act; a.y = y; a.y_pix_stride = y_pix_stride;
+    double fill;
+    grouped_grid(h, w, &a.n_ty, &a.n_tx, &fill);
+    const long tiles = (long)B * a.n_ty * a.n_tx;
+    const int slabs = c / 64;
+    if (tiles > 0x7fffffffL || slabs > 65535) return BTS_ERR_UNSUPPORTED;
+    a.tiles = (int)tiles;
+    // persistent workgroups: what the chip holds at two per CU, shared among the slabs
+    const long chunks = tiles < (GR_RESIDENT + slabs - 1) / slabs ? tiles : (GR_RESIDENT + slabs - 1) / slabs;
+    const dim3 grid((unsigned)chunks, (unsigned)slabs);
+    const int cg = c / groups;
+    if (cg == 16) hipLaunchKernelGGL(conv_grouped_kernel<16>, grid, dim3(256), 0, (hipStream_t)stream, a);
+    else if (cg == 8) hipLaunchKernelGGL(conv_grouped_kernel<8>, grid, dim3(256), 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(conv_grouped_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, a);
     return (int)hipGetLastError();
 }
 

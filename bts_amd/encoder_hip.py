@@ -190,10 +190,19 @@ class ResNetHip:
     runs as ONE launch over channel bundles (``bts_conv_desc.n_bundles``): consecutive groups packed block-diagonally
     into >= 32-channel bundles, so the MFMA tiles stay full at the price of (32 / channels-per-group)x redundant
     FLOPs on the two shallow stages only.  The taps the decoder needs (relu, layer1..3; reference bts.py:318-338) are
-    written straight into its concat buffers; layer4's output is the decoder's dense input."""
+    written straight into its concat buffers; layer4's output is the decoder's dense input.
+
+    ``grouped_conv`` (BtsModel.grouped_conv sets it): "bundles" (default) as above; "auto" = the native grouped kernel
+    (ops.conv_grouped_forward, 16-channel MFMA blocks) on the layers ops.conv_grouped_plan finds eligible; "native" = on
+    every layer its entry point supports (stride 1, at most 16 channels per group, width % 64 == 0, fp32 launch config).
+    Stride-2 blocks, groups of 32 / 64 channels (nothing redundant to remove) and the bf16 / bf16x3 precisions stay on
+    bundles in every mode; the training graph (bts_amd/train.py) never reads the attribute."""
+
+    GROUPED_MODES = ("bundles", "auto", "native")
 
     def __init__(self, model: nn.Module, key_module: Optional[nn.Module] = None):
         self.model = model
+        self.grouped_conv = "bundles"
         self.key_module = key_module if key_module is not None else model
         self._pack = None
         self._pack_key = None
@@ -235,7 +244,8 @@ class ResNetHip:
                 width = blk.conv2.out_channels
                 b = dict(w1=w1, e1=_bn_vecs(blk.bn1, co1), w2=w2, nb=nb, cb=cb, cg=blk.conv2.in_channels // g,
                          e2=_bn_vecs(blk.bn2, ops.round_up(width, 32)), w3=w3, e3=_bn_vecs(blk.bn3, co3),
-                         stride=blk.conv2.stride[0], width=width, c_out=blk.conv3.out_channels, down=None)
+                         stride=blk.conv2.stride[0], width=width, c_out=blk.conv3.out_channels, down=None,
+                         groups=g, conv2=blk.conv2, w2n=None)        # w2n: ops.pack_grouped_native, made on first use
                 if blk.downsample is not None:
                     wd, cod, _ = ops.pack_conv_weight(blk.downsample[0].weight.detach())
                     b["down"] = dict(w=wd, e1=_bn_vecs(blk.downsample[1], cod), stride=blk.downsample[0].stride[0])
@@ -243,6 +253,26 @@ class ResNetHip:
             P["layers"].append(blocks)
         self._pack, self._pack_key = P, key
         return P
+
+    def _pack_grouped_native(self, P, device):
+        """The native-form weights (ops.pack_grouped_native) of every block the entry point supports, into the pack ``P``:
+        made on the first forward that needs one, all at once, and finished before this returns -- the sub-batches of a
+        BtsModel forward run on several streams, and the others must not read a weight the first is still writing.
+        (A host synchronise: like every first forward, not something to capture into a hipGraph.)"""
+        for blocks in P["layers"]:
+            for b in blocks:
+                if b["nb"] > 1 and b["w2n"] is None and b["stride"] == 1 and b["cg"] <= 16 and b["width"] % 64 == 0:
+                    b["w2n"] = ops.pack_grouped_native(b["conv2"].weight.detach(), b["groups"])
+        torch.cuda.current_stream(device).synchronize()
+
+    def _grouped_native(self, b, h, w) -> bool:
+        """Does this block's grouped 3x3 (input map h x w) take the native kernel under ``self.grouped_conv``?"""
+        mode = self.grouped_conv
+        if mode not in self.GROUPED_MODES:
+            raise ops.BtsHipError("ResNetHip.grouped_conv must be one of %s, got %r" % (self.GROUPED_MODES, mode))
+        if mode == "bundles" or b["stride"] != 1 or b["cg"] > 16 or b["width"] % 64 or ops.current_launch_config()[1] != 0:
+            return False
+        return mode == "native" or ops.conv_grouped_plan(h, w, b["width"], b["groups"]).eligible
 
     def _workspace(self, B, H, W, device, slot=0):
         return self._ws.get((B, H, W, str(device), slot), lambda: self._alloc_workspace(B, H, W, device))
@@ -298,7 +328,12 @@ class ResNetHip:
                 t2 = ws["t2_%d" % li][: B * ho * wo]
                 ops.conv_forward(cur, B, h, w, b["w1"], b["width"], 1, e1=b["e1"], act=RELU, y2d=t1, tag=tag + "_1x1",
                                  splitk_ws=sk)
-                if b["nb"] > 1:
+                if b["nb"] > 1 and self._grouped_native(b, h, w):
+                    if b["w2n"] is None:
+                        self._pack_grouped_native(P, dev)
+                    ops.conv_grouped_forward(t1, B, h, w, b["w2n"], b["width"], b["groups"], e1=b["e2"], act=RELU, y2d=t2,
+                                             tag=tag + "_g3x3")
+                elif b["nb"] > 1:
                     ops.conv_forward(t1, B, h, w, b["w2"], b["cb"], 3, stride=s, pad=1, c_in_ld=b["cb"], e1=b["e2"], act=RELU,
                                      y2d=t2, n_bundles=b["nb"], tag=tag + "_g3x3", c_in_real=b["cg"])
                 else:

@@ -137,15 +137,15 @@ def _check_act3(act: int, who: str):
         raise BtsHipError("%s: act must be none, ReLU or ELU" % who)
 
 
-def _e2_vectors(e2, n: int, who: str):
-    """The (scale, shift) pair of an e2 affine over ``n`` channels, checked; (None, None) when absent."""
+def _e2_vectors(e2, n: int, who: str, what: str = "e2"):
+    """The (scale, shift) pair of an e2 (or ``what``) affine over ``n`` channels, checked; (None, None) when absent."""
     if e2 is None:
         return None, None
     es, eb = e2
     _need(es, who)
     _need(eb, who)
     if es.numel() < n or eb.numel() < n:
-        raise BtsHipError("%s: e2 vectors need %d elements" % (who, n))
+        raise BtsHipError("%s: %s vectors need %d elements" % (who, what, n))
     return es, eb
 
 
@@ -1311,6 +1311,91 @@ def conv_tail_wino_forward(x2d: torch.Tensor, B: int, h: int, w: int, u: torch.T
              (_ptr(x2d), xs, B, h, w, 32, _ptr(u), _ptr(w_tail), ptrs[0], ptrs[1], ptrs[2], ptrs[3], len(planes), 32, int(act), _ptr(y_nchw)),
              trace=(kern, tag, flops, nbytes, xflops))
     return y_nchw
+
+
+# ---- ResNeXt's grouped 3x3 on the multi-block fp32 MFMA (csrc/conv_grouped.inc), opt-in beside the bundle path
+def _grouped_native_shape(w: torch.Tensor, groups: int) -> Tuple[int, int]:
+    if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or groups <= 0 or w.shape[0] != w.shape[1] * groups:
+        raise BtsHipError("pack_grouped_native: needs a [c, c / groups, 3, 3] weight (cin == cout == c)")
+    c, cg = int(w.shape[0]), int(w.shape[1])
+    if c % 64 or cg not in (4, 8, 16):
+        raise BtsHipError("pack_grouped_native: c = %d in groups of %d; needs c %% 64 == 0 and 4, 8 or 16 channels per group" % (c, cg))
+    return c, cg
+
+
+def pack_grouped_native(w: torch.Tensor, groups: int) -> torch.Tensor:
+    """Grouped [c, c/groups, 3, 3] weight -> the 144 * c floats bts_conv_grouped_fwd_f32 reads (include/bts_hip.h): index
+    ((s*9 + tap)*16 + k)*64 + lane = the weight from input channel 64 s + 16 (lane >> 4) + k to output channel 64 s + lane,
+    bit for bit, exact zeros where the two lie in different groups.  Once per weight (ResNetHip.packed caches it)."""
+    c, cg = _grouped_native_shape(w, groups)
+    wv = w.detach().float().reshape(c // 64, 4, 16, cg, 9)                  # [slab, block, row, k in group, tap]
+    k = torch.arange(16, device=w.device)
+    full = wv[:, :, :, k % cg, :]                                           # [slab, block, row, k in block, tap]
+    same = (k[:, None] // cg) == (k[None, :] // cg)                         # [row, k]: one group
+    full = torch.where(same[None, None, :, :, None], full, torch.zeros((), dtype=torch.float32, device=w.device))
+    return full.permute(0, 4, 3, 1, 2).contiguous().view(-1)                # (slab, tap, k, block, row): lane = 16 block + row
+
+
+def pack_grouped_native_reference(w: torch.Tensor, groups: int) -> torch.Tensor:
+    """Index-by-index statement of pack_grouped_native, kept as its test oracle: every flat index decoded as the header
+    writes it."""
+    c, cg = _grouped_native_shape(w, groups)
+    wc = w.detach().float().cpu()
+    idx = torch.arange(144 * c)
+    lane, k, tap, s = idx % 64, (idx // 64) % 16, (idx // 1024) % 9, idx // 9216
+    n, ci = 64 * s + lane, 64 * s + 16 * (lane // 16) + k                   # output channel, input channel
+    val = wc[n, ci % cg, tap // 3, tap % 3]
+    return torch.where(ci // cg == n // cg, val, torch.zeros(())).to(w.device)
+
+
+GroupedPlan = TilePlan        # of bts_conv_grouped_plan; all 0 = the layer stays on channel bundles
+
+
+def conv_grouped_plan(h: int, w: int, c: int, groups: int, precision=None, fill_frames: Optional[int] = None) -> GroupedPlan:
+    """Should this grouped 3x3 layer take conv_grouped_forward?  Host-only query (bts_conv_grouped_plan); ``precision`` /
+    ``fill_frames`` default to the launch_config in force."""
+    ff, pr = _resolve_launch(precision, fill_frames, "conv_grouped_plan")
+    bm, bn, wgs = C.c_int(0), C.c_int(0), C.c_long(0)
+    _lib.check(_lib.load_real().bts_conv_grouped_plan(int(h), int(w), int(c), int(groups), int(pr), int(ff), C.byref(bm), C.byref(bn),
+                                                       C.byref(wgs)), "bts_conv_grouped_plan")
+    return GroupedPlan((bm.value, bn.value, wgs.value))
+
+
+def conv_grouped_forward(x2d: torch.Tensor, B: int, h: int, w: int, w_packed: torch.Tensor, c: int, groups: int,
+                         e1: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, act: int = ACT_NONE,
+                         y2d: Optional[torch.Tensor] = None, tag: str = "grouped_conv"):
+    """act(e1(grouped conv3x3(x))) in one launch of the multi-block MFMA kernel (bts_conv_grouped_fwd_f32): stride 1,
+    padding 1, x2d [B*h*w, >= c] NHWC view (c channels read), w_packed from pack_grouped_native, e1 a (scale, shift) pair of
+    >= c floats, y2d [B*h*w, c] NHWC view (a channel slice is fine; allocated when None).  Runs whatever the plan query
+    says: callers ask conv_grouped_plan first."""
+    name = "conv_grouped_forward"
+    xs, xc = _rows2d(x2d, name)
+    if y2d is None:
+        y2d = torch.empty((B * h * w, c), dtype=torch.float32, device=x2d.device)
+    ys, yc = _rows2d(y2d, name)
+    _need(w_packed, name)
+    if c <= 0 or groups <= 0 or c % groups:
+        raise BtsHipError("conv_grouped_forward: %d channels do not split into %d groups" % (c, groups))
+    cg = c // groups
+    if c % 64 or cg not in (4, 8, 16):
+        raise BtsHipError("conv_grouped_forward: c = %d in groups of %d; needs c %% 64 == 0 and 4, 8 or 16 channels per group" % (c, cg))
+    if xc < c or yc != c or x2d.shape[0] != B * h * w or y2d.shape[0] != B * h * w:
+        raise BtsHipError("conv_grouped_forward: views %s / %s do not fit B=%d %dx%d, %d channels"
+                          % (tuple(x2d.shape), tuple(y2d.shape), B, h, w, c))
+    if w_packed.numel() != 144 * c or not w_packed.is_contiguous():
+        raise BtsHipError("conv_grouped_forward: w_packed must come from pack_grouped_native (144 * c floats)")
+    _check_act3(act, name)
+    es, eb = _e2_vectors(e1, c, name, "e1")
+    kern, flops, nbytes, xflops = "conv", 0.0, 0.0, None
+    if _trace is not None:
+        kern = conv_plan.grouped_kernel_name(cg)
+        flops = 2.0 * B * h * w * c * cg * 9
+        nbytes = 4.0 * (2 * B * h * w * c + 9 * c * cg)
+        xflops = 2.0 * 9 * 16 * (B * ((h + 7) // 8) * ((w + 15) // 16) * 128) * c    # 16-channel blocks, ragged tiles included
+    _enqueue("bts_conv_grouped_fwd_f32", x2d,
+             (_ptr(x2d), xs, B, h, w, c, groups, _ptr(w_packed), _ptr(es), _ptr(eb), int(act), _ptr(y2d), ys),
+             trace=(kern, tag, flops, nbytes, xflops))
+    return y2d
 
 
 def pad_vec(v: Optional[torch.Tensor], n: int, fill: float = 0.0) -> Optional[torch.Tensor]:

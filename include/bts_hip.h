@@ -343,6 +343,33 @@ int bts_conv_tail_wino_fwd_f32(const float* x, long x_pix_stride, int B, int h, 
 int bts_conv_tail_wino_plan(int h, int w, int c_main, int c_out, int n_tail, int precision, int fill_frames, int* bm, int* bn,
                             long* workgroups);
 
+/* ResNeXt's grouped 3x3 convolution (stride 1, padding 1, dilation 1, c channels in and out in `groups` groups of
+ * cg = c / groups channels; forward, fp32) in one launch of the multi-block fp32 MFMA kernel (csrc/conv_grouped.inc,
+ * v_mfma_f32_16x16x1_4b_f32: one 16-channel block per MFMA block):
+ *   y[p][n] = act( e1( sum_{tap, k < cg} x[q(p, tap)][cg * (n / cg) + k] * w[n][k][tap] ) ),   tap = 3 (dy+1) + (dx+1)
+ * zero padding; e1 = per-channel scale / shift (both or neither); act 0 none / 1 ReLU / 2 ELU.  Opt-in: bts_conv_fwd_f32
+ * never takes this path on its own (it runs grouped layers as bts_conv_desc.n_bundles channel bundles).
+ *   x, y     : NHWC [B,h,w], pixel strides >= c floats (multiples of 4), 16-byte aligned; y may be a channel slice
+ *   w_packed : 144 * c floats, 16-byte aligned (bts_amd/ops.py:pack_grouped_native): float index
+ *              ((s * 9 + tap) * 16 + k) * 64 + lane = the weight from input channel 64 s + 16 (lane >> 4) + k to output
+ *              channel n = 64 s + lane: w[n][(16 (lane >> 4) + k) mod cg][tap] when that input channel lies in n's group,
+ *              else 0 (cg < 16: the 16-channel block is block-diagonal)
+ *   e1_scale, e1_shift : c floats each, 16-byte aligned, or both NULL
+ * c % 64 != 0 or cg not in {4, 8, 16}: BTS_ERR_UNSUPPORTED.  Any supported shape runs, whatever the plan query says.
+ * Sum order fixed (tap-major, input channel ascending): a frame's bits depend neither on B nor on fill_frames.
+ * Non-finite values: an input value reaches only outputs of its own 16-channel block whose nine taps touch it -- its own
+ * group for cg 16; for cg < 16 also the other groups of that block (0 * inf; the bundle path does the same over 32 channels). */
+int bts_conv_grouped_fwd_f32(const float* x, long x_pix_stride, int B, int h, int w, int c, int groups, const float* w_packed,
+                             const float* e1_scale, const float* e1_shift, int act, float* y, long y_pix_stride,
+                             bts_stream_t stream);
+
+/* Should a grouped layer take bts_conv_grouped_fwd_f32 (host-side query, no GPU work, no pointers)?  Eligible: precision 0,
+ * c % 64 == 0, cg in {4, 8, 16}, a grid of 8x16-pixel tiles that is at least 0.55 real pixels, and a declared launch
+ * (fill_frames as in bts_conv_desc, 0 = the library default; never B) of at least 1024 (tile, 64-channel slab) pairs.
+ *   *bm = pixels per workgroup tile (128), *bn = output channels per workgroup (64), *workgroups = (tile, slab) pairs PER
+ *   FRAME; all three 0 when the layer should stay on bundles. */
+int bts_conv_grouped_plan(int h, int w, int c, int groups, int precision, int fill_frames, int* bm, int* bn, long* workgroups);
+
 /* Which kernel bts_conv_fwd_f32 will launch for this descriptor (host-side query, no GPU work: it walks the real
  * dispatch path): lets a profiler attribute a launch to its kernel instantiation.
  *   *kind = one kernel family (kind & BTS_CONV_KIND_MASK) plus any of the BTS_CONV_FLAG_* bits. */
