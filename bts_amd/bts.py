@@ -670,6 +670,9 @@ class encoder(nn.Module):
         self.feat_names, self.feat_out_channels = list(names), list(channels)
         self.batched_wgrad = False          # train() mode: True defers the weight gradients of a DenseNet block to the end
                                             # of its backward walk and computes them in one batched launch (train._DenseBlockFn)
+        self.grouped_conv_train = False     # train() mode, ResNeXt: True runs every stride-1 grouped 3x3 with <= 16 channels per
+                                            # group (width % 64 == 0) on the native grouped kernels in all three passes
+                                            # (train.conv2d(grouped_native=True)); fp32 only, a shape rule with no fill query
 
     def forward(self, x):
         """[x, tap@1/2, tap@1/4, tap@1/8, tap@1/16, tap@1/32]: run the backbone's children in order and keep the outputs
@@ -721,7 +724,8 @@ class BtsModel(nn.Module):
                                             # (ops.conv_grouped_forward) where ops.conv_grouped_plan finds the layer eligible;
                                             # "native" = on every layer it supports (stride 1, <= 16 channels per group,
                                             # width % 64 == 0).  Stride-2 blocks, 32 / 64-channel groups, conv_precision
-                                            # "bf16" / "bf16x3" and the training graph stay on bundles in every mode.  A plan
+                                            # "bf16" / "bf16x3" stay on bundles in every mode; the training graph has its own
+                                            # switch (grouped_conv_train).  A plan
                                             # cannot replay the native launch: with use_plans the forward raises BtsHipError
         self._plans = PlanCache()
         self._fp_state = [0, None, -1]      # workspace.tensor_fingerprint: [structure token, cached tensor list, its token]
@@ -755,6 +759,16 @@ class BtsModel(nn.Module):
     @bf16_tail_convs.setter
     def bf16_tail_convs(self, on: bool):
         self.decoder.bf16_tail_convs = bool(on)
+
+    @property
+    def grouped_conv_train(self) -> bool:
+        """The encoder's switch of the same name (encoder.grouped_conv_train), default False: ResNeXt's stride-1 grouped 3x3
+        layers on the native grouped kernels in forward, input gradient and weight gradient of the training step."""
+        return self.encoder.grouped_conv_train
+
+    @grouped_conv_train.setter
+    def grouped_conv_train(self, on: bool):
+        self.encoder.grouped_conv_train = bool(on)
 
     @property
     def batched_wgrad(self) -> bool:

@@ -76,6 +76,12 @@ def grouped_kernel_name(cg: int) -> str:
     return "conv_grouped_kernel<%d>" % cg
 
 
+def grouped_wgrad_kernel_name(cg: int) -> str:
+    """The kernel bts_conv_grouped_wgrad_f32 launches for ``cg`` channels per group, as KernelTrace records it (its reduce
+    launch rides in the same record)."""
+    return "conv_grouped_wgrad_kernel<%d>" % cg
+
+
 def round_up(v: int, m: int) -> int:
     return (v + m - 1) // m * m
 

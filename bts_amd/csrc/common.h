@@ -36,6 +36,29 @@ __device__ __forceinline__ int bts_table_find(const T* __restrict__ table, int n
     return lo;
 }
 
+// The fixed-order sum of split partials shared by the weight-gradient reduce kernels (wgrad.hip, conv_grouped_wgrad.inc): 16
+// lanes walk the splits of one float4 element -- lane j adds splits j, j + 16, ... in ascending order, four independent loads
+// in flight added as (a0 + a1) + (a2 + a3), then one at a time -- and lane 0 adds the 16 lane sums in lane order.
+// p = split 0's float4, step = float4s from one split to the next.
+__device__ __forceinline__ f32x4 sum_splits(const f32x4* __restrict__ p, size_t step, int ksplit, int lane) {
+    f32x4 v = (f32x4)(0.f);
+    int s = lane;
+    for (; s + 48 < ksplit; s += 64) {
+        const f32x4 a0 = p[(size_t)s * step], a1 = p[(size_t)(s + 16) * step];
+        const f32x4 a2 = p[(size_t)(s + 32) * step], a3 = p[(size_t)(s + 48) * step];
+        v += (a0 + a1) + (a2 + a3);
+    }
+    for (; s < ksplit; s += 16) v += p[(size_t)s * step];
+    return v;
+}
+
+__device__ __forceinline__ f32x4 sum_lanes(const f32x4 (&red)[16][16], int el) {
+    f32x4 r = red[0][el];
+#pragma unroll
+    for (int j = 1; j < 16; ++j) r += red[j][el];
+    return r;
+}
+
 // Raise a kernel's dynamic-LDS limit above the 64 KB default.  hipFuncAttributeMaxDynamicSharedMemorySize is a property
 // of (function, DEVICE): a process that drives several GPUs (nn.DataParallel: one Python thread per device,
 // bts_test.py:91) must set it on each of them.  `done` is one bit per device ordinal, owned by the kernel

@@ -25,6 +25,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include <type_traits>
+#include <algorithm>
 #include "common.h"
 
 namespace {
@@ -825,6 +826,7 @@ thread_local ConvChoice* g_dry = nullptr;
 #include "conv_up9.inc"
 #include "conv_wino_tail.inc"
 #include "conv_grouped.inc"
+#include "conv_grouped_wgrad.inc"
 #include "conv_tail_bf16.inc"
 #include "conv_1x1.inc"
 #include "conv_stem.inc"
@@ -1356,6 +1358,54 @@ extern "C" int bts_conv_grouped_fwd_f32(const float* x, long x_pix_stride, int B
     if (cg == 16) hipLaunchKernelGGL(conv_grouped_kernel<16>, grid, dim3(256), 0, (hipStream_t)stream, a);
     else if (cg == 8) hipLaunchKernelGGL(conv_grouped_kernel<8>, grid, dim3(256), 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL(conv_grouped_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
+}
+
+// ---- its weight gradient (conv_grouped_wgrad.inc): the shapes of the forward, the same 32-bit index guards
+namespace {
+int grouped_wgrad_check(int B, int h, int w, int c, int groups, long ws_floats) {
+    if (B <= 0 || h <= 0 || w <= 0 || c <= 0 || groups <= 0 || (c % groups) || ws_floats < 0) return BTS_ERR_INVALID;
+    if (!grouped_supported(c, groups)) return BTS_ERR_UNSUPPORTED;
+    if ((double)B * h * w >= 2147483648.0 || c / 64 > 65535) return BTS_ERR_UNSUPPORTED;
+    return 0;
+}
+}  // namespace
+
+extern "C" int bts_conv_grouped_wgrad_plan(int B, int h, int w, int c, int groups, long ws_floats, int* splits,
+                                           long* ws_floats_used) {
+    if (!splits || !ws_floats_used) return BTS_ERR_INVALID;
+    if (const int rc = grouped_wgrad_check(B, h, w, c, groups, ws_floats); rc != 0) return rc;
+    const GroupedWgradPlan p = grouped_wgrad_plan(B, h, w, c, ws_floats, true);
+    *splits = (int)p.splits; *ws_floats_used = p.ws_used;
+    return 0;
+}
+
+extern "C" int bts_conv_grouped_wgrad_f32(const float* x, long x_pix_stride, const float* dy, long dy_pix_stride, int B, int h,
+                                          int w, int c, int groups, float* dw, float* ws, long ws_floats, bts_stream_t stream) {
+    if (const int rc = grouped_wgrad_check(B, h, w, c, groups, ws ? ws_floats : 0); rc != 0) return rc;
+    if (!nhwc_view_ok(x, x_pix_stride, c) || !nhwc_view_ok(dy, dy_pix_stride, c) || !dw || ((uintptr_t)dw & 15) ||
+        ((uintptr_t)ws & 15)) return BTS_ERR_INVALID;
+    const GroupedWgradPlan p = grouped_wgrad_plan(B, h, w, c, ws_floats, ws != nullptr);
+    GroupedWgradArgs a;
+    a.x = x; a.x_pix_stride = x_pix_stride; a.dy = dy; a.dy_pix_stride = dy_pix_stride; a.B = B; a.H = h; a.W = w;
+    double fill;
+    grouped_grid(h, w, &a.n_ty, &a.n_tx, &fill);
+    a.tiles = (int)p.tiles; a.tiles_per_split = (int)p.tiles_per_split;     // < 2^31: B h w is
+    a.direct = p.splits == 1; a.out = a.direct ? dw : ws;
+    const int cg = c / groups;
+    const dim3 grid((unsigned)p.splits, (unsigned)(c / 64));
+    const long red_blocks = ((long)c * 9 * (cg / 4) + 15) / 16;
+    hipStream_t s = (hipStream_t)stream;
+    auto run = [&](auto tag) {
+        constexpr int CG = decltype(tag)::value;
+        hipLaunchKernelGGL(conv_grouped_wgrad_kernel<CG>, grid, dim3(256), 0, s, a);
+        if (!a.direct)
+            hipLaunchKernelGGL(conv_grouped_wgrad_reduce_kernel<CG>, dim3((unsigned)red_blocks), dim3(256), 0, s, (const float*)ws, dw,
+                               c, (int)p.splits);
+    };
+    if (cg == 16) run(std::integral_constant<int, 16>{});
+    else if (cg == 8) run(std::integral_constant<int, 8>{});
+    else run(std::integral_constant<int, 4>{});
     return (int)hipGetLastError();
 }
 

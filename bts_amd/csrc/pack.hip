@@ -22,7 +22,10 @@ struct PackEntry {          // 14 x int64, filled by the host (bts_amd/train.py)
     long cg, gmode;         // grouped weight [C][cg][k][k] packed block-diagonally into a bundle (src points at the
                             // bundle's first output channel): cg = channels per group; gmode 1 = forward (row = output
                             // channel, inner = bundle-local input channel), 2 = input gradient (row = bundle-local input
-                            // channel, inner = output channel); entries outside a row's own group are zero.  0 = dense
+                            // channel, inner = output channel); entries outside a row's own group are zero.  0 = dense.
+                            // gmode 3 / 4: the whole [c][cg][3][3] weight (src) in the 144 c-float layout of
+                            // bts_conv_grouped_fwd_f32 (rows_pad * k_pad = 144 c; only cg and the two pointers are read):
+                            // 3 = the forward weight, 4 = the flipped, group-transposed weight of the input gradient
 };
 static_assert(sizeof(PackEntry) == 14 * 8, "train.py builds these rows as 14 int64 columns");
 
@@ -39,7 +42,16 @@ __global__ __launch_bounds__(256) void pack_weights_kernel(const PackEntry* __re
         if (i0 >= total) continue;
         const long row = i0 / e.k_pad, col0 = i0 - row * e.k_pad;
         f32x4 v = (f32x4)(0.f);
-        if (row < e.rows) {
+        if (e.gmode >= 3) {                                              // native grouped layout: four lanes of one (s, tap, k)
+            const long lane0 = i0 & 63, kb = (i0 >> 6) & 15, tap = (i0 >> 10) % 9, s = i0 / 9216;
+            const long ci = 64 * s + 16 * (lane0 >> 4) + kb;            // input channel of the product; lanes = output channels
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const long n = 64 * s + lane0 + j;
+                if (n / e.cg == ci / e.cg)
+                    v[j] = e.gmode == 3 ? e.src[(n * e.cg + ci % e.cg) * 9 + tap] : e.src[(ci * e.cg + n % e.cg) * 9 + 8 - tap];
+            }
+        } else if (row < e.rows) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const long col = col0 + j;

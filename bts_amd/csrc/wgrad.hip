@@ -266,25 +266,8 @@ __global__ __launch_bounds__(256, 2) void upconv_wgrad_kernel(const WgradArgs a)
 // The output is small and the split count can be in the hundreds, so the walk over splits is itself spread over 16 lanes
 // per element (a serial walk is pure load latency): a block owns 16 consecutive float4 elements, lane j adds splits j,
 // j+16, ... (sum_splits: four independent loads in flight, added as (a0+a1)+(a2+a3), then one at a time), then lane 0
-// adds the 16 lane sums in lane order (sum_lanes).  p = split 0's float4, step = float4s from one split to the next.
-__device__ __forceinline__ f32x4 sum_splits(const f32x4* __restrict__ p, size_t step, int ksplit, int lane) {
-    f32x4 v = (f32x4)(0.f);
-    int s = lane;
-    for (; s + 48 < ksplit; s += 64) {
-        const f32x4 a0 = p[(size_t)s * step], a1 = p[(size_t)(s + 16) * step];
-        const f32x4 a2 = p[(size_t)(s + 32) * step], a3 = p[(size_t)(s + 48) * step];
-        v += (a0 + a1) + (a2 + a3);
-    }
-    for (; s < ksplit; s += 16) v += p[(size_t)s * step];
-    return v;
-}
-
-__device__ __forceinline__ f32x4 sum_lanes(const f32x4 (&red)[16][16], int el) {
-    f32x4 r = red[0][el];
-#pragma unroll
-    for (int j = 1; j < 16; ++j) r += red[j][el];
-    return r;
-}
+// adds the 16 lane sums in lane order (sum_lanes).  Both live in common.h: the grouped weight gradient (conv_grouped_wgrad.inc)
+// sums its partials with them too.
 
 // dw[0 .. count4) = the split sum of ws [ksplit][count4] float4s; element t = 16 * block + el, lane = split residue.
 __device__ __forceinline__ void reduce_block(const float* __restrict__ ws, float* __restrict__ dw, long count4, int ksplit,

@@ -1398,6 +1398,82 @@ def conv_grouped_forward(x2d: torch.Tensor, B: int, h: int, w: int, w_packed: to
     return y2d
 
 
+def _grouped_cg(c: int, groups: int, who: str) -> int:
+    if c <= 0 or groups <= 0 or c % groups:
+        raise BtsHipError("%s: %d channels do not split into %d groups" % (who, c, groups))
+    cg = c // groups
+    if c % 64 or cg not in (4, 8, 16):
+        raise BtsHipError("%s: c = %d in groups of %d; needs c %% 64 == 0 and 4, 8 or 16 channels per group" % (who, c, cg))
+    return cg
+
+
+def grouped_native_supported(c: int, groups: int) -> bool:
+    """The shapes bts_conv_grouped_fwd_f32 / bts_conv_grouped_wgrad_f32 run (csrc/conv_grouped.inc: grouped_supported)."""
+    return c > 0 and groups > 0 and c % groups == 0 and c % 64 == 0 and c // groups in (4, 8, 16)
+
+
+def grouped_dgrad_weight(w: torch.Tensor, groups: int) -> torch.Tensor:
+    """w_t[cg g + i][o][8 - tap] = w[cg g + o][i][tap]: the grouped weight whose forward convolution is the input gradient of
+    ``w``'s (taps flipped, each group's matrix transposed)."""
+    c, cg = int(w.shape[0]), int(w.shape[1])
+    wg = w.detach().reshape(groups, cg, cg, 9)                              # [g, o, i, tap]
+    return wg.permute(0, 2, 1, 3).flip(3).reshape(c, cg, 3, 3).contiguous()
+
+
+def pack_grouped_train_reference(w: torch.Tensor, groups: int, dgrad: bool) -> torch.Tensor:
+    """Index-by-index statement of the two per-step packs train.WeightPacker keeps of a natively run grouped weight
+    (bts_pack_weights_f32 gmode 3 / 4, include/bts_hip.h), kept as their test oracle: float ((s*9 + tap)*16 + k)*64 + lane
+    pairs output channel n = 64 s + lane with input channel ci = 64 s + 16 (lane >> 4) + k; forward w[n][ci mod cg][tap],
+    input gradient w[ci][n mod cg][8 - tap], exact zeros across groups."""
+    c, cg = _grouped_native_shape(w, groups)
+    wc = w.detach().float().cpu().reshape(c, cg, 9)
+    idx = torch.arange(144 * c)
+    lane, k, tap, s = idx % 64, (idx // 64) % 16, (idx // 1024) % 9, idx // 9216
+    n, ci = 64 * s + lane, 64 * s + 16 * (lane // 16) + k
+    val = wc[ci, n % cg, 8 - tap] if dgrad else wc[n, ci % cg, tap]
+    return torch.where(ci // cg == n // cg, val, torch.zeros(())).to(w.device)
+
+
+def conv_grouped_wgrad_plan(B: int, h: int, w: int, c: int, groups: int, ws_floats: int = 0) -> Tuple[int, int]:
+    """(splits, workspace floats written) of conv_grouped_wgrad with a workspace of ``ws_floats`` floats (0 = none): the
+    library's own rule (bts_conv_grouped_wgrad_plan), host arithmetic only."""
+    splits, used = C.c_int(0), C.c_long(0)
+    _lib.check(_lib.load_real().bts_conv_grouped_wgrad_plan(int(B), int(h), int(w), int(c), int(groups), int(ws_floats),
+                                                             C.byref(splits), C.byref(used)), "bts_conv_grouped_wgrad_plan")
+    return splits.value, used.value
+
+
+def conv_grouped_wgrad(x2d: torch.Tensor, B: int, h: int, w: int, dy2d: torch.Tensor, c: int, groups: int,
+                       ws: Optional[torch.Tensor] = None, dw: Optional[torch.Tensor] = None, tag: str = "grouped_wgrad"):
+    """Weight gradient of the grouped 3x3 convolution (stride 1, padding 1) on the multi-block MFMA kernel
+    (bts_conv_grouped_wgrad_f32): x2d / dy2d [B*h*w, >= c] NHWC views (c channels read), returns dw in the parameter's own
+    OIHW layout [c, c/groups, 3, 3] (``dw``: a contiguous tensor of that many floats to write instead).  ``ws``: scratch for
+    the split partials; None runs unsplit."""
+    name = "conv_grouped_wgrad"
+    cg = _grouped_cg(c, groups, name)
+    xs, ds = _rows2d_c(x2d, c, B * h * w, name), _rows2d_c(dy2d, c, B * h * w, name)
+    if dw is None:
+        dw = torch.empty((c, cg, 3, 3), dtype=torch.float32, device=x2d.device)
+    _need(dw, name)
+    if dw.numel() != c * cg * 9 or not dw.is_contiguous() or dw.data_ptr() % 16:
+        raise BtsHipError("conv_grouped_wgrad: dw must be %d contiguous floats, 16-byte aligned" % (c * cg * 9))
+    nws = 0
+    if ws is not None:
+        _need(ws, name)
+        if not ws.is_contiguous() or ws.data_ptr() % 16:
+            raise BtsHipError("conv_grouped_wgrad: ws must be contiguous and 16-byte aligned")
+        nws = ws.numel()
+    kern, flops, nbytes, xflops = "wgrad", 0.0, 0.0, None
+    if _trace is not None:
+        kern = conv_plan.grouped_wgrad_kernel_name(cg)
+        flops = 2.0 * B * h * w * c * cg * 9
+        nbytes = 4.0 * (2 * B * h * w * c + 9 * c * cg)
+        xflops = 2.0 * 9 * 16 * B * h * w * c                                # 16-channel blocks; pixels outside the map are skipped
+    _enqueue("bts_conv_grouped_wgrad_f32", x2d, (_ptr(x2d), xs, _ptr(dy2d), ds, B, h, w, c, groups, _ptr(dw), _ptr(ws), nws),
+             trace=(kern, tag, flops, nbytes, xflops))
+    return dw
+
+
 def pad_vec(v: Optional[torch.Tensor], n: int, fill: float = 0.0) -> Optional[torch.Tensor]:
     if v is None:
         return None

@@ -72,6 +72,7 @@ class WeightPacker:
     of the entry set (the native optimiser rebuilds its table when it moves)."""
 
     FWD, DGRAD = 0, 1
+    FWD_NATIVE, DGRAD_NATIVE = 2, 3    # grouped weights in the 144 c-float layout of bts_conv_grouped_fwd_f32 (pack.hip gmode 3 / 4)
 
     def __init__(self):
         self.entries = {}          # (data_ptr, shape, c_in_ld, mode, groups) -> dict(wref, dst, version, rows)
@@ -97,6 +98,11 @@ class WeightPacker:
         s_row, s_c, flip, cg, gmode)."""
         cout, cin_g, k, _ = weight.shape
         kk = k * k
+        if mode in (WeightPacker.FWD_NATIVE, WeightPacker.DGRAD_NATIVE):
+            if k != 3 or not ops.grouped_native_supported(cout, groups) or cin_g * groups != cout:
+                raise BtsHipError("train.conv2d: grouped convolution %s with %d groups has no native pack" % (tuple(weight.shape), groups))
+            gmode = 3 if mode == WeightPacker.FWD_NATIVE else 4
+            return [(0, 0, 144, 0, 3, 0, 144, cout, 0, 0, 0, cin_g, gmode)], (144 * cout,)
         if groups == 1:
             if mode == WeightPacker.FWD:
                 rows, inner, s_row, s_c, flip = cout, cin_g, cin_g * kk, kk, 0
@@ -139,7 +145,8 @@ class WeightPacker:
 
     def get(self, weight, c_in_ld, mode, groups=1):
         """Packed buffer for ``weight`` (an nn.Parameter or any contiguous OIHW CUDA tensor), current with its values:
-        [rows_pad, k_pad] for a dense convolution, [n_bundles, cb, k_pad] for a grouped one."""
+        [rows_pad, k_pad] for a dense convolution, [n_bundles, cb, k_pad] for a grouped one, 144 * c floats for the native
+        grouped modes (``c_in_ld`` is then only part of the key)."""
         key = (weight.data_ptr(), tuple(weight.shape), c_in_ld, mode, groups)
         e = self.entries.get(key)
         if e is not None and e["wref"]() is None:          # the tensor this entry was packed from is gone: the address
@@ -305,7 +312,7 @@ class _ConvFn(torch.autograd.Function):
     """y = conv2d(nearest_up(x, up), w, stride, padding, dilation, groups), bias-free, on libbts_hip.so."""
 
     @staticmethod
-    def forward(ctx, x, weight, stride, padding, dilation, up, tag, groups, act=ops.ACT_NONE):
+    def forward(ctx, x, weight, stride, padding, dilation, up, tag, groups, act=ops.ACT_NONE, grouped_native=False):
         refuse_bf16("train.conv2d")
         ops._need(x, "train.conv2d")
         ops._need(weight, "train.conv2d")
@@ -322,11 +329,17 @@ class _ConvFn(torch.autograd.Function):
         if groups > 1:
             if up != 1 or cout != C or act != ops.ACT_NONE:
                 raise BtsHipError("train.conv2d: grouped convolutions need cin == cout, no upsample, no activation")
-            cb = WeightPacker.bundle_channels(weight, groups)
-            wp = _PACKER.get(weight, cb, WeightPacker.FWD, groups)
-            ops.conv_forward(x2d, B, h, w, wp, cb, k, dil=dilation, c_in_ld=cb, y2d=y.view(B * H * W, cout), stride=stride,
-                             pad=padding, tag=tag + ".fwd", c_in_real=cin_g, n_bundles=C // cb)
+            native = _grouped_native_layer(grouped_native, C, groups, k, stride, padding, dilation)
+            if native:
+                wp = _PACKER.get(weight, 0, WeightPacker.FWD_NATIVE, groups)
+                ops.conv_grouped_forward(x2d, B, h, w, wp, C, groups, y2d=y.view(B * H * W, cout), tag=tag + ".fwd")
+            else:
+                cb = WeightPacker.bundle_channels(weight, groups)
+                wp = _PACKER.get(weight, cb, WeightPacker.FWD, groups)
+                ops.conv_forward(x2d, B, h, w, wp, cb, k, dil=dilation, c_in_ld=cb, y2d=y.view(B * H * W, cout), stride=stride,
+                                 pad=padding, tag=tag + ".fwd", c_in_real=cin_g, n_bundles=C // cb)
         else:
+            native = False
             wp = _PACKER.get(weight, c4, WeightPacker.FWD)
             ops.conv_forward(x2d, B, h, w, wp, cout, k, dil=dilation, up=up, c_in_ld=c4, y2d=y.view(B * H * W, cout),
                              stride=stride, pad=padding, tag=tag + ".fwd", c_in_real=C, act=act,
@@ -339,6 +352,7 @@ class _ConvFn(torch.autograd.Function):
         ctx.weight = weight                   # the caller's parameter object: the packer tracks it by identity/version
         ctx.geom = (B, C, h, w, c4, cout, k, stride, padding, dilation, up, H, W, tag, groups)
         ctx.act = act
+        ctx.grouped_native = native           # decided once, in forward: all three passes of a layer take the same form
         return out
 
     @staticmethod
@@ -366,7 +380,10 @@ class _ConvFn(torch.autograd.Function):
                                               else grad_out.permute(0, 2, 3, 1))      # a strided view has co4 == cout
                 g2d, gh, gw = u.view(B * Hs * Ws, co4), Hs, Ws
             dxu = torch.empty((B, Hs, Ws, C), dtype=torch.float32, device=dev)
-            if groups > 1:
+            if ctx.grouped_native:          # the adjoint is the same operator with flipped taps and transposed groups
+                wp = _PACKER.get(weight, 0, WeightPacker.DGRAD_NATIVE, groups)
+                ops.conv_grouped_forward(g2d, B, gh, gw, wp, C, groups, y2d=dxu.view(B * Hs * Ws, C), tag=tag + ".dgrad")
+            elif groups > 1:
                 cb = WeightPacker.bundle_channels(weight, groups)
                 wp = _PACKER.get(weight, cb, WeightPacker.DGRAD, groups)
                 ops.conv_forward(g2d, B, gh, gw, wp, cb, k, dil=dilation, c_in_ld=cb, y2d=dxu.view(B * Hs * Ws, C),
@@ -379,7 +396,9 @@ class _ConvFn(torch.autograd.Function):
                 dxu = dxu.view(B, h, 2, w, 2, C).sum(dim=(2, 4))
             dx = dxu.permute(0, 3, 1, 2)
         if ctx.needs_input_grad[1]:
-            if groups > 1:
+            if ctx.grouped_native:          # written in the parameter's own OIHW layout: no dense block, no gather
+                dw = ops.conv_grouped_wgrad(x2d, B, h, w, dy2d, C, groups, ws=_workspace(dev), tag=tag + ".wgrad")
+            elif groups > 1:
                 cb = WeightPacker.bundle_channels(weight, groups)
                 cg, nb = weight.shape[1], C // cb
                 gpb = cb // cg
@@ -393,16 +412,25 @@ class _ConvFn(torch.autograd.Function):
                 g = ops.conv_wgrad(x2d, B, h, w, c4, dy2d, co4, k, dil=dilation, stride=stride, pad=padding, up=up,
                                    ws=_workspace(dev), tag=tag + ".wgrad")
                 dw = g[:cout, :, :C].reshape(cout, k, k, C).permute(0, 3, 1, 2).contiguous()   # OIHW, the layout DDP buckets expect
-        return dx, dw, None, None, None, None, None, None, None
+        return dx, dw, None, None, None, None, None, None, None, None
+
+
+def _grouped_native_layer(asked, c, groups, k, stride, padding, dilation) -> bool:
+    """Does a grouped layer take the native entry points (bts_conv_grouped_fwd_f32 / bts_conv_grouped_wgrad_f32) in all three
+    passes?  Asked for, fp32 launch precision (bf16x3 stays on bundles silently, as the inference switch does for bf16) and
+    a shape rule only: stride 1, 3x3, padding = dilation = 1, c % 64 == 0, 4 / 8 / 16 channels per group."""
+    return bool(asked) and ops.current_launch_config()[1] == 0 and stride == 1 and k == 3 and padding == 1 and dilation == 1 \
+        and ops.grouped_native_supported(c, groups)
 
 
 def conv2d(x: torch.Tensor, weight: torch.Tensor, padding: int = 0, dilation: int = 1, stride: int = 1,
-           up: int = 1, tag: str = "conv", groups: int = 1, act: int = ops.ACT_NONE) -> torch.Tensor:
+           up: int = 1, tag: str = "conv", groups: int = 1, act: int = ops.ACT_NONE, grouped_native: bool = False) -> torch.Tensor:
     """Differentiable bias-free convolution on the HIP kernels; ``up=2`` folds a nearest-2x upsample of ``x`` into
-    the gather (reference upconv, bts.py:90-92); ``groups`` > 1: ResNeXt's grouped 3x3 as channel bundles;
+    the gather (reference upconv, bts.py:90-92); ``groups`` > 1: ResNeXt's grouped 3x3 as channel bundles, or, with
+    ``grouped_native`` on the layers _grouped_native_layer names, on the native grouped kernels in all three passes;
     ``act=ops.ACT_ELU``: the ELU that follows every decoder convolution (bts.py:93, 183-221) applied in the epilogue.
     Returns a channels_last [B,c_out,H,W] tensor."""
-    return _ConvFn.apply(x, weight, stride, padding, dilation, up, tag, groups, act)
+    return _ConvFn.apply(x, weight, stride, padding, dilation, up, tag, groups, act, grouped_native)
 
 
 _BN_WS: Dict[Tuple[str, int], torch.Tensor] = {}
@@ -915,12 +943,13 @@ def densenet_encoder_forward(enc, x):
 
 
 # ------------------------------------------------------------------------------------------ encoder (ResNet / ResNeXt)
-def _bottleneck(blk, x, tag):
-    """torchvision Bottleneck.forward: 1x1 -> (grouped, strided) 3x3 -> 1x1, + identity, ReLU."""
+def _bottleneck(blk, x, tag, grouped_native=False):
+    """torchvision Bottleneck.forward: 1x1 -> (grouped, strided) 3x3 -> 1x1, + identity, ReLU.  ``grouped_native``:
+    encoder.grouped_conv_train."""
     out = _bn(conv2d(x, blk.conv1.weight, tag=tag), blk.bn1, relu=True)
     c2 = blk.conv2
     out = _bn(conv2d(out, c2.weight, padding=c2.padding[0], dilation=c2.dilation[0], stride=c2.stride[0], groups=c2.groups,
-                     tag=tag), blk.bn2, relu=True)
+                     tag=tag, grouped_native=grouped_native), blk.bn2, relu=True)
     out = _bn(conv2d(out, blk.conv3.weight, tag=tag), blk.bn3)
     if blk.downsample is not None:
         d = blk.downsample[0]
@@ -937,12 +966,13 @@ def resnet_encoder_forward(enc, x):
     m = enc.base_model
     cur = x.float().contiguous(memory_format=torch.channels_last)
     c1 = m.conv1
+    native = bool(getattr(enc, "grouped_conv_train", False))
     with _deferred_batch_counts():
         cur = _bn(conv2d(cur, c1.weight, padding=c1.padding[0], stride=c1.stride[0], tag="enc"), m.bn1, relu=True)
         taps = [x, cur]
         cur = m.maxpool(cur)
         for li, layer in enumerate((m.layer1, m.layer2, m.layer3, m.layer4)):
             for blk in layer:
-                cur = _bottleneck(blk, cur, "enc")
+                cur = _bottleneck(blk, cur, "enc", native)
             taps.append(cur)
     return taps

@@ -370,6 +370,32 @@ int bts_conv_grouped_fwd_f32(const float* x, long x_pix_stride, int B, int h, in
  *   FRAME; all three 0 when the layer should stay on bundles. */
 int bts_conv_grouped_plan(int h, int w, int c, int groups, int precision, int fill_frames, int* bm, int* bn, long* workgroups);
 
+/* Weight gradient of the same grouped 3x3 convolution (csrc/conv_grouped_wgrad.inc, v_mfma_f32_16x16x1_4b_f32: one
+ * instruction accumulates four 16 x 16 (output channel x input channel) blocks from one dy and one x float per lane):
+ *   dw[n][k][tap] = sum_{b, p} dy[b, p][n] * x[b, q(p, tap)][cg * (n / cg) + k],   tap = 3 (dy+1) + (dx+1)
+ * stride 1, padding 1, zero padding.  The input gradient needs no entry point of its own: bts_conv_grouped_fwd_f32 on dy
+ * with the weights of bts_pack_weights_f32's gmode 4.
+ *   x, dy : NHWC [B,h,w], pixel strides >= c floats (multiples of 4), 16-byte aligned; either may be a channel slice of a
+ *           wider buffer
+ *   dw    : c * cg * 9 floats, 16-byte aligned, the parameter's own OIHW layout [c][cg][3][3]; every float is written
+ *   ws    : ws_floats floats of scratch for the split partials, 16-byte aligned, or NULL
+ * The tile axis (8 x 16-pixel tiles of all B frames) is split over workgroups; partials [split][c / 64][9][16][64] go to ws
+ * and a second launch sums the in-group entries in ascending split order and writes OIHW (no atomics; the products of a
+ * 16-channel block that cross groups, cg < 16, are computed and never reach dw).  The split count is a function of
+ * (B, h, w, c, groups, ws_floats) only: min(ceil(512 / (c / 64)), tiles), lowered to what ws holds (ws_floats / (144 c)),
+ * 1 with ws == NULL or room for fewer than two partials -- never an error; then settled so that no split is empty.
+ * c % 64 != 0 or cg not in {4, 8, 16}: BTS_ERR_UNSUPPORTED, as is B * h * w >= 2^31 (32-bit pixel and tile indices).
+ * Sum order fixed by the shape and the split count: bit-reproducible.  Non-finite values: an x or dy value reaches only dw
+ * entries of its own 16-channel block; the cross-group products are dropped, so for the written entries its own group.
+ * Pixels of ragged tiles outside the map are skipped, never multiplied by zero. */
+int bts_conv_grouped_wgrad_f32(const float* x, long x_pix_stride, const float* dy, long dy_pix_stride, int B, int h, int w, int c,
+                               int groups, float* dw, float* ws, long ws_floats, bts_stream_t stream);
+
+/* The split bts_conv_grouped_wgrad_f32 runs with a workspace of ws_floats floats (host-side query, no GPU work, no pointers;
+ * ws_floats 0 = no workspace) and the floats of it the launch writes (0 when unsplit; <= ws_floats).  Unsupported shapes are
+ * refused as by the launch. */
+int bts_conv_grouped_wgrad_plan(int B, int h, int w, int c, int groups, long ws_floats, int* splits, long* ws_floats_used);
+
 /* Which kernel bts_conv_fwd_f32 will launch for this descriptor (host-side query, no GPU work: it walks the real
  * dispatch path): lets a profiler attribute a launch to its kernel instantiation.
  *   *kind = one kernel family (kind & BTS_CONV_KIND_MASK) plus any of the BTS_CONV_FLAG_* bits. */
@@ -547,6 +573,12 @@ int bts_upconv_train_pack_f32(const void* table, int n_entries, long total_block
  *   forward layout : rows = c_out, inner = c_in, s_row = c_in*k*k, s_c = k*k, flip 0
  *   input gradient : rows = c_in, inner = c_out, s_row = k*k, s_c = c_in*k*k, flip 1   (transposed, flipped kernel)
  * dst[row][tap*c_in_ld + c] = src[row*s_row + c*s_c + (flip ? k*k-1-tap : tap)], zero elsewhere.
+ * gmode 3 / 4: src is a whole grouped [c][cg][3][3] weight and dst the 144 * c floats bts_conv_grouped_fwd_f32 reads
+ * (rows_pad * k_pad = 144 * c; of the other fields only cg is read).  With n = 64 s + lane the output channel and
+ * ci = 64 s + 16 (lane >> 4) + k the input channel of float ((s * 9 + tap) * 16 + k) * 64 + lane:
+ *   gmode 3 (forward)        : w[n][ci mod cg][tap]           where ci lies in n's group, else 0  (ops.pack_grouped_native's bits)
+ *   gmode 4 (input gradient) : w[ci][n mod cg][8 - tap]       where ci lies in n's group, else 0  -- the forward layout of
+ *                              w_t[cg g + i][o][8 - tap] = w[cg g + o][i][tap]: run on dy it yields dx.
  */
 long bts_pack_weights_blocks(long rows_pad, long k_pad);
 int bts_pack_weights_f32(const void* table, int n_entries, long total_blocks, bts_stream_t stream);

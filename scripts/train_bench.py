@@ -43,6 +43,9 @@ def main():
                          "of torch's fused AdamW + a full re-pack")
     ap.add_argument("--subpixel-upconv", action="store_true",
                     help="the decoder's ratio-2 upconvs in sub-pixel form in all three passes (BtsModel.subpixel_upconv_train)")
+    ap.add_argument("--grouped-native", action="store_true",
+                    help="ResNeXt's stride-1 grouped 3x3 layers on the native grouped kernels in all three passes "
+                         "(BtsModel.grouped_conv_train)")
     a = ap.parse_args()
     # BASELINE config 5 (B=32 over 8 GPUs = 4 per GPU, DDP): launch with
     #   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 scripts/train_bench.py
@@ -66,6 +69,7 @@ def main():
     model.fused_reduction_train = a.fused_reduc
     model.batched_wgrad = a.batched_wgrad
     model.subpixel_upconv_train = a.subpixel_upconv
+    model.grouped_conv_train = a.grouped_native
     loss_fn = M.silog_loss(0.85, native=a.native_loss)
     if not a.no_freeze:
         trainer.set_misc(model, a.encoder)          # the reference freezes the stem conv and the encoder norm affines
@@ -123,7 +127,7 @@ def main():
                loss="silog native (HIP)" if a.native_loss else "silog torch",
                config=dict(encoder=a.encoder, batch_per_gpu=B, height=H, width=W, decoder_only=a.decoder_only,
                            fused_reduc=a.fused_reduc, batched_wgrad=a.batched_wgrad, native_optim=a.native_optim,
-                           subpixel_upconv=a.subpixel_upconv),
+                           subpixel_upconv=a.subpixel_upconv, grouped_native=a.grouped_native),
                peak_mem_gb=torch.cuda.max_memory_allocated() / 2**30)
     if a.trace:
         tr = ops.KernelTrace()
