@@ -61,9 +61,9 @@ __device__ __forceinline__ f32x4 sum_lanes(const f32x4 (&red)[16][16], int el) {
 
 // Raise a kernel's dynamic-LDS limit above the 64 KB default.  hipFuncAttributeMaxDynamicSharedMemorySize is a property
 // of (function, DEVICE): a process that drives several GPUs (nn.DataParallel: one Python thread per device,
-// bts_test.py:91) must set it on each of them.  `done` is one bit per device ordinal, owned by the kernel
-// instantiation's launcher; the only library state that is ever written after load, idempotent (setting the attribute
-// twice is harmless) and lock-free, so concurrent callers on any mix of devices and streams are safe.
+// bts_test.py:91) must set it on each of them.  `done` is one bit per device ordinal, one word per kernel (lds_set
+// below); the only library state that is ever written after load, idempotent (setting the attribute twice is harmless)
+// and lock-free, so concurrent callers on any mix of devices and streams are safe.
 inline hipError_t bts_ensure_dynamic_lds(const void* kern, size_t bytes, std::atomic<unsigned long long>& done) {
     if (bytes < 64 * 1024) return hipSuccess;
     int dev = 0;
@@ -75,4 +75,15 @@ inline hipError_t bts_ensure_dynamic_lds(const void* kern, size_t bytes, std::at
     if (e != hipSuccess) return e;
     if (bit) done.fetch_or(bit, std::memory_order_release);
     return hipSuccess;
+}
+
+// The one way the library enqueues a kernel that may need more than 64 KB of dynamic LDS: raise Kern's limit on the current
+// device if `lds_bytes` asks for it, then launch.  Returns the attribute step's error, or 0 with the kernel enqueued; the
+// caller reads hipGetLastError after its last launch.
+template <auto Kern> inline std::atomic<unsigned long long> lds_set{0};      // per kernel: one bit per device
+template <auto Kern, typename... Args>
+int bts_launch(dim3 grid, dim3 block, size_t lds_bytes, hipStream_t s, const Args&... args) {
+    if (hipError_t e = bts_ensure_dynamic_lds((const void*)Kern, lds_bytes, lds_set<Kern>); e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(Kern, grid, block, lds_bytes, s, args...);
+    return 0;
 }

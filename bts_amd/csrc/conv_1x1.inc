@@ -207,7 +207,7 @@ inline bool conv1x1_eligible(const ConvArgs& a, bool nchw, int bn) {
 }
 
 template <int BN, int WM = 4, bool SB = false>
-int launch_conv1x1(const ConvArgs& a0, hipStream_t s) {
+int launch_conv1x1(const ConvArgs& a0, const ConvRun& r) {
     ConvArgs a = a0;
     constexpr int BM = WM * 32;
     const long n_mtiles = (a.M + BM - 1) / BM;
@@ -215,12 +215,6 @@ int launch_conv1x1(const ConvArgs& a0, hipStream_t s) {
     a.tiles_per_class = (int)(n_mtiles * a.n_ntiles);
     a.ksplit = 1;
     const long nwg = n_mtiles * a.n_ntiles;
-    if (nwg > 0x7fffffffL) return BTS_ERR_INVALID;
-    if (g_dry) { *g_dry = ConvChoice{BTS_CONV_KIND_WIDE_1X1, BM, BN, 1}; return 0; }
     const size_t lds = (size_t)(2 * BM + (SB ? 1 : 2) * BN) * LdsLd<32>::value * sizeof(float);
-    auto k = conv1x1_kernel<BN, WM, SB>;
-    static std::atomic<unsigned long long> lds_set{0};
-    if (hipError_t e = bts_ensure_dynamic_lds((const void*)k, lds, lds_set); e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(k, dim3((unsigned)nwg), dim3(WM * 128), lds, s, a);
-    return (int)hipGetLastError();
+    return conv_launch<conv1x1_kernel<BN, WM, SB>>(r, ConvChoice{BTS_CONV_KIND_WIDE_1X1, BM, BN, 1}, BTS_ERR_INVALID, nwg, nwg, WM * 128, lds, a);
 }

@@ -474,7 +474,7 @@ inline bool halo_eligible(const ConvArgs& a, bool precision0, int mf, double* fi
 }
 
 template <int BN, int WM, int WN, int MF, int KS, bool TAIL = false, bool SB = false, int DIL = 1>
-int launch_halo(const ConvArgs& a0, bool nchw, hipStream_t s) {
+int launch_halo(const ConvArgs& a0, const ConvRun& r) {
     ConvArgs a = a0;
     constexpr int TW = MF, TH = 128 / MF;
     constexpr int NPIX = (TH + KS - 1) * (TW + (KS - 1) * DIL);
@@ -484,9 +484,8 @@ int launch_halo(const ConvArgs& a0, bool nchw, hipStream_t s) {
     a.tiles_per_class = (int)(n_mtiles * a.n_ntiles);
     a.ksplit = 1;
     const long nwg = n_mtiles * a.n_ntiles * a.n_classes;
-    if (nwg > 0x7fffffffL) return BTS_ERR_INVALID;
-    if (DIL > 1 && (nchw || a.dil != DIL || a.pad != DIL)) return BTS_ERR_INVALID;
-    if (g_dry) { *g_dry = ConvChoice{(TAIL ? BTS_CONV_KIND_HALO_TAIL : BTS_CONV_KIND_HALO) | (BN == 48 && WM == 8 ? BTS_CONV_FLAG_W8 : 0) | (DIL > 1 ? BTS_CONV_FLAG_DIL : 0), 128, BN, 1}; return 0; }
+    if (DIL > 1 && (r.nchw || a.dil != DIL || a.pad != DIL)) return BTS_ERR_INVALID;
+    const ConvChoice c{(TAIL ? BTS_CONV_KIND_HALO_TAIL : BTS_CONV_KIND_HALO) | (BN == 48 && WM == 8 ? BTS_CONV_FLAG_W8 : 0) | (DIL > 1 ? BTS_CONV_FLAG_DIL : 0), 128, BN, 1};
     static_assert(halo_lds_bytes<BN, MF, KS, DIL>() == 2 * (NPIX + BN) * LdsLd<MF>::value * 4, "LDS size");
     const int c_main = TAIL ? a.c_in_ld - 4 : a.c_in_ld;
     a.halo_single_a = c_main <= BK ? 1 : 0;
@@ -495,19 +494,8 @@ int launch_halo(const ConvArgs& a0, bool nchw, hipStream_t s) {
     static_assert(!SB || (size_t)(2 * NPIX + BN) * LdsLd<MF>::value * 4 <= 160 * 1024, "single-weight-buffer tile must fit the LDS");
     if (SB) a.halo_single_a = 0;
     a.stagger = (BN == 48 && WM * WN == 8) ? 1 : 0;
-    hipError_t e;
-    if constexpr (DIL == 1) {
-        if (nchw) {
-            auto k = conv_halo_kernel<BN, WM, WN, MF, KS, true, TAIL, SB>;
-            static std::atomic<unsigned long long> lds_set{0};
-            if ((e = bts_ensure_dynamic_lds((const void*)k, lds, lds_set)) != hipSuccess) return (int)e;
-            hipLaunchKernelGGL(k, dim3((unsigned)nwg), dim3(WM * WN * 64), lds, s, a);
-            return (int)hipGetLastError();
-        }
+    if constexpr (DIL == 1) {                          // the dilated tiles have no NCHW twin
+        if (r.nchw) return conv_launch<conv_halo_kernel<BN, WM, WN, MF, KS, true, TAIL, SB>>(r, c, BTS_ERR_INVALID, nwg, nwg, WM * WN * 64, lds, a);
     }
-    auto k = conv_halo_kernel<BN, WM, WN, MF, KS, false, TAIL, SB, DIL>;
-    static std::atomic<unsigned long long> lds_set{0};
-    if ((e = bts_ensure_dynamic_lds((const void*)k, lds, lds_set)) != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(k, dim3((unsigned)nwg), dim3(WM * WN * 64), lds, s, a);
-    return (int)hipGetLastError();
+    return conv_launch<conv_halo_kernel<BN, WM, WN, MF, KS, false, TAIL, SB, DIL>>(r, c, BTS_ERR_INVALID, nwg, nwg, WM * WN * 64, lds, a);
 }

@@ -414,20 +414,15 @@ inline bool halo_emu_eligible(const ConvArgs& a, bool nchw) {
 }
 
 template <int BN, int KS, int NP = 3>
-int launch_halo_emu(const ConvArgs& a0, hipStream_t s) {
+int launch_halo_emu(const ConvArgs& a0, const ConvRun& r) {
     ConvArgs a = a0;
     const long n_mtiles = (long)a.B * tiles_4x32(a.H, a.W);
     a.n_ntiles = (a.c_out + BN - 1) / BN;
     a.tiles_per_class = (int)(n_mtiles * a.n_ntiles);
     a.ksplit = 1;
     const long nwg = n_mtiles * a.n_ntiles * a.n_classes;
-    if (nwg > 0x7fffffffL) return BTS_ERR_INVALID;
-    if (g_dry) { *g_dry = ConvChoice{NP == 3 ? BTS_CONV_KIND_HALO_EMU : BTS_CONV_KIND_HALO_BF16, 128, BN, 1}; return 0; }
     constexpr size_t lds = (size_t)HaloEmuGeom<BN, KS, NP>::LDS_BYTES;
     static_assert(lds <= 160 * 1024, "LDS");
-    auto k = conv_halo_emu_kernel<BN, KS, NP>;
-    static std::atomic<unsigned long long> lds_set{0};
-    if (hipError_t e = bts_ensure_dynamic_lds((const void*)k, lds, lds_set); e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(k, dim3((unsigned)nwg), dim3(512), lds, s, a);
-    return (int)hipGetLastError();
+    return conv_launch<conv_halo_emu_kernel<BN, KS, NP>>(r, ConvChoice{NP == 3 ? BTS_CONV_KIND_HALO_EMU : BTS_CONV_KIND_HALO_BF16, 128, BN, 1},
+                                                         BTS_ERR_INVALID, nwg, nwg, 512, lds, a);
 }

@@ -816,9 +816,32 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_fwd_kernel(const ConvArgs a
         }
 }
 
-// bts_conv_plan_f32 runs the real dispatch with this set: launch_* then report their choice instead of launching
+// What a launcher chose: the answer of a plan query (bts_conv_plan_f32, bts_conv_plan_ksteps_f32, bts_upconv_dgrad_plan)
 struct ConvChoice { int kind, bm, bn, ksplit; long ksteps_issued = 0, ksteps_dense = 0; };   // ksteps: tap-steps over all row tiles (tap skipping)
-thread_local ConvChoice* g_dry = nullptr;
+
+// What a launcher gets besides the kernel arguments.  `plan` set: a plan query walks the same dispatch -- the launcher
+// stores its choice there and calls no HIP function.
+struct ConvRun {
+    hipStream_t stream;
+    ConvChoice* plan;                // null: launch
+    bool nchw;                       // bts_conv_desc.y_nchw
+    long ws_floats;                  // the split-K workspace the caller lent (0: none)
+    int prec;                        // the precision that runs: the descriptor's unless $BTS_CONV_PRECISION overrides it
+};
+
+// The shared tail of every launcher, in this order for every kernel family: more workgroups (`tiles`; the persistent kernels
+// launch a smaller `grid`) than a grid dimension holds is the launcher's error `too_many`, which a plan query reports as
+// well; a plan query gets `choice` and no HIP call; a launch raises Kern's dynamic-LDS limit where `lds` needs it and enqueues.
+constexpr long kMaxWgs = 0x7fffffffL;
+inline ConvRun launch_on(bts_stream_t stream) { return ConvRun{(hipStream_t)stream, nullptr, false, 0, 0}; }     // the opt-in entry points: always a launch
+template <auto Kern, typename... Args>
+int conv_launch(const ConvRun& r, const ConvChoice& choice, int too_many, long tiles, long grid, int threads, size_t lds,
+                const Args&... args) {
+    if (tiles > kMaxWgs) return too_many;
+    if (r.plan) { *r.plan = choice; return 0; }
+    if (const int rc = bts_launch<Kern>(dim3((unsigned)grid), dim3((unsigned)threads), lds, r.stream, args...); rc != 0) return rc;
+    return (int)hipGetLastError();
+}
 
 #include "conv_halo.inc"
 #include "conv_halo_emu.inc"
@@ -903,7 +926,7 @@ inline bool geometry_kernel_ok(const ConvArgs& a, int bn, long ws_floats, long w
 }
 
 template <int BM, int BN, int WM, int WN, int MF = 32, int PREC = 0>
-int launch_conv(const ConvArgs& a0, bool nchw, hipStream_t s, long ws_floats) {
+int launch_conv(const ConvArgs& a0, const ConvRun& r) {
     ConvArgs a = a0;
     const long n_mtiles = (a.M + BM - 1) / BM;
     a.n_ntiles = (a.c_out + BN - 1) / BN;            // tiles over REAL channels; wrow clamps into c_out_pad
@@ -915,50 +938,34 @@ int launch_conv(const ConvArgs& a0, bool nchw, hipStream_t s, long ws_floats) {
     // bits, must not depend on how many frames share the launch (frames are independent, bts.py:223-293).
     const int nit_all = a.k_pad / BK;
     a.ksplit = 1; a.its_per_split = nit_all; a.ws_ld = (a.c_out + 3) & ~3;
-    if (const int sp = split_factor(a, ws_floats); sp > 1) {
+    if (const int sp = split_factor(a, r.ws_floats); sp > 1) {
         a.its_per_split = (nit_all + sp - 1) / sp;
         a.ksplit = (nit_all + a.its_per_split - 1) / a.its_per_split;     // no empty splits
     }
     const long nwg = tiles * a.ksplit;
-    if (nwg > 0x7fffffffL) return BTS_ERR_INVALID;
     const bool lean = (a.c_in_ld % BK) == 0 && a.ups == 0;
     a.tapskip = (knobs().tapskip && lean && a.ksplit == 1 && a.stride == 1 && a.ksize > 1 && a.ksize * a.ksize <= 49) ? 1 : 0;
-    if (g_dry) {
-        *g_dry = ConvChoice{PREC == 3 ? BTS_CONV_KIND_ROW_BF16 : BTS_CONV_KIND_ROW, BM, BN, a.ksplit};
-        const long taps = (long)a.ksize * a.ksize;
-        g_dry->ksteps_dense = n_mtiles * a.n_classes * taps;
-        g_dry->ksteps_issued = g_dry->ksteps_dense;
-        if (a.tapskip) {                           // the kernel's own tile rule, summed over the row tiles (x classes)
-            long issued = 0;
+    ConvChoice c{PREC == 3 ? BTS_CONV_KIND_ROW_BF16 : BTS_CONV_KIND_ROW, BM, BN, a.ksplit};
+    if (r.plan && nwg <= kMaxWgs) {                    // the tap-step counts: for a plan query only, never on a launch
+        c.ksteps_dense = c.ksteps_issued = n_mtiles * a.n_classes * (long)a.ksize * a.ksize;
+        if (a.tapskip) {                               // the kernel's own tile rule, summed over the row tiles (x classes)
+            c.ksteps_issued = 0;
             for (int cls = 0; cls < a.n_classes; ++cls) {
                 const int pad_y = a.subpix ? 1 - (cls >> 1) : a.pad, pad_x = a.subpix ? 1 - (cls & 1) : a.pad;
                 for (long mt = 0; mt < n_mtiles; ++mt)
-                    issued += __builtin_popcountll(tile_tapmask(a.H, a.W, a.Hs, a.Ws, a.ksize, a.dil, pad_y, pad_x, a.M, mt * BM, BM));
+                    c.ksteps_issued += __builtin_popcountll(tile_tapmask(a.H, a.W, a.Hs, a.Ws, a.ksize, a.dil, pad_y, pad_x, a.M, mt * BM, BM));
             }
-            g_dry->ksteps_issued = issued;
         }
-        return 0;
     }
     const size_t lds = PREC == 0 ? (size_t)2 * (BM + BN) * LdsLd<MF>::value * sizeof(float)
                                  : (size_t)(PREC == 3 ? 2 : 3) * (BM + BN) * EMU_ROW_BYTES;     // bf16: two buffers of one plane
-    hipError_t e;
-    if (nchw) {
-        auto k = conv_fwd_kernel<BM, BN, WM, WN, MF, true, PREC>;
-        static std::atomic<unsigned long long> lds_set{0};    // per instantiation: one bit per device (bts_ensure_dynamic_lds)
-        if ((e = bts_ensure_dynamic_lds((const void*)k, lds, lds_set)) != hipSuccess) return (int)e;
-        hipLaunchKernelGGL(k, dim3((unsigned)nwg), dim3(WM * WN * 64), lds, s, a);
-    } else {
-        auto k = conv_fwd_kernel<BM, BN, WM, WN, MF, false, PREC>;
-        static std::atomic<unsigned long long> lds_set{0};
-        if ((e = bts_ensure_dynamic_lds((const void*)k, lds, lds_set)) != hipSuccess) return (int)e;
-        hipLaunchKernelGGL(k, dim3((unsigned)nwg), dim3(WM * WN * 64), lds, s, a);
-    }
-    if (a.ksplit > 1) {
-        const long total = a.M * (long)a.c_out;
-        long blocks = (total + 255) / 256;
-        if (blocks > 256L * 8) blocks = 256L * 8;
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a, nchw ? 1 : 0);
-    }
+    const int rc = r.nchw ? conv_launch<conv_fwd_kernel<BM, BN, WM, WN, MF, true, PREC>>(r, c, BTS_ERR_INVALID, nwg, nwg, WM * WN * 64, lds, a)
+                          : conv_launch<conv_fwd_kernel<BM, BN, WM, WN, MF, false, PREC>>(r, c, BTS_ERR_INVALID, nwg, nwg, WM * WN * 64, lds, a);
+    if (rc != 0 || r.plan || a.ksplit == 1) return rc;
+    const long total = a.M * (long)a.c_out;
+    long blocks = (total + 255) / 256;
+    if (blocks > 256L * 8) blocks = 256L * 8;
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, r.stream, a, r.nchw ? 1 : 0);
     return (int)hipGetLastError();
 }
 
@@ -985,17 +992,11 @@ void choose_tile(long M, int c_out, int* bm, int* bn) {
     }
 }
 
-}  // namespace
-
-namespace {
-// even_ok: bts_upconv_dgrad_f32's own 4x4 / stride-2 gather; bts_conv_fwd_f32's accept set stays odd ksize
-int conv_dispatch(const bts_conv_desc* d, bts_stream_t stream, bool even_ok = false);
-}
-
-extern "C" int bts_conv_fwd_f32(const bts_conv_desc* d, bts_stream_t stream) { return conv_dispatch(d, stream); }
-
-namespace {
-int conv_dispatch(const bts_conv_desc* d, bts_stream_t stream, bool even_ok) {
+// Step 1 of conv_dispatch: every check on the descriptor (the order decides which code a doubly wrong descriptor gets:
+// tests/golden/conv_reject_table.npz), the kernel arguments `a` (value-initialised by the caller; the launchers set the tile
+// and split fields), and what `r` takes from the descriptor: y_nchw, the lent workspace, the precision that runs.  No launch,
+// no kernel choice.  even_ok: bts_upconv_dgrad_f32's own 4x4 / stride-2 gather; bts_conv_fwd_f32's accept set stays odd ksize.
+int conv_args(const bts_conv_desc* d, bool even_ok, ConvArgs& a, ConvRun& r) {
     if (!d || !d->x || !d->w || !d->y) return BTS_ERR_INVALID;
     if (d->B <= 0 || d->h_in <= 0 || d->w_in <= 0 || d->c_out <= 0) return BTS_ERR_INVALID;
     if (d->up != 1 && d->up != 2) return BTS_ERR_UNSUPPORTED;
@@ -1021,7 +1022,6 @@ int conv_dispatch(const bts_conv_desc* d, bts_stream_t stream, bool even_ok) {
     if ((double)d->B * d->h_in * d->w_in * (double)d->x_pix_stride >= 4294967296.0) return BTS_ERR_UNSUPPORTED;
     if ((double)d->c_out_pad * (double)d->k_pad * (d->subpixel ? 4.0 : 1.0) >= 4294967296.0) return BTS_ERR_UNSUPPORTED;
 
-    ConvArgs a;
     a.x = d->x; a.x_pix_stride = d->x_pix_stride; a.c_in_ld = d->c_in_ld; a.k_pad = d->k_pad;
     a.B = d->B; a.h_in = d->h_in; a.w_in = d->w_in; a.ups = d->up == 2 ? 1 : 0;
     a.ksize = d->ksize; a.dil = d->dil; a.stride = d->stride; a.pad = d->pad; a.subpix = d->subpixel ? 1 : 0;
@@ -1042,8 +1042,7 @@ int conv_dispatch(const bts_conv_desc* d, bts_stream_t stream, bool even_ok) {
     if (a.H <= 0 || a.W <= 0) return BTS_ERR_INVALID;
     a.M = (long)d->B * a.H * a.W;
     if (a.M >= 2147483648L) return BTS_ERR_UNSUPPORTED;          // the kernel decodes pixel indices with 32-bit arithmetic
-    a.n_ntiles = 0; a.tiles_per_class = 0;
-    a.n_classes = a.subpix ? 4 : 1; a.bundled = 0;
+    a.n_classes = a.subpix ? 4 : 1;
     a.res = d->res; a.res_pix_stride = d->res_pix_stride;
     a.n_tail = d->n_tail;
     if (d->fill_frames < 0 || d->fill_frames > 4096) return BTS_ERR_INVALID;
@@ -1068,70 +1067,70 @@ int conv_dispatch(const bts_conv_desc* d, bts_stream_t stream, bool even_ok) {
         if ((double)d->n_bundles * d->c_out_pad * (double)d->k_pad >= 4294967296.0) return BTS_ERR_UNSUPPORTED;
         a.n_classes = d->n_bundles; a.bundled = 1;
     } else if (d->n_bundles < 0) return BTS_ERR_INVALID;
-    a.ksplit = 1; a.its_per_split = 0; a.ws_ld = 0; a.tapskip = 0; a.halo_single_a = 0; a.stagger = 0; a.w_split = d->w_split; a.w_wino = d->w_wino;
+    a.ksplit = 1; a.w_split = d->w_split; a.w_wino = d->w_wino;
     a.ws = d->splitk_ws;
-    const long wsf = d->splitk_ws ? d->splitk_ws_floats : 0;
+    r.ws_floats = d->splitk_ws ? d->splitk_ws_floats : 0;
     if (d->splitk_ws && (((uintptr_t)d->splitk_ws & 15) || d->splitk_ws_floats < 0)) return BTS_ERR_INVALID;
-    hipStream_t s = (hipStream_t)stream;
-    const bool nchw = d->y_nchw != 0;
-    int bm, bn;
-    choose_tile(a.M * a.n_classes, d->c_out, &bm, &bn);
+    r.nchw = d->y_nchw != 0;
     // precision: 0 = v_mfma_f32_32x32x2_f32 (exact fp32 products), 1 = fp32 emulated on the bf16 matrix cores
     // (three-way split, six products; see split_store), 2 = bf16 operands rounded to nearest even, one product (rne_store).
     // BTS_CONV_PRECISION (0 / 1) overrides the descriptor (A/B runs).
     const int prec_env = knobs().precision;
-    const int prec = prec_env >= 0 ? prec_env : d->precision;
-    if (prec != 0 && prec != 1 && prec != 2) return BTS_ERR_INVALID;
+    r.prec = prec_env >= 0 ? prec_env : d->precision;
+    if (r.prec != 0 && r.prec != 1 && r.prec != 2) return BTS_ERR_INVALID;
     if (prec_env >= 0 && prec_env != 0 && prec_env != 1) return BTS_ERR_INVALID;
     // w_split's layout is the DESCRIPTOR's precision (three planes for 1, one for 2): when BTS_CONV_PRECISION overrides it,
     // the buffer does not describe the arithmetic that runs -- the kernels then work from the fp32 `w` alone
-    if (prec != d->precision) a.w_split = nullptr;
+    if (r.prec != d->precision) a.w_split = nullptr;
+    return 0;
+}
+
+// The bf16 branches of conv_choose.  PREC 1: fp32 emulated with three bf16 planes (pre-split weights, row tile PREC 2);
+// PREC 2: one plane rounded to nearest even (pre-rounded weights, row tile PREC 3).  Never Winograd (its transformed operands
+// would not be the rounded ones), never the fp32 wide 1x1.
+template <int PREC>
+int conv_choose_bf16(const ConvArgs& a, const ConvRun& r, int bm, int bn) {
+    constexpr int NP = PREC == 1 ? 3 : 1, ROW = PREC == 1 ? 2 : 3;
+    if (bn == 48) bn = 64;                           // the 16x16x4 48-wide tile has no bf16 twin: pad DenseNet's growth convs to 64
+    // stride-1 3x3 / sub-pixel 2x2 convolutions on maps that tile well, whole 32-channel chunks, pre-split (pre-rounded)
+    // weights: the bf16 halo-tile kernel (conv_halo_emu.inc)
+    if ((bn == 128 || bn == 64) && halo_emu_eligible(a, r.nchw)) {
+        const long halo_wgs = (long)a.fill_frames * tiles_4x32(a.H, a.W) * ((a.c_out + bn - 1) / bn) * a.n_classes;
+        if (geometry_kernel_ok(a, bn, r.ws_floats, halo_wgs)) {
+            if (a.subpix) return bn == 128 ? launch_halo_emu<128, 2, NP>(a, r) : launch_halo_emu<64, 2, NP>(a, r);
+            return bn == 128 ? launch_halo_emu<128, 3, NP>(a, r) : launch_halo_emu<64, 3, NP>(a, r);
+        }
+    }
+    // everything else (1x1, strided, dilated, bundles, split-K, NCHW output, residual): the row-tiled kernel; under PREC 2 it
+    // rounds the fp32 weights itself on the way to LDS (the same rounding as the pre-rounded plane).
+    // PREC 1 -- ONE LDS buffer per workgroup: the planes take 6 B per element, and with one buffer (two barriers per K-step, the
+    // other resident workgroup fills the gaps) every tile runs faster than double-buffered with fewer workgroups per CU
+    // (total over the decoder layers 134.7 vs 126.6 TFLOP/s-equivalent).  (Forcing a third workgroup per CU with an
+    // 80-VGPR cap on the narrow tiles: same layer rates, whole model 39.7 vs 38.3 ms -- dropped.)
+    if (bn == 128) return bm == 128 ? launch_conv<128, 128, 2, 4, 32, ROW>(a, r) : launch_conv<64, 128, 2, 4, 32, ROW>(a, r);
+    if (bn == 64) return bm == 128 ? launch_conv<128, 64, 4, 2, 32, ROW>(a, r) : launch_conv<64, 64, 2, 2, 32, ROW>(a, r);
+    return launch_conv<128, 32, 4, 1, 32, ROW>(a, r);
+}
+
+// Step 2 of conv_dispatch: the kernel choice -- one tree, a function of the per-frame geometry, the declared frames per launch
+// and the precision only -- down to the launcher instantiation that runs it (or, for a plan query, reports itself).
+int conv_choose(const ConvArgs& a, const ConvRun& r) {
+    const bool nchw = r.nchw;
+    const long wsf = r.ws_floats;
+    int bm, bn;
+    choose_tile(a.M * a.n_classes, a.c_out, &bm, &bn);
     // fused Winograd F(2x2,3x3) (conv_wino.inc), planar-tail layers included (conv3 / conv2: NHWC output)
-    if (a.n_tail > 0 && prec == 0 && knobs().wino && (bn == 128 || bn == 64) && a.c_out_pad % (bn == 128 ? 128 : 64) == 0 && wino_eligible(a, nchw))
-        return bn == 128 ? launch_wino<128, true>(a, s) : launch_wino<64, true>(a, s);
+    if (a.n_tail > 0 && r.prec == 0 && knobs().wino && (bn == 128 || bn == 64) && a.c_out_pad % (bn == 128 ? 128 : 64) == 0 && wino_eligible(a, nchw))
+        return bn == 128 ? launch_wino<128, true>(a, r) : launch_wino<64, true>(a, r);
     if (a.n_tail > 0) {   // planar tail operand: always the halo-tile kernel (fp32-input MFMA whatever `precision` says)
-        if (bn == 128) return launch_halo<128, 4, 2, 32, 3, true>(a, nchw, s);
-        if (bn == 32) return launch_halo<32, 4, 1, 32, 3, true>(a, nchw, s);
-        return launch_halo<64, 4, 2, 32, 3, true>(a, nchw, s);
+        if (bn == 128) return launch_halo<128, 4, 2, 32, 3, true>(a, r);
+        if (bn == 32) return launch_halo<32, 4, 1, 32, 3, true>(a, r);
+        return launch_halo<64, 4, 2, 32, 3, true>(a, r);
     }
-    if (prec == 1) {
-        if (bn == 48) bn = 64;                       // the 16x16x4 48-wide tile has no bf16x3 twin: pad to 64
-        // stride-1 3x3 / sub-pixel 2x2 convolutions on maps that tile well, whole 32-channel chunks, pre-split weights:
-        // the bf16x3 halo-tile kernel (conv_halo_emu.inc)
-        if ((bn == 128 || bn == 64) && halo_emu_eligible(a, nchw)) {
-            const long halo_wgs = (long)a.fill_frames * tiles_4x32(a.H, a.W) * ((a.c_out + bn - 1) / bn) * a.n_classes;
-            if (geometry_kernel_ok(a, bn, wsf, halo_wgs)) {
-                if (a.subpix) return bn == 128 ? launch_halo_emu<128, 2>(a, s) : launch_halo_emu<64, 2>(a, s);
-                return bn == 128 ? launch_halo_emu<128, 3>(a, s) : launch_halo_emu<64, 3>(a, s);
-            }
-        }
-        // ONE LDS buffer per workgroup: the planes take 6 B per element, and with one buffer (two barriers per K-step, the
-        // other resident workgroup fills the gaps) every tile runs faster than double-buffered with fewer workgroups per CU
-        // (total over the decoder layers 134.7 vs 126.6 TFLOP/s-equivalent).  (Forcing a third workgroup per CU with an
-        // 80-VGPR cap on the narrow tiles: same layer rates, whole model 39.7 vs 38.3 ms -- dropped.)
-        if (bn == 128) return bm == 128 ? launch_conv<128, 128, 2, 4, 32, 2>(a, nchw, s, wsf) : launch_conv<64, 128, 2, 4, 32, 2>(a, nchw, s, wsf);
-        if (bn == 64) return bm == 128 ? launch_conv<128, 64, 4, 2, 32, 2>(a, nchw, s, wsf) : launch_conv<64, 64, 2, 2, 32, 2>(a, nchw, s, wsf);
-        return launch_conv<128, 32, 4, 1, 32, 2>(a, nchw, s, wsf);
-    }
+    if (r.prec == 1) return conv_choose_bf16<1>(a, r, bm, bn);
     // the encoder stem (7x7 / stride 2 on the 3-channel image): its own kernel (conv_stem.inc), in fp32 under precision 2 too
-    if (stem_eligible(a, nchw, prec)) return a.c_out == 96 ? launch_stem<96>(a, s) : launch_stem<64>(a, s);
-    if (prec == 2) {
-        // bf16 operands: never Winograd (its transformed operands would not be the rounded ones), never the fp32 wide 1x1
-        if (bn == 48) bn = 64;                       // no 48-wide bf16 tile: pad DenseNet's growth convs to 64, as precision 1
-        // stride-1 3x3 / sub-pixel 2x2 on maps that tile well, pre-rounded weights: the one-plane halo tile (conv_halo_emu.inc)
-        if ((bn == 128 || bn == 64) && halo_emu_eligible(a, nchw)) {
-            const long halo_wgs = (long)a.fill_frames * tiles_4x32(a.H, a.W) * ((a.c_out + bn - 1) / bn) * a.n_classes;
-            if (geometry_kernel_ok(a, bn, wsf, halo_wgs)) {
-                if (a.subpix) return bn == 128 ? launch_halo_emu<128, 2, 1>(a, s) : launch_halo_emu<64, 2, 1>(a, s);
-                return bn == 128 ? launch_halo_emu<128, 3, 1>(a, s) : launch_halo_emu<64, 3, 1>(a, s);
-            }
-        }
-        // everything else (1x1, strided, dilated, bundles, split-K, NCHW output, residual): the row-tiled kernel, which
-        // rounds the fp32 weights itself on the way to LDS (the same rounding as the pre-rounded plane)
-        if (bn == 128) return bm == 128 ? launch_conv<128, 128, 2, 4, 32, 3>(a, nchw, s, wsf) : launch_conv<64, 128, 2, 4, 32, 3>(a, nchw, s, wsf);
-        if (bn == 64) return bm == 128 ? launch_conv<128, 64, 4, 2, 32, 3>(a, nchw, s, wsf) : launch_conv<64, 64, 2, 2, 32, 3>(a, nchw, s, wsf);
-        return launch_conv<128, 32, 4, 1, 32, 3>(a, nchw, s, wsf);
-    }
+    if (stem_eligible(a, nchw, r.prec)) return a.c_out == 96 ? launch_stem<96>(a, r) : launch_stem<64>(a, r);
+    if (r.prec == 2) return conv_choose_bf16<2>(a, r, bm, bn);
     // plain 1x1 convolutions with a 192-multiple output: one workgroup per 128 (or 64) pixels x 192 channels (conv_1x1.inc).
     // Layers that will really split K stay on the row-tiled kernel whatever the declared launch (conv1x1_eligible already
     // asks for a chip-filling one).
@@ -1141,14 +1140,14 @@ int conv_dispatch(const bts_conv_desc* d, bts_stream_t stream, bool even_ok) {
         // of LDS: two workgroups per CU) overlaps them; from ~24 K-steps on the fatter tile's lower staging-per-MFMA wins
         // (measured at B=16: block 2, K 192..720: 2.62 -> 2.33 ms with 64 rows; block 3, K 384..2064: 4.86 ms with 128 rows,
         // 5.06 with 64)
-        return a.c_in_ld <= 768 ? launch_conv1x1<192, 2, true>(a, s) : launch_conv1x1<192>(a, s);
+        return a.c_in_ld <= 768 ? launch_conv1x1<192, 2, true>(a, r) : launch_conv1x1<192>(a, r);
     }
     // fused Winograd F(2x2,3x3) (conv_wino.inc); its workgroup count is taken over 128-wide channel tiles whatever bn is
     if (knobs().wino && ((bn == 128 && a.c_out_pad % 128 == 0) || (bn == 64 && a.c_out_pad % 64 == 0) || (bn == 48 && a.c_out % 48 == 0)) &&
         wino_eligible(a, nchw)) {
         const long wgs = (long)a.fill_frames * ((a.H + 7) / 8) * ((a.W + 15) / 16) * ((a.c_out + 127) / 128);
         if (geometry_kernel_ok(a, bn, wsf, wgs))
-            return bn == 128 ? launch_wino<128>(a, s) : (bn == 64 ? launch_wino<64>(a, s) : launch_wino<48>(a, s));
+            return bn == 128 ? launch_wino<128>(a, r) : (bn == 64 ? launch_wino<64>(a, r) : launch_wino<48>(a, r));
     }
     // stride-1 3x3 (and sub-pixel 2x2) convolutions on maps that tile well: the halo-tile kernel (conv_halo.inc).  The
     // 128- and 32-wide tiles keep one weight buffer: two / three workgroups per CU instead of one / two.
@@ -1156,57 +1155,67 @@ int conv_dispatch(const bts_conv_desc* d, bts_stream_t stream, bool even_ok) {
     const long halo_wgs = (long)a.fill_frames * ((a.H + 128 / mf - 1) / (128 / mf)) * ((a.W + mf - 1) / mf) * ((a.c_out + bn - 1) / bn) * a.n_classes;
     if (geometry_kernel_ok(a, bn, wsf, halo_wgs) && halo_eligible(a, true, mf, nullptr)) {
         if (a.subpix) {
-            if (bn == 128) return launch_halo<128, 4, 2, 32, 2, false, true>(a, nchw, s);
-            if (bn == 64) return launch_halo<64, 4, 2, 32, 2>(a, nchw, s);
-            if (bn == 32) return launch_halo<32, 4, 1, 32, 2, false, true>(a, nchw, s);
+            if (bn == 128) return launch_halo<128, 4, 2, 32, 2, false, true>(a, r);
+            if (bn == 64) return launch_halo<64, 4, 2, 32, 2>(a, r);
+            if (bn == 32) return launch_halo<32, 4, 1, 32, 2, false, true>(a, r);
         } else if (a.dil != 1) {
             // dilated halo tiles (ASPP branches, c_out 128): one eight-wave workgroup per CU, single weight buffer
             if (bn == 128 && !nchw) {
-                if (a.dil == 3) return launch_halo<128, 4, 2, 32, 3, false, true, 3>(a, nchw, s);
-                if (a.dil == 6) return launch_halo<128, 4, 2, 32, 3, false, true, 6>(a, nchw, s);
-                if (a.dil == 12) return launch_halo<128, 4, 2, 32, 3, false, true, 12>(a, nchw, s);
+                if (a.dil == 3) return launch_halo<128, 4, 2, 32, 3, false, true, 3>(a, r);
+                if (a.dil == 6) return launch_halo<128, 4, 2, 32, 3, false, true, 6>(a, r);
+                if (a.dil == 12) return launch_halo<128, 4, 2, 32, 3, false, true, 12>(a, r);
             }
         } else {
-            if (bn == 128) return launch_halo<128, 4, 2, 32, 3, false, true>(a, nchw, s);
-            if (bn == 64) return launch_halo<64, 4, 2, 32, 3>(a, nchw, s);
-            if (bn == 32) return launch_halo<32, 4, 1, 32, 3, false, true>(a, nchw, s);
+            if (bn == 128) return launch_halo<128, 4, 2, 32, 3, false, true>(a, r);
+            if (bn == 64) return launch_halo<64, 4, 2, 32, 3>(a, r);
+            if (bn == 32) return launch_halo<32, 4, 1, 32, 3, false, true>(a, r);
             // eight waves per workgroup (one 16-pixel row each): 16 instead of 8 waves per CU at two workgroups per CU.  Worth
             // -10 % over four where the launch is under-filled (DenseNet block 3: 240 workgroups at fill_frames 16) and -2 %
             // on the chip-filling block 1 / 2 launches
-            if (bn == 48) return launch_halo<48, 8, 1, 16, 3>(a, nchw, s);
+            if (bn == 48) return launch_halo<48, 8, 1, 16, 3>(a, r);
         }
     }
-    if (bn == 48) return bm == 128 ? launch_conv<128, 48, 4, 1, 16>(a, nchw, s, wsf) : launch_conv<64, 48, 4, 1, 16>(a, nchw, s, wsf);
+    if (bn == 48) return bm == 128 ? launch_conv<128, 48, 4, 1, 16>(a, r) : launch_conv<64, 48, 4, 1, 16>(a, r);
     // 8-wave workgroups (two waves per SIMD from the same tile) for the 128-row tiles and the 64x128 tile: +2 % end to end
     // over the 4-wave layout on MI355X (more waves to cover each other's staging)
-    if (bn == 128) return bm == 128 ? launch_conv<128, 128, 2, 4>(a, nchw, s, wsf) : launch_conv<64, 128, 2, 4>(a, nchw, s, wsf);
-    if (bn == 64) return bm == 128 ? launch_conv<128, 64, 4, 2>(a, nchw, s, wsf) : launch_conv<64, 64, 2, 2>(a, nchw, s, wsf);
-    return launch_conv<128, 32, 4, 1>(a, nchw, s, wsf);
+    if (bn == 128) return bm == 128 ? launch_conv<128, 128, 2, 4>(a, r) : launch_conv<64, 128, 2, 4>(a, r);
+    if (bn == 64) return bm == 128 ? launch_conv<128, 64, 4, 2>(a, r) : launch_conv<64, 64, 2, 2>(a, r);
+    return launch_conv<128, 32, 4, 1>(a, r);
+}
+
+// Descriptor -> arguments -> kernel choice -> launch on `stream`; with `plan` the same walk ends in *plan and no HIP call.
+int conv_dispatch(const bts_conv_desc* d, bts_stream_t stream, bool even_ok = false, ConvChoice* plan = nullptr) {
+    ConvArgs a{};
+    ConvRun r{(hipStream_t)stream, plan, false, 0, 0};
+    if (const int rc = conv_args(d, even_ok, a, r); rc != 0) return rc;
+    return conv_choose(a, r);
+}
+
+// The plan queries' shared end: what conv_dispatch would launch for `d`, with the split-K flag on the kind.  A rejected
+// descriptor leaves the row kernel's kind and a 0 x 0 tile behind its error code.
+int conv_plan(const bts_conv_desc* d, bool even_ok, ConvChoice& c) {
+    c = ConvChoice{BTS_CONV_KIND_ROW, 0, 0, 1};
+    const int rc = conv_dispatch(d, nullptr, even_ok, &c);
+    if (c.ksplit > 1) c.kind |= BTS_CONV_FLAG_SPLITK;
+    return rc;
 }
 
 }  // namespace
 
-// The real decision path with g_dry set: launch_* fill `c` instead of launching.
-static int conv_dry_run(const bts_conv_desc* d, ConvChoice& c) {
-    c = ConvChoice{BTS_CONV_KIND_ROW, 0, 0, 1};
-    g_dry = &c;
-    const int rc = conv_dispatch(d, nullptr);
-    g_dry = nullptr;
-    return rc;
-}
+extern "C" int bts_conv_fwd_f32(const bts_conv_desc* d, bts_stream_t stream) { return conv_dispatch(d, stream); }
 
 extern "C" int bts_conv_plan_f32(const bts_conv_desc* d, int* bm, int* bn, int* kind) {
     if (!d || !bm || !bn || !kind) return BTS_ERR_INVALID;
     ConvChoice c;
-    const int rc = conv_dry_run(d, c);
-    *bm = c.bm; *bn = c.bn; *kind = c.kind | (c.ksplit > 1 ? BTS_CONV_FLAG_SPLITK : 0);
+    const int rc = conv_plan(d, false, c);
+    *bm = c.bm; *bn = c.bn; *kind = c.kind;
     return rc;
 }
 
 extern "C" int bts_conv_plan_ksteps_f32(const bts_conv_desc* d, long* issued, long* dense) {
     if (!d || !issued || !dense) return BTS_ERR_INVALID;
     ConvChoice c;
-    const int rc = conv_dry_run(d, c);
+    const int rc = conv_plan(d, false, c);
     *issued = c.ksteps_issued; *dense = c.ksteps_dense;      // both 0 for the kernel families that never skip
     return rc;
 }
@@ -1242,10 +1251,8 @@ extern "C" int bts_upconv_up9_fwd_f32(const float* x, long x_pix_stride, int B, 
     up9_grid(h, w, &a.n_ty, &a.n_tx, &fill);
     a.n_ntiles = c_out / 32;
     const long nwg = (long)B * a.n_ty * a.n_tx * a.n_ntiles;
-    if (nwg > 0x7fffffffL) return BTS_ERR_UNSUPPORTED;
     a.ntiles = (int)nwg;
-    hipLaunchKernelGGL(conv_up9_kernel<32>, dim3((unsigned)nwg), dim3(256), 0, (hipStream_t)stream, a);
-    return (int)hipGetLastError();
+    return conv_launch<conv_up9_kernel<32>>(launch_on(stream), ConvChoice{}, BTS_ERR_UNSUPPORTED, nwg, nwg, 256, 0, a);
 }
 
 // ---- planar-tail 3x3 convolution with bf16 main operands (conv_tail_bf16.inc): its own opt-in entry point and plan query,
@@ -1280,7 +1287,7 @@ extern "C" int bts_conv_tail_bf16_fwd_f32(const float* x, long x_pix_stride, int
     a.w_main = static_cast<const unsigned short*>(w_main); a.w_tail = w_tail; a.tail = tail_plane;
     a.c_out = c_out; a.c_out_pad = c_out_pad; a.e2_scale = e2_scale; a.e2_shift = e2_shift; a.act = act;
     a.y = y; a.y_pix_stride = y_pix_stride; a.n_ntiles = 0;
-    return tail_bf16_bn(c_out) == 128 ? launch_tail_bf16<128>(a, (hipStream_t)stream) : launch_tail_bf16<64>(a, (hipStream_t)stream);
+    return tail_bf16_bn(c_out) == 128 ? launch_tail_bf16<128>(a, launch_on(stream)) : launch_tail_bf16<64>(a, launch_on(stream));
 }
 
 // ---- conv1 (32 features + planar tail -> 32, NCHW) as a fused Winograd F(2x2,3x3) kernel (conv_wino_tail.inc): its own opt-in
@@ -1314,10 +1321,8 @@ extern "C" int bts_conv_tail_wino_fwd_f32(const float* x, long x_pix_stride, int
     double fill;
     wino_tail_grid(h, w, &a.n_ty, &a.n_tx, &fill);
     const long nwg = (long)B * a.n_ty * a.n_tx;
-    if (nwg > 0x7fffffffL) return BTS_ERR_UNSUPPORTED;
     a.ntiles = (int)nwg;
-    hipLaunchKernelGGL(conv_wino_tail_kernel<32>, dim3((unsigned)nwg), dim3(256), 0, (hipStream_t)stream, a);
-    return (int)hipGetLastError();
+    return conv_launch<conv_wino_tail_kernel<32>>(launch_on(stream), ConvChoice{}, BTS_ERR_UNSUPPORTED, nwg, nwg, 256, 0, a);
 }
 
 // ---- ResNeXt's grouped 3x3 on the multi-block fp32 MFMA (conv_grouped.inc): its own opt-in entry point and plan query, so
@@ -1355,10 +1360,11 @@ extern "C" int bts_conv_grouped_fwd_f32(const float* x, long x_pix_stride, int B
     const long chunks = tiles < (GR_RESIDENT + slabs - 1) / slabs ? tiles : (GR_RESIDENT + slabs - 1) / slabs;
     const dim3 grid((unsigned)chunks, (unsigned)slabs);
     const int cg = c / groups;
-    if (cg == 16) hipLaunchKernelGGL(conv_grouped_kernel<16>, grid, dim3(256), 0, (hipStream_t)stream, a);
-    else if (cg == 8) hipLaunchKernelGGL(conv_grouped_kernel<8>, grid, dim3(256), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(conv_grouped_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, a);
-    return (int)hipGetLastError();
+    hipStream_t s = (hipStream_t)stream;
+    const int rc = cg == 16 ? bts_launch<conv_grouped_kernel<16>>(grid, dim3(256), 0, s, a)
+                 : cg == 8  ? bts_launch<conv_grouped_kernel<8>>(grid, dim3(256), 0, s, a)
+                            : bts_launch<conv_grouped_kernel<4>>(grid, dim3(256), 0, s, a);
+    return rc != 0 ? rc : (int)hipGetLastError();
 }
 
 // ---- its weight gradient (conv_grouped_wgrad.inc): the shapes of the forward, the same 32-bit index guards
@@ -1398,15 +1404,15 @@ extern "C" int bts_conv_grouped_wgrad_f32(const float* x, long x_pix_stride, con
     hipStream_t s = (hipStream_t)stream;
     auto run = [&](auto tag) {
         constexpr int CG = decltype(tag)::value;
-        hipLaunchKernelGGL(conv_grouped_wgrad_kernel<CG>, grid, dim3(256), 0, s, a);
+        if (const int rc = bts_launch<conv_grouped_wgrad_kernel<CG>>(grid, dim3(256), 0, s, a); rc != 0) return rc;
         if (!a.direct)
             hipLaunchKernelGGL(conv_grouped_wgrad_reduce_kernel<CG>, dim3((unsigned)red_blocks), dim3(256), 0, s, (const float*)ws, dw,
                                c, (int)p.splits);
+        return (int)hipGetLastError();
     };
-    if (cg == 16) run(std::integral_constant<int, 16>{});
-    else if (cg == 8) run(std::integral_constant<int, 8>{});
-    else run(std::integral_constant<int, 4>{});
-    return (int)hipGetLastError();
+    if (cg == 16) return run(std::integral_constant<int, 16>{});
+    if (cg == 8) return run(std::integral_constant<int, 8>{});
+    return run(std::integral_constant<int, 4>{});
 }
 
 // ---- input gradient of the sub-pixel upconv (training): one 4x4 / stride-2 / padding-1 convolution over dy at its natural
@@ -1454,10 +1460,8 @@ extern "C" int bts_upconv_dgrad_plan(int B, int h, int w, int c_out, int c_in, i
     float* dummy = (float*)(uintptr_t)(1 << 20);       // pointers are checked, never followed
     if (const int rc = upconv_dgrad_desc(dummy, c_out, B, h, w, c_out, dummy, c_in, dummy, c_in, precision, fill_frames,
                                          splitk_ws_floats > 0 ? dummy : nullptr, splitk_ws_floats, d); rc != 0) return rc;
-    ConvChoice c{BTS_CONV_KIND_ROW, 0, 0, 1};
-    g_dry = &c;
-    const int rc = conv_dispatch(&d, nullptr, true);
-    g_dry = nullptr;
-    *bm = c.bm; *bn = c.bn; *kind = c.kind | (c.ksplit > 1 ? BTS_CONV_FLAG_SPLITK : 0);
+    ConvChoice c;
+    const int rc = conv_plan(&d, true, c);
+    *bm = c.bm; *bn = c.bn; *kind = c.kind;
     return rc;
 }

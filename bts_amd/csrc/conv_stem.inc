@@ -141,18 +141,13 @@ inline bool stem_eligible(const ConvArgs& a, bool nchw, int prec) {
 }
 
 template <int BN>
-int launch_stem(const ConvArgs& a0, hipStream_t s) {
+int launch_stem(const ConvArgs& a0, const ConvRun& r) {
     ConvArgs a = a0;
     const int n_ty = (a.H + 7) / 8, n_tx = (a.W + 31) / 32;
     const long n_tiles = (long)a.B * n_ty * n_tx;
-    if (n_tiles > 0x7fffffffL) return BTS_ERR_INVALID;
     a.n_ntiles = 1; a.tiles_per_class = (int)n_tiles; a.ksplit = 1;
-    if (g_dry) { *g_dry = ConvChoice{BTS_CONV_KIND_STEM, 256, BN, 1}; return 0; }
     const size_t lds = (size_t)(BN * 228 + 2 * 21 * 320) * sizeof(float);
-    auto k = conv_stem_kernel<BN>;
-    static std::atomic<unsigned long long> lds_set{0};
-    if (hipError_t e = bts_ensure_dynamic_lds((const void*)k, lds, lds_set); e != hipSuccess) return (int)e;
     const long nwg = n_tiles < 256 ? n_tiles : 256;            // persistent: one workgroup per CU of the MI355X (141 KB of LDS each)
-    hipLaunchKernelGGL(k, dim3((unsigned)nwg), dim3(512), lds, s, a, n_ty, n_tx, (int)n_tiles);
-    return (int)hipGetLastError();
+    return conv_launch<conv_stem_kernel<BN>>(r, ConvChoice{BTS_CONV_KIND_STEM, 256, BN, 1}, BTS_ERR_INVALID, n_tiles, nwg, 512, lds,
+                                             a, n_ty, n_tx, (int)n_tiles);
 }

@@ -175,16 +175,11 @@ inline bool tail_bf16_eligible(int H, int W, int c_main, int c_out, int n_tail, 
 }
 
 template <int BN>
-int launch_tail_bf16(TailBf16Args a, hipStream_t s) {
+int launch_tail_bf16(TailBf16Args a, const ConvRun& r) {
     const long n_mtiles = (long)a.B * tiles_4x32(a.H, a.W);
     a.n_ntiles = (a.c_out + BN - 1) / BN;
     const long nwg = n_mtiles * a.n_ntiles;
-    if (nwg > 0x7fffffffL) return BTS_ERR_UNSUPPORTED;
     constexpr size_t lds = (size_t)tail_bf16_lds_bytes<BN>();
     static_assert(lds <= 80 * 1024, "two workgroups per CU");
-    auto k = conv_tail_bf16_kernel<BN>;
-    static std::atomic<unsigned long long> lds_set{0};
-    if (hipError_t e = bts_ensure_dynamic_lds((const void*)k, lds, lds_set); e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(k, dim3((unsigned)nwg), dim3(512), lds, s, a);
-    return (int)hipGetLastError();
+    return conv_launch<conv_tail_bf16_kernel<BN>>(r, ConvChoice{}, BTS_ERR_UNSUPPORTED, nwg, nwg, 512, lds, a);
 }

@@ -437,25 +437,19 @@ inline bool wino_eligible(const ConvArgs& a, bool nchw) {
 }
 
 template <int BN, bool TAIL = false>
-int launch_wino(const ConvArgs& a0, hipStream_t s) {
+int launch_wino(const ConvArgs& a0, const ConvRun& r) {
     ConvArgs a = a0;
     const long n_mtiles = (long)a.B * ((a.H + 7) / 8) * ((a.W + 15) / 16);
     a.n_ntiles = (a.c_out + BN - 1) / BN;
     a.tiles_per_class = (int)(n_mtiles * a.n_ntiles);
     a.ksplit = 1;
     const long nwg = n_mtiles * a.n_ntiles;
-    if (nwg > 0x7fffffffL) return BTS_ERR_INVALID;
-    if (g_dry) { *g_dry = ConvChoice{BTS_CONV_KIND_WINO, 128, BN, 1}; return 0; }
     constexpr size_t lds = (size_t)wino_lds_bytes<BN, TAIL>();
     static_assert(lds <= 160 * 1024, "LDS");
-    auto k = conv_wino_kernel<BN, TAIL>;
-    static std::atomic<unsigned long long> lds_set{0};
-    if (hipError_t e = bts_ensure_dynamic_lds((const void*)k, lds, lds_set); e != hipSuccess) return (int)e;
     // persistent grid: R = tiles per workgroup when 256 CUs share them; every workgroup gets R tiles (some R - 1), and a launch
     // that cannot fill the chip leaves whole CUs to the other streams instead of a ragged last round
     const long R = (nwg + 255) / 256;
     long G = ((nwg + R - 1) / R + 7) & ~7L;                        // multiple of 8: a workgroup's tiles stay on its XCD's slice of the swizzle
     if (G > nwg) G = nwg;
-    hipLaunchKernelGGL(k, dim3((unsigned)G), dim3(512), lds, s, a);
-    return (int)hipGetLastError();
+    return conv_launch<conv_wino_kernel<BN, TAIL>>(r, ConvChoice{BTS_CONV_KIND_WINO, 128, BN, 1}, BTS_ERR_INVALID, nwg, G, 512, lds, a);
 }

@@ -177,15 +177,13 @@ int launch_reduc(const float* x, long stride, long npix, const float* w_frag, lo
     constexpr long NW = chain_frag_float4s<C0, M0>();
     if (w_frag_floats != NW * 4) return BTS_ERR_INVALID;
     const size_t lds = (size_t)NW * 16;
-    auto kern = reduc_fwd_kernel<C0, M0, FINAL, LPGK>;
-    static std::atomic<unsigned long long> lds_set{0};     // per instantiation: one bit per device (common.h)
-    if (hipError_t e = bts_ensure_dynamic_lds((const void*)kern, lds, lds_set); e != hipSuccess) return (int)e;
     const long ntiles = (npix + 31) / 32;
     const int per_cu = lds > 80 * 1024 ? 1 : 2;
     long blocks = (ntiles + 7) / 8;
     if (blocks > 256L * per_cu) blocks = 256L * per_cu;
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(512), lds, s, x, stride, npix,
-                       reinterpret_cast<const float4*>(w_frag), max_depth, normalize, out, lt);
+    if (const int rc = bts_launch<reduc_fwd_kernel<C0, M0, FINAL, LPGK>>(dim3((unsigned)blocks), dim3(512), lds, s, x, stride, npix,
+                                                                         reinterpret_cast<const float4*>(w_frag), max_depth,
+                                                                         normalize, out, lt); rc != 0) return rc;
     return (int)hipGetLastError();
 }
 

@@ -259,15 +259,12 @@ int launch_reduc_bwd(const float* x, long stride, long npix, int ch, int cw, con
                      long dx_stride, float* G, float* Y, hipStream_t s) {
     using S = ChainSizes<C0, M0>;
     if (w_frag_floats != S::NWF * 4 || wt_frag_floats != S::NWT * 4) return BTS_ERR_INVALID;
-    auto kern = reduc_bwd_kernel<C0, M0, FINAL, LPGK>;
-    static std::atomic<unsigned long long> lds_set{0};     // per instantiation: one bit per device (common.h)
-    if (hipError_t e = bts_ensure_dynamic_lds((const void*)kern, S::LDS, lds_set); e != hipSuccess) return (int)e;
     const long ntiles = (npix + 31) / 32;
     long blocks = (ntiles + 7) / 8;
     if (blocks > S::MAX_BLOCKS) blocks = S::MAX_BLOCKS;
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(512), S::LDS, s, x, stride, npix,
-                       reinterpret_cast<const float4*>(w_frag), reinterpret_cast<const float4*>(wt_frag), max_depth, ch, cw,
-                       gout, dx, dx_stride, G, Y);
+    if (const int rc = bts_launch<reduc_bwd_kernel<C0, M0, FINAL, LPGK>>(
+            dim3((unsigned)blocks), dim3(512), S::LDS, s, x, stride, npix, reinterpret_cast<const float4*>(w_frag),
+            reinterpret_cast<const float4*>(wt_frag), max_depth, ch, cw, gout, dx, dx_stride, G, Y); rc != 0) return rc;
     return (int)hipGetLastError();
 }
 

@@ -424,11 +424,7 @@ template <typename T> long wgrad_tile_grid(WgradGeom& g) {
 // Enqueue a wgrad_tile kernel of tile T: its LDS (two stages of both operands), raised above the default where needed.
 // Returns that step's error, or 0 with the kernel enqueued; the caller reads hipGetLastError after its last launch.
 template <typename T, auto Kern, typename... Args> int launch_wgrad_tiles(dim3 grid, hipStream_t s, Args... args) {
-    constexpr size_t lds_bytes = (size_t)2 * WBK * (T::BM + T::BN) * sizeof(float);
-    static std::atomic<unsigned long long> lds_set{0};     // per instantiation: one bit per device (common.h)
-    if (hipError_t e = bts_ensure_dynamic_lds((const void*)Kern, lds_bytes, lds_set); e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(Kern, grid, dim3(256), lds_bytes, s, args...);
-    return 0;
+    return bts_launch<Kern>(grid, dim3(256), (size_t)2 * WBK * (T::BM + T::BN) * sizeof(float), s, args...);
 }
 
 // `a` and `split` come from prepare_wgrad: a.g.pix_per_split and the split count are final here.
