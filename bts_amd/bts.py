@@ -727,6 +727,11 @@ class BtsModel(nn.Module):
                                             # "bf16" / "bf16x3" stay on bundles in every mode; the training graph has its own
                                             # switch (grouped_conv_train).  A plan
                                             # cannot replay the native launch: with use_plans the forward raises BtsHipError
+        self.bf16_wide_1x1 = False          # DenseNet161's bottleneck 1x1 layers (eval forward, conv_precision "bf16" only): True runs
+                                            # the ones ops.conv1x1_bf16_plan accepts on the wide bf16 tile
+                                            # (ops.conv1x1_bf16_forward); nothing changes under "fp32" / "bf16x3", for
+                                            # transitions, ASPP, ResNe(X)t or DenseNet121.  A plan cannot replay the launch: with
+                                            # use_plans the bf16 forward raises BtsHipError
         self._plans = PlanCache()
         self._fp_state = [0, None, -1]      # workspace.tensor_fingerprint: [structure token, cached tensor list, its token]
         self._origin = [self]               # reaches DataParallel replicas through replicate()'s shallow __dict__ copy
@@ -786,6 +791,10 @@ class BtsModel(nn.Module):
 
     def _forward_native(self, x, focal, slot, outs=None, abs_mins=None):
         if self.use_plans and ops._trace is None and not _lib_mod.is_recording():
+            if (self.bf16_wide_1x1 and ops.current_launch_config()[1] == 2
+                    and not isinstance(self.encoder.base_model, encoders.ResNet)):
+                raise BtsHipError("BtsModel: bf16_wide_1x1 launches bts_conv1x1_bf16_fwd_f32, which a plan cannot replay; "
+                                  "set use_plans = False or bf16_wide_1x1 = False")
             r = self._plans.forward(self, x, focal, slot, outs)
             if abs_mins is not None:
                 dec = self.decoder
@@ -806,6 +815,8 @@ class BtsModel(nn.Module):
         plan.bind(base, key_module=src_base)
         if cls is ResNetHip:
             plan.grouped_conv = self.grouped_conv
+        else:
+            plan.bf16_wide_1x1 = bool(self.bf16_wide_1x1)
         plan._ws.max_entries = max(plan._ws.max_entries, 2 * int(self.sub_batches))
         B, _, H, W = x.shape
         dec = self.decoder

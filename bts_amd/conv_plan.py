@@ -70,6 +70,11 @@ def tail_bf16_kernel_name(bn: int) -> str:
     return "conv_tail_bf16_kernel<%d>" % bn
 
 
+def wide_1x1_bf16_kernel_name(bn: int = 192) -> str:
+    """The kernel bts_conv1x1_bf16_fwd_f32 launches (its own entry point: no bts_conv_plan_f32 kind), as KernelTrace records it."""
+    return "conv1x1_bf16_kernel<%d>" % bn
+
+
 def grouped_kernel_name(cg: int) -> str:
     """The kernel bts_conv_grouped_fwd_f32 launches for ``cg`` channels per group (its own entry point: no bts_conv_plan_f32
     kind), as KernelTrace records it."""

@@ -851,6 +851,7 @@ int conv_launch(const ConvRun& r, const ConvChoice& choice, int too_many, long t
 #include "conv_grouped.inc"
 #include "conv_grouped_wgrad.inc"
 #include "conv_tail_bf16.inc"
+#include "conv_1x1_bf16.inc"
 #include "conv_1x1.inc"
 #include "conv_stem.inc"
 
@@ -1288,6 +1289,39 @@ extern "C" int bts_conv_tail_bf16_fwd_f32(const float* x, long x_pix_stride, int
     a.c_out = c_out; a.c_out_pad = c_out_pad; a.e2_scale = e2_scale; a.e2_shift = e2_shift; a.act = act;
     a.y = y; a.y_pix_stride = y_pix_stride; a.n_ntiles = 0;
     return tail_bf16_bn(c_out) == 128 ? launch_tail_bf16<128>(a, launch_on(stream)) : launch_tail_bf16<64>(a, launch_on(stream));
+}
+
+// ---- wide 1x1 convolution with bf16 operands (conv_1x1_bf16.inc: DenseNet161's bottlenecks under precision 2): its own opt-in
+//      entry point and plan query, so that bts_conv_fwd_f32 / bts_conv_plan_f32 answer for every descriptor exactly as before
+extern "C" int bts_conv1x1_bf16_plan(int h, int w, int c_in, int c_out, int fill_frames, int* bm, int* bn, long* workgroups) {
+    int ff, prec;                                           // the arithmetic is this entry point's own: no precision argument
+    if (!bm || !bn || !workgroups || !resolve_declaration(fill_frames, 0, &ff, &prec)) return BTS_ERR_INVALID;
+    long wgs = 0;
+    const bool ok = c1b_eligible(h, w, c_in, c_out, ff, &wgs);
+    *bm = ok ? C1B_BM : 0; *bn = ok ? 192 : 0; *workgroups = ok ? wgs : 0;
+    return 0;
+}
+
+extern "C" int bts_conv1x1_bf16_fwd_f32(const float* x, long x_pix_stride, long npix, int c_in, const void* w_bf16, int k_pad,
+                                        int c_out, int c_out_pad, const float* pre_scale, const float* pre_shift, int pre_relu,
+                                        const float* e1_scale, const float* e1_shift, int act, float* y, long y_pix_stride,
+                                        bts_stream_t stream) {
+    if (!x || !w_bf16 || !y || npix <= 0 || c_in <= 0 || c_out <= 0 || k_pad <= 0 || c_out_pad < c_out) return BTS_ERR_INVALID;
+    if ((pre_scale == nullptr) != (pre_shift == nullptr) || !act_e2_ok(act, e1_scale, e1_shift)) return BTS_ERR_INVALID;
+    if (!nhwc_view_ok(x, x_pix_stride, c_in) || (y_pix_stride & 3) || y_pix_stride < c_out || ((uintptr_t)y & 3) ||
+        ((uintptr_t)w_bf16 & 15) || ((uintptr_t)pre_scale & 3) || ((uintptr_t)pre_shift & 3) || ((uintptr_t)e1_scale & 3) ||
+        ((uintptr_t)e1_shift & 3)) return BTS_ERR_INVALID;
+    if (!c1b_supported(c_in, c_out) || (k_pad % BK) || k_pad < c_in) return BTS_ERR_UNSUPPORTED;
+    // pixel rows are addressed in 64 bits; the kernel adds 32-bit offsets inside a 32-pixel row block and inside the weight
+    // plane, and keeps the prologue vectors of all c_in channels in LDS (more workgroups than a grid holds: conv_launch)
+    if (x_pix_stride >= (1L << 26) || y_pix_stride >= (1L << 26) || !fits_u32((double)c_out_pad * (double)k_pad) ||
+        c1b_lds_bytes<192>(c_in, true) > 160 * 1024) return BTS_ERR_UNSUPPORTED;
+    Conv1x1Bf16Args a;
+    a.x = x; a.x_pix_stride = x_pix_stride; a.npix = npix; a.c_in = c_in;
+    a.w = static_cast<const unsigned short*>(w_bf16); a.k_pad = k_pad; a.c_out = c_out; a.c_out_pad = c_out_pad;
+    a.pre_scale = pre_scale; a.pre_shift = pre_shift; a.pre_relu = pre_relu;
+    a.e1_scale = e1_scale; a.e1_shift = e1_shift; a.act = act; a.y = y; a.y_pix_stride = y_pix_stride; a.n_ntiles = 0;
+    return launch_conv1x1_bf16<192>(a, launch_on(stream));
 }
 
 // ---- conv1 (32 features + planar tail -> 32, NCHW) as a fused Winograd F(2x2,3x3) kernel (conv_wino_tail.inc): its own opt-in

@@ -391,6 +391,49 @@ void conv_tail_bf16(const Tensor& x, const Tensor& w_main, const Tensor& w_tail,
                                         current_stream()), op);
 }
 
+// ------------------------------------------------------------------------------- wide 1x1, bf16 operands (c_out % 192 == 0)
+// act(e1(conv1x1(bf16(pre(x))))) as one launch of the wide bf16 tile (bts_conv1x1_bf16_fwd_f32).  x: [npix, >= c_in] NHWC
+// view; w_plane: the one-plane bf16 form of the packed weight, [c_out_pad, k_pad] or [1, c_out_pad, k_pad], int16 bits
+// (ops.round_bf16) or bfloat16; y: [npix, c_out] NHWC view.  geom = {npix, c_in, c_out, pre_relu, act}.
+void conv1x1_bf16(const Tensor& x, const Tensor& w_plane, OptTensor pre_scale, OptTensor pre_shift, OptTensor e1_scale, OptTensor e1_shift,
+                  Tensor y, std::vector<int64_t> geom) {
+    const char* op = "bts_hip::conv1x1_bf16";
+    TORCH_CHECK(geom.size() == 5, op, ": geom must hold 5 integers, got ", geom.size());
+    const int64_t npix = geom[0], c_in = geom[1], c_out = geom[2], pre_relu = geom[3], act = geom[4];
+    TORCH_CHECK(npix > 0 && c_in > 0 && c_out > 0, op, ": non-positive dimension");
+    TORCH_CHECK(c_in % 16 == 0 && c_out % 192 == 0, op, ": needs c_in % 16 == 0 and c_out % 192 == 0, got ", c_in, " -> ", c_out);
+    const long xs = rows2d_stride(x, op, "x"), ys = rows2d_stride(y, op, "y");
+    TORCH_CHECK(w_plane.is_cuda(), op, ": w_plane must be a CUDA(ROCm) tensor (no CPU fallback)");
+    TORCH_CHECK(w_plane.scalar_type() == at::kShort || w_plane.scalar_type() == at::kBFloat16, op,
+                ": w_plane must hold bf16 bits (int16 from ops.round_bf16, or bfloat16), got ", w_plane.scalar_type());
+    same_device(x, w_plane, op, "w_plane");
+    same_device(x, y, op, "y");
+    TORCH_CHECK(x.size(0) == npix && x.size(1) >= c_in, op, ": x (", x.sizes(), ") is not a [npix, >= c_in] view");
+    TORCH_CHECK(y.size(0) == npix && y.size(1) == c_out, op, ": y (", y.sizes(), ") is not a [npix, c_out] view");
+    const int64_t wd = w_plane.dim();
+    TORCH_CHECK(w_plane.is_contiguous() && (wd == 2 || (wd == 3 && w_plane.size(0) == 1)), op,
+                ": w_plane must be contiguous [c_out_pad, k_pad] or [1, c_out_pad, k_pad] (ops.round_bf16), got ", w_plane.sizes());
+    const int64_t c_out_pad = w_plane.size(wd - 2), k_pad = w_plane.size(wd - 1);
+    TORCH_CHECK(c_out_pad >= c_out && k_pad >= c_in && k_pad % 32 == 0, op, ": w_plane ", w_plane.sizes(), " does not hold ", c_out, " rows of ",
+                c_in, " channels padded to a multiple of 32");
+    TORCH_CHECK(act >= 0 && act <= 2, op, ": act must be 0 (none), 1 (ReLU) or 2 (ELU), got ", act);
+    auto vec = [&](const OptTensor& t, const char* what, int64_t n) -> const float* {
+        if (!(t.has_value() && t->defined())) return nullptr;
+        need_f32_cuda(*t, op, what);
+        same_device(x, *t, op, what);
+        TORCH_CHECK(t->is_contiguous() && t->numel() >= n, op, ": ", what, " must be a contiguous vector of at least ", n, " floats");
+        return t->data_ptr<float>();
+    };
+    const float* ps = vec(pre_scale, "pre_scale", c_in);
+    const float* pb = vec(pre_shift, "pre_shift", c_in);
+    const float* es = vec(e1_scale, "e1_scale", c_out);
+    const float* eb = vec(e1_shift, "e1_shift", c_out);
+    TORCH_CHECK((ps == nullptr) == (pb == nullptr) && (es == nullptr) == (eb == nullptr), op, ": give both vectors of an affine or neither");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+    check_rc(bts_conv1x1_bf16_fwd_f32(x.data_ptr<float>(), xs, (long)npix, (int)c_in, w_plane.data_ptr(), (int)k_pad, (int)c_out, (int)c_out_pad,
+                                      ps, pb, (int)(pre_relu != 0), es, eb, (int)act, y.data_ptr<float>(), ys, current_stream()), op);
+}
+
 // ------------------------------------------------------------------------------------------------------ training losses
 // silog_loss / depth_l1_loss (pytorch/bts.py:41-63) over the valid pixels of the whole batch, csrc/loss.hip: no boolean gather, no host
 // sync.  kind 0 = silog (param = variance_focus), 1 = asymmetric L1 (param = inbalance_to_closer); mask bool / uint8 or None (gt > gt_min).
@@ -462,6 +505,8 @@ TORCH_LIBRARY(bts_hip, m) {
           "Tensor? w_wino, int[] geom) -> ()");
     m.def("upconv_up9(Tensor x, Tensor u, Tensor? e2_scale, Tensor? e2_shift, Tensor(a!) y, int[] geom) -> ()");
     m.def("conv_tail_bf16(Tensor x, Tensor w_main, Tensor w_tail, Tensor tail, Tensor? e2_scale, Tensor? e2_shift, Tensor(a!) y, int[] geom) -> ()");
+    m.def("conv1x1_bf16(Tensor x, Tensor w_plane, Tensor? pre_scale, Tensor? pre_shift, Tensor? e1_scale, Tensor? e1_shift, Tensor(a!) y, "
+          "int[] geom) -> ()");
     m.def("depth_loss(Tensor est, Tensor gt, Tensor? mask, float gt_min, int kind, float param) -> (Tensor loss, Tensor stats)");
     m.def("depth_loss_backward(Tensor est, Tensor gt, Tensor? mask, float gt_min, int kind, float param, Tensor stats, Tensor grad_loss) -> Tensor");
 }
@@ -477,6 +522,7 @@ TORCH_LIBRARY_IMPL(bts_hip, CUDA, m) {
     m.impl("conv_fwd", &conv_fwd);
     m.impl("upconv_up9", &upconv_up9);
     m.impl("conv_tail_bf16", &conv_tail_bf16);
+    m.impl("conv1x1_bf16", &conv1x1_bf16);
     m.impl("depth_loss", &depth_loss);
     m.impl("depth_loss_backward", &depth_loss_backward);
 }

@@ -39,10 +39,16 @@ def _key(module: nn.Module):
 
 
 class DenseNetHip:
-    """Execution plan for ``encoders.densenet_features`` (torchvision ``DenseNet.features``)."""
+    """Execution plan for ``encoders.densenet_features`` (torchvision ``DenseNet.features``).
+
+    ``bf16_wide_1x1`` (BtsModel.bf16_wide_1x1 sets it): True runs the bottleneck 1x1 of every dense layer that
+    ops.conv1x1_bf16_plan accepts on the wide bf16 tile (ops.conv1x1_bf16_forward: 192 output channels per workgroup, the
+    pre-rounded weight plane) -- under the bf16 launch precision only; fp32 / bf16x3 forwards, transitions and bottlenecks of
+    another width (DenseNet121: 128) stay on ops.conv_forward whatever the switch says."""
 
     def __init__(self, features: nn.Sequential, key_module: Optional[nn.Module] = None):
         self.features = features
+        self.bf16_wide_1x1 = False
         self.key_module = key_module if key_module is not None else features   # whose tensors fingerprint the packs
         self._pack = None
         self._pack_key = None
@@ -99,6 +105,18 @@ class DenseNetHip:
         self._pack, self._pack_key = P, key
         return P
 
+    def _round_bottleneck_planes(self, P, device):
+        """The one-plane bf16 form (ops.round_bf16, cached on the packed weight as ``_bts_round1``: the plane conv_forward's
+        own bf16 kernels stream) of every bottleneck 1x1 weight of the pack ``P``: made on the first forward that needs one,
+        all at once, and finished before this returns -- the sub-batches of a BtsModel forward run on several streams, and
+        the others must not read a plane the first is still writing.  (A host synchronise: like every first forward, not
+        something to capture into a hipGraph.)"""
+        for layers in P["blocks"]:
+            for L in layers:
+                ops._derived_weight(L["w1"], "_bts_round1", ops.round_bf16)
+        torch.cuda.current_stream(device).synchronize()
+        P["planes_made"] = True
+
     # ----------------------------------------------------------------------- workspace
     def _workspace(self, B, H, W, device, slot=0):
         return self._ws.get((B, H, W, str(device), slot), lambda: self._alloc_workspace(B, H, W, device))
@@ -140,6 +158,7 @@ class DenseNetHip:
             if skip_dst[i] is None:
                 skip_dst[i] = torch.empty((B * hs[i] * wss[i], taps_c[i]), dtype=torch.float32, device=dev)
         RELU = ops.ACT_RELU
+        wide_bf16 = bool(self.bf16_wide_1x1) and ops.current_launch_config()[1] == 2
 
         # stem: conv0 7x7/2 + norm0 + relu0 -> skip0 slot; pool0 -> block-1 prefix (+ skip1 slot)
         ops.nchw_to_nhwc(x, ws["img"][:, :3])
@@ -153,8 +172,15 @@ class DenseNetHip:
             mid = ws["mid"][: B * h * w]
             for li, L in enumerate(layers):
                 cin = L["cin"]
-                ops.conv_forward(buf[:, :cin], B, h, w, L["w1"], self.c_mid, 1, pre=L["pre"], pre_relu=True, e1=L["e1"],
-                                 act=RELU, y2d=mid, tag="enc_b%d_1x1" % (bi + 1), splitk_ws=ws["splitk"])
+                if wide_bf16 and ops.conv1x1_bf16_plan(h, w, cin, self.c_mid).eligible:
+                    if not P.get("planes_made"):
+                        self._round_bottleneck_planes(P, dev)
+                    wb = ops._derived_weight(L["w1"], "_bts_round1", ops.round_bf16)      # cached on the packed weight
+                    ops.conv1x1_bf16_forward(buf[:, :cin], B * h * w, cin, wb, self.c_mid, mid, pre=L["pre"], pre_relu=True,
+                                             e1=L["e1"], act=RELU, tag="enc_b%d_1x1" % (bi + 1))
+                else:
+                    ops.conv_forward(buf[:, :cin], B, h, w, L["w1"], self.c_mid, 1, pre=L["pre"], pre_relu=True, e1=L["e1"],
+                                     act=RELU, y2d=mid, tag="enc_b%d_1x1" % (bi + 1), splitk_ws=ws["splitk"])
                 ops.conv_forward(mid, B, h, w, L["w2"], self.growth, 3, y2d=buf[:, cin:cin + self.growth],
                                  tag="enc_b%d_3x3" % (bi + 1), splitk_ws=ws["splitk"])
             if bi < 3:

@@ -1190,8 +1190,63 @@ def conv_tail_bf16_forward(x2d: torch.Tensor, B: int, h: int, w: int, w_main: to
     return y2d
 
 
+# ---- wide 1x1 with bf16 operands, c_out % 192 == 0 (DenseNet161's bottlenecks under conv_precision "bf16"; csrc/conv_1x1_bf16.inc)
+def conv1x1_bf16_plan(h: int, w: int, c_in: int, c_out: int, fill_frames: Optional[int] = None) -> TilePlan:
+    """Should this 1x1 layer take conv1x1_bf16_forward?  Host-only query (bts_conv1x1_bf16_plan) on the per-frame geometry;
+    ``fill_frames`` defaults to the launch_config in force."""
+    ff, _ = _resolve_launch(None, fill_frames, "conv1x1_bf16_plan")
+    bm, bn, wgs = C.c_int(0), C.c_int(0), C.c_long(0)
+    _lib.check(_lib.load_real().bts_conv1x1_bf16_plan(int(h), int(w), int(c_in), int(c_out), int(ff), C.byref(bm), C.byref(bn),
+                                                       C.byref(wgs)), "bts_conv1x1_bf16_plan")
+    return TilePlan((bm.value, bn.value, wgs.value))
+
+
+def conv1x1_bf16_forward(x2d: torch.Tensor, npix: int, c_in: int, w_plane: torch.Tensor, c_out: int, y2d: torch.Tensor,
+                         pre: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, pre_relu: bool = False,
+                         e1: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, act: int = ACT_NONE, tag: str = "conv1x1_bf16"):
+    """act(e1(conv1x1(bf16(pre(x))))) in one launch of the wide bf16 tile (bts_conv1x1_bf16_fwd_f32): x2d [npix, >= c_in] NHWC
+    view (c_in channels read), w_plane the one-plane bf16 form of the layer's packed weight (``round_bf16(w_packed)``:
+    int16 [1, c_out_pad, k_pad], or the same bits as [c_out_pad, k_pad] / bfloat16), pre / e1 (scale, shift) pairs of >= c_in /
+    >= c_out floats, y2d [npix, c_out] NHWC view (a channel slice is fine).  Runs whatever the plan query says: callers ask
+    conv1x1_bf16_plan first."""
+    name = "conv1x1_bf16_forward"
+    xs, xc = _rows2d(x2d, name)
+    ys, yc = _rows2d(y2d, name)
+    if not isinstance(w_plane, torch.Tensor) or not w_plane.is_cuda or w_plane.dtype not in (torch.int16, torch.bfloat16):
+        raise BtsHipError("conv1x1_bf16_forward: w_plane must be an int16 / bfloat16 CUDA/ROCm tensor (round_bf16 of the packed weight)")
+    if c_in <= 0 or c_in % 16 or c_out <= 0 or c_out % 192:
+        raise BtsHipError("conv1x1_bf16_forward: %d -> %d channels; needs c_in %% 16 == 0 and c_out %% 192 == 0" % (c_in, c_out))
+    if npix <= 0 or xc < c_in or yc != c_out or x2d.shape[0] != npix or y2d.shape[0] != npix:
+        raise BtsHipError("conv1x1_bf16_forward: views %s / %s do not fit %d pixels, %d -> %d channels"
+                          % (tuple(x2d.shape), tuple(y2d.shape), npix, c_in, c_out))
+    if xs % 4 or ys % 4 or x2d.data_ptr() % 16 or y2d.data_ptr() % 16:
+        raise BtsHipError("conv1x1_bf16_forward: rows must be 16-byte aligned (pixel strides %d / %d, multiples of 4 floats)" % (xs, ys))
+    if (w_plane.dim() not in (2, 3) or (w_plane.dim() == 3 and w_plane.shape[0] != 1) or not w_plane.is_contiguous()
+            or w_plane.shape[-2] < c_out or w_plane.shape[-1] < c_in or w_plane.shape[-1] % 32):
+        raise BtsHipError("conv1x1_bf16_forward: w_plane %s must be contiguous [1, c_out_pad >= %d, k_pad >= %d (a multiple of 32)]"
+                          % (tuple(w_plane.shape), c_out, c_in))
+    cout_pad, k_pad = int(w_plane.shape[-2]), int(w_plane.shape[-1])
+    _check_act3(act, name)
+    ps, pb = _e2_vectors(pre, c_in, name, "pre")
+    es, eb = _e2_vectors(e1, c_out, name, "e1")
+    kern, flops, nbytes, xflops = "conv", 0.0, 0.0, None
+    if _trace is not None:
+        kern = conv_plan.wide_1x1_bf16_kernel_name(192)
+        flops = 2.0 * npix * c_out * c_in
+        nbytes = 4.0 * npix * (c_in + c_out) + 2.0 * c_out * c_in
+        xflops = 2.0 * (round_up(npix, 128)) * c_out * c_in                    # ragged last tile included
+    tops = torch_ops()
+    run = None
+    if tops is not None:
+        run = lambda: _op(lambda: tops.conv1x1_bf16(x2d, w_plane, ps, pb, es, eb, y2d, [npix, c_in, c_out, int(bool(pre_relu)), int(act)]))
+    _enqueue("bts_conv1x1_bf16_fwd_f32", x2d,
+             (_ptr(x2d), xs, npix, c_in, _ptr(w_plane), k_pad, c_out, cout_pad, _ptr(ps), _ptr(pb), int(bool(pre_relu)), _ptr(es), _ptr(eb),
+              int(act), _ptr(y2d), ys), trace=(kern, tag, flops, nbytes, xflops), run=run)
+    return y2d
+
+
 # ---- conv1 (32 features + planar tail -> 32 channels, NCHW) as a fused Winograd F(2x2,3x3) kernel (csrc/conv_wino_tail.inc)
-_WINO_G = ((1.0, 0.0, 0.0), (0.5, 0.5, 0.5), (0.5, -0.5, 0.5), (0.0, 0.0, 1.0))
+_WINO_G =((1.0, 0.0, 0.0), (0.5, 0.5, 0.5), (0.5, -0.5, 0.5), (0.0, 0.0, 1.0))
 _WINO_BT = ((1.0, 0.0, -1.0, 0.0), (0.0, 1.0, 1.0, 0.0), (0.0, -1.0, 1.0, 0.0), (0.0, 1.0, 0.0, -1.0))
 _WINO_AT = ((1.0, 1.0, 1.0, 0.0), (0.0, 1.0, -1.0, -1.0))
 

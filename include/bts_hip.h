@@ -310,6 +310,44 @@ int bts_conv_tail_bf16_fwd_f32(const float* x, long x_pix_stride, int B, int h, 
  *   both 0 when the layer should stay on bts_conv_fwd_f32's fp32 tail kernel. */
 int bts_conv_tail_bf16_plan(int h, int w, int c_main, int c_out, int n_tail, int fill_frames, int* bn, long* workgroups);
 
+/* A 1x1 convolution with c_out % 192 == 0 (DenseNet161's bottleneck layers) in the precision-2 arithmetic, in one launch of
+ * the wide bf16 tile (csrc/conv_1x1_bf16.inc: one workgroup = 128 pixels x ALL 192 channels of an N tile, so every input
+ * value is fetched, affined and converted once):
+ *   y[p][n] = act( e1( sum_{c < c_in} bf16( P(x[p][c]) ) * w_bf16[n][c] ) )
+ *   P(v)  = fma(v, pre_scale[c], pre_shift[c]), then max(., 0) when pre_relu     (identity when pre_* are NULL)
+ *   e1(a) = fma(a, e1_scale[n], e1_shift[n])                                    (identity when e1_* are NULL)
+ * ROUNDED: P's result, once, to the nearest bf16 (ties to even); P itself is ONE fused multiply-add in fp32.  w_bf16 is
+ * supplied rounded.  NOT rounded: the products (exact in fp32), the sum (fp32, v_mfma_f32_32x32x16_bf16), the epilogue, and
+ * every tensor in memory (x, y and the vectors are fp32).  Opt-in: bts_conv_fwd_f32 never takes this path on its own
+ * (precision 2 keeps these layers on BTS_CONV_KIND_ROW_BF16).
+ *   x       : [npix] NHWC pixels, x_pix_stride >= c_in floats per pixel (a multiple of 4), 16-byte aligned; c_in % 16 == 0.
+ *             A channel-prefix view is fine: channels >= c_in are never loaded.
+ *   w_bf16  : bf16 [c_out_pad][k_pad], k = c, 16-byte aligned: the one-plane precision-2 form of the packed weight
+ *             (bts_amd/ops.py:round_bf16 of pack_conv_weight's matrix); k_pad % 32 == 0, k_pad >= c_in.  Columns >= c_in of
+ *             a row are read when c_in % 32 == 16 and never multiplied; rows >= c_out are never read.
+ *   pre_*   : c_in floats each, 4-byte aligned, or both NULL;  e1_*: c_out floats each, 4-byte aligned, or both NULL
+ *   y       : [npix] NHWC pixels, y_pix_stride >= c_out (a multiple of 4), 4-byte aligned; a channel slice of a wider
+ *             buffer is fine: nothing is written outside [p][0 .. c_out)
+ *   act 0 none / 1 ReLU / 2 ELU
+ * BTS_ERR_UNSUPPORTED: c_out % 192 != 0, c_in % 16 != 0, k_pad % 32 != 0, k_pad < c_in, a pixel stride >= 2^26 floats,
+ * c_out_pad * k_pad >= 2^32 (32-bit offsets inside a row block and inside the plane), c_in so large that the prologue vectors
+ * do not fit LDS.  Any supported shape runs, whatever the plan query says.
+ * Sum order fixed (ascending c, in 16-channel MFMA blocks): a pixel's bits depend neither on npix nor on fill_frames.
+ * Non-finite values: an input value reaches exactly the outputs of its own pixel; max(NaN, 0) = 0 under pre_relu, as in
+ * every other prologue of this library. */
+int bts_conv1x1_bf16_fwd_f32(const float* x, long x_pix_stride, long npix, int c_in, const void* w_bf16, int k_pad,
+                             int c_out, int c_out_pad, const float* pre_scale, const float* pre_shift, int pre_relu,
+                             const float* e1_scale, const float* e1_shift, int act, float* y, long y_pix_stride,
+                             bts_stream_t stream);
+
+/* Should a 1x1 layer take bts_conv1x1_bf16_fwd_f32 (host-side query, no GPU work, no pointers)?  Eligible: c_out % 192 == 0,
+ * c_in % 16 == 0, and a declared launch (fill_frames as in bts_conv_desc, 0 = the library default; never B) whose pixel
+ * tiles fall in the range where the measured bench has the kernel win (csrc/conv_1x1_bf16.inc: the constants and their source).
+ *   *bm = pixels per workgroup (128), *bn = output channels per workgroup (192), *workgroups = workgroups PER FRAME
+ *   (ceil(h w / 128) * c_out / 192; a launch tiles its B h w pixels as one run, so it has at most that many per frame);
+ *   all three 0 when the layer should stay on bts_conv_fwd_f32. */
+int bts_conv1x1_bf16_plan(int h, int w, int c_in, int c_out, int fill_frames, int* bm, int* bn, long* workgroups);
+
 /* The decoder's full-resolution planar-tail 3x3 convolution (conv1: stride 1, padding 1, 32 NHWC feature channels plus up to
  * four dense depth planes in, 32 channels out, activation, NCHW result) in one launch of a fused Winograd F(2x2,3x3) kernel
  * (csrc/conv_wino_tail.inc):

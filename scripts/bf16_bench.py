@@ -11,6 +11,7 @@ alike.  The bf16 outputs are then compared with the fp32 outputs of the same inp
     python scripts/bf16_bench.py --configs 1 --rounds 5
     python scripts/bf16_bench.py --only bf16 --configs 1 --steps 3   # bf16 forwards only (run under rocprofv3)
     python scripts/bf16_bench.py --bf16-tail                 # a third graph: bf16 with conv3 / conv2 on the bf16 tail kernel
+    python scripts/bf16_bench.py --wide-1x1 [--bf16-tail]    # one more graph per bf16 variant: the same with BtsModel.bf16_wide_1x1 on
 """
 import argparse
 import json
@@ -68,9 +69,11 @@ def accuracy(got, ref):
 
 
 def set_variant(model, p):
-    """"fp32" / "bf16": the precision with the decoder's bf16_tail_convs switch off; "bf16_tail": bf16 with it on."""
-    model.conv_precision = "bf16" if p == "bf16_tail" else p
-    model.bf16_tail_convs = p == "bf16_tail"
+    """"fp32" / "bf16": the precision with both switches off; "bf16_tail": bf16 with the decoder's bf16_tail_convs on;
+    "bf16_wide" / "bf16_tail_wide": the same two with BtsModel.bf16_wide_1x1 on."""
+    model.conv_precision = "bf16" if p.startswith("bf16") else p
+    model.bf16_tail_convs = p.startswith("bf16_tail")
+    model.bf16_wide_1x1 = p.endswith("_wide")
 
 
 def run_config(idx, args, device):
@@ -82,8 +85,11 @@ def run_config(idx, args, device):
     image = torch.from_numpy(synth.image_batch(B, H, W, 1234)).to(device)
     focal = torch.from_numpy(synth.focal_values(B, params.dataset, 1234)).to(device)
     precs = [args.only] if args.only else ["fp32", "bf16"] + (["bf16_tail"] if args.bf16_tail else [])
+    if args.wide_1x1 and not args.only:
+        precs += [p + "_wide" for p in precs if p.startswith("bf16")]
     if args.only:                                   # profiling run: eager forwards, no timing claims
-        set_variant(model, "bf16_tail" if (args.bf16_tail and args.only == "bf16") else args.only)
+        v = "bf16_tail" if (args.bf16_tail and args.only == "bf16") else args.only
+        set_variant(model, v + "_wide" if (args.wide_1x1 and args.only == "bf16") else v)
         with torch.no_grad():
             for _ in range(args.steps):
                 model(image, focal)
@@ -124,6 +130,12 @@ def run_config(idx, args, device):
     if "bf16_tail" in outs:
         res["speedup_bf16_tail_over_bf16"] = res["bf16_tail"]["frames_per_s"] / res["bf16"]["frames_per_s"]
         res["bf16_tail_vs_fp32_outputs"] = accuracy(outs["bf16_tail"], outs["fp32"])
+    for p in precs:
+        if p.endswith("_wide"):
+            base = p[:-len("_wide")]
+            res["speedup_%s_over_%s" % (p, base)] = res[p]["frames_per_s"] / res[base]["frames_per_s"]
+            res["%s_vs_fp32_outputs" % p] = accuracy(outs[p], outs["fp32"])
+            res["%s_vs_%s_outputs_bit_identical" % (p, base)] = all(torch.equal(a, b) for a, b in zip(outs[p], outs[base]))
     return res
 
 
@@ -136,6 +148,8 @@ def main():
     ap.add_argument("--only", choices=("fp32", "bf16"), default=None, help="run one precision eagerly (profiling)")
     ap.add_argument("--bf16-tail", action="store_true",
                     help="also time bf16 with the decoder's bf16_tail_convs switch on (a third graph in the same alternation)")
+    ap.add_argument("--wide-1x1", action="store_true",
+                    help="also time every bf16 variant with BtsModel.bf16_wide_1x1 on (one more graph each in the same alternation)")
     ap.add_argument("--out", default=None, help="also write the JSON document here")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bf16_bench.py needs a GPU"
