@@ -9,7 +9,9 @@ from oracle import bts_oracle as O
 
 MAX_DEPTH = 80.0
 # (c_in, c_first_out, upratio); upratio 0 = the final chain
-CHAINS = {"8x8": (128, 128, 8), "4x4": (128, 64, 4), "2x2": (64, 32, 2), "final": (32, 16, 0)}
+CHAINS = {"8x8": (128, 128, 8), "4x4": (128, 64, 4), "2x2": (64, 32, 2), "final": (32, 16, 0),
+          # bts_size 256 (forward only: bts_reduc_bwd_f32 is not built for these, tests/reduc_lpg_cases.py)
+          "8x8/256": (64, 64, 8), "4x4/256": (64, 32, 4), "2x2/256": (32, 16, 2), "final/256": (16, 8, 0)}
 
 
 def make_case(name, B, h, w, seed, theta_scale=None):
