@@ -7,7 +7,9 @@ kernel rounds m and v exactly as ATen's CPU lerp_ / addcmul_ do (one fused multi
 floor; p differs from the CPU's in the order of the last two roundings of the update only.
 
 Packs: after every step each destination equals a fresh bts_pack_weights_f32 of the updated parameter bit for bit, padding
-included, and every float outside the planned extents of p / m / v / the destinations keeps its poison bits."""
+included, and every float outside the planned extents of p / m / v / the destinations keeps its poison bits.  A fresh pack
+is the pack kernel's word, so each destination is also held against the plain statement of tests/pack_cases.py, and the ABI
+test runs a second time with the destinations' padding poisoned: the step writes the real elements and nothing else."""
 import copy
 import ctypes as C
 from types import SimpleNamespace
@@ -17,6 +19,7 @@ import pytest
 import torch
 
 import adamw_cases as AC
+import pack_cases as PC
 from bts_amd import _lib, synth
 from parity_util import Params, t as as_tensor
 
@@ -128,13 +131,29 @@ def _fresh_pack(w4d, mode):
     return train.WeightPacker().get(w4d, ld, mode)
 
 
+def _statement(w4d, mode):
+    """int32 bits [rows_pad][k_pad] and the real-element mask of a dense weight's pack, from tests/pack_cases.py."""
+    shape = tuple(w4d.shape)
+    row = PC.dense_row(shape, mode, AC.pack_geometry(shape, mode)[2])
+    return torch.from_numpy(PC.dense_statement(w4d, row).view(np.int32)), torch.from_numpy(PC.real_mask(row))
+
+
+def _assert_entry_is_the_statement(key, e, what):
+    """A live packer entry (dense, bundled or native) against the statement of its parameter's current values."""
+    w = e["wref"]().detach().cpu()
+    rows = PC.table_rows(PC.Case("", tuple(key[1]), key[4], key[3], key[2], None))
+    assert rows == [tuple(r) for r in e["rows"]], (what, key[1:])
+    want = PC.statement(w, rows, tuple(e["dst"].shape), key[4])
+    assert np.array_equal(e["dst"].cpu().view(torch.int32).numpy(), want), (what, key[1:])
+
+
 def _offsets(ref, name):
     """Float offsets of (p, g, m, v) from a 16-byte line: one record with all four 4 bytes off (16 B per lane after a
     3-float head), one with only p off (one element per lane), and the 5-float record as one head element + one group."""
     return {"flat%d" % (ref.span + 1): (1, 1, 1, 1), "flat%d" % (ref.span - 1): (1, 0, 0, 0), "flat5": (3, 3, 3, 3)}.get(name, (0, 0, 0, 0))
 
 
-def _build_state(ref):
+def _build_state(ref, poison_pad=False):
     P, G, M, V, D = _Arena(), _Arena(), _Arena(), _Arena(), _Arena()
     regs = []
     for name, shape, modes in ref.cases:
@@ -155,6 +174,9 @@ def _build_state(ref):
         G.f[r.g:r.g + r.n] = 0
         for (start, rows_pad, k_pad), mode in zip(r.dst, modes):
             D.f[start:start + rows_pad * k_pad] = _fresh_pack(p0.cuda(), mode).reshape(-1)
+            if poison_pad:                                  # the step must write the real elements and nothing else
+                pad = ~_statement(p0.view(shape), mode)[1].reshape(-1)
+                D.bits[start:start + rows_pad * k_pad][pad.cuda()] = POISON
     P.f[extra:extra + 37] = 1.25
     ptrs = [(P.ptr(r.p), G.ptr(r.g), M.ptr(r.m), V.ptr(r.v), [D.ptr(s) for s, _, _ in r.dst]) for r in regs]
     items = AC.make_items(ref.cases, ptrs, ref.group)
@@ -182,8 +204,8 @@ def _snapshot(st):
     return [a.bits.clone() for a in (st.P, st.M, st.V, st.D)]
 
 
-def test_three_steps_match_fp64_packs_are_exact_and_nothing_else_is_written(ref):
-    st = _build_state(ref)
+def _three_steps(ref, poison_pad):
+    st = _build_state(ref, poison_pad)
     for s in range(3):
         _launch(st, ref, s)
         for i, (r, (name, shape, modes)) in enumerate(zip(st.regs, ref.cases)):
@@ -193,10 +215,24 @@ def test_three_steps_match_fp64_packs_are_exact_and_nothing_else_is_written(ref)
                 fresh = _fresh_pack(got["p"].clone().view(shape), mode)
                 assert fresh.shape == (rows_pad, k_pad)
                 mine = st.D.f[start:start + rows_pad * k_pad].view(rows_pad, k_pad)
+                want, real = _statement(got["p"].cpu().view(shape), mode)
+                assert want.shape == (rows_pad, k_pad)
+                assert torch.equal(fresh.cpu().view(torch.int32), want), (s + 1, name, mode, "the pack kernel against the statement")
+                if poison_pad:
+                    mine = mine.cpu().view(torch.int32)
+                    assert torch.equal(mine[real], want[real]), (s + 1, name, mode)
+                    assert bool((mine[~real] == POISON).all()), (s + 1, name, mode, "the step wrote padding")
+                    continue
                 assert torch.equal(mine.view(torch.int32), fresh.view(torch.int32)), (s + 1, name, mode)
+                assert torch.equal(mine.cpu().view(torch.int32), want), (s + 1, name, mode)
         for a, what in ((st.P, "p"), (st.M, "m"), (st.V, "v"), (st.D, "packs"), (st.G, "g")):
             assert a.untouched_outside(), "step %d wrote outside the planned extents of %s" % (s + 1, what)
         assert bool((st.P.f[st.extra:st.extra + 37] == 1.25).all())
+
+
+def test_three_steps_match_fp64_packs_are_exact_and_nothing_else_is_written(ref):
+    _three_steps(ref, poison_pad=False)                   # destinations start as fresh packs: padding +0.0 before and after
+    _three_steps(ref, poison_pad=True)                    # padding poisoned before the first step: still poison after each
 
 
 def test_skip_leaves_every_byte_and_zero_equals_null(ref):
@@ -257,6 +293,7 @@ def _check_native(ref, s, params, opt):
         assert id(e) in mine and e["version"] == w._version
         fresh = _fresh_pack(w.detach().clone(), key[3])
         assert torch.equal(e["dst"].view(torch.int32), fresh.view(torch.int32)), (s + 1, key[1], key[3])
+        _assert_entry_is_the_statement(key, e, "native step %d" % (s + 1))
         n_attached += 1
     assert n_attached == sum(len(m) for _, _, m in ref.cases) == len(opt.attached)
     assert opt.unattached == []
@@ -330,6 +367,7 @@ def _assert_entries_current(entries, what):
         w = e["wref"]()
         fresh = train.WeightPacker().get(w.detach().clone(), key[2], key[3], key[4])
         assert torch.equal(e["dst"].view(torch.int32), fresh.view(torch.int32)), (what, key[1:])
+        _assert_entry_is_the_statement(key, e, what)
 
 
 def _train_run(enc, steps, native, freeze=False, base=None):
