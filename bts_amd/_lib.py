@@ -135,6 +135,10 @@ ABI: Dict[str, Entry] = {
     "bts_conv_wgrad_batch_table_bytes": _query(_l64, _i),
     "bts_conv_wgrad_batch_plan_f32": _query(_i, _wgrad, _i, _pvp, _pl, _i, _l64, _vp, C.POINTER(ConvWgradBatchItem)),
     "bts_conv_wgrad_batch_f32": _launch(_vp, _vp, _i, _pvp, _i, _vp, _vp),
+    # bf16 operands, fp32 accumulation (train_precision "bf16"): the fp32 descriptor, planner and batch table
+    "bts_conv_wgrad_bf16_f32": _launch(_wgrad, _vp),
+    "bts_conv_wgrad_bf16_plan_f32": _query(_i, _wgrad, _pi, _pi, _pl, _pl),
+    "bts_conv_wgrad_batch_bf16_f32": _launch(_vp, _vp, _i, _pvp, _i, _vp, _vp),
     "bts_upconv_dgrad_f32": _launch(_vp, _l64, _i, _i, _i, _i, _vp, _i, _vp, _l64, _i, _i, _vp, _l64, _vp),
     "bts_upconv_dgrad_plan": _query(_i, _i, _i, _i, _i, _i, _i, _i, _l64, _pi, _pi, _pi),
     "bts_upconv_wgrad_f32": _launch(_vp, _l64, _i, _i, _i, _i, _vp, _l64, _i, _vp, _vp, _l64, _vp),

@@ -388,6 +388,10 @@ class bts(nn.Module):
         self.fused_reduction_train = False              # train() mode: True runs each reduction_1x1 -> LPG scale and reduc1x1 as one
                                                         # autograd node on the fused kernels (train.fused_lpg_scale);
                                                         # chains the library does not build (bts_size 256) keep the layer graph
+        self.train_precision = "fp32"                   # train() mode with grad enabled: "bf16" runs the convolutions the bf16
+                                                        # inference mode takes with bf16 operands and fp32 accumulation in
+                                                        # forward, input gradient and weight gradient (train.precision_scope;
+                                                        # DESIGN 3a); needs conv_precision "fp32"; eval forwards never read it
         self.batched_wgrad = False                      # train() mode, with fused_reduction_train: True computes the weight
                                                         # gradients of one scale's layers in one batched launch (ops.WgradBatch)
         self.subpixel_upconv_train = False              # train() mode: True runs the ratio-2 upconvs in sub-pixel form in the
@@ -668,6 +672,8 @@ class encoder(nn.Module):
         self.base_model = build_base_model(params.encoder)
         names, channels = self.TAPS.get(params.encoder, self.RESNET_TAPS)
         self.feat_names, self.feat_out_channels = list(names), list(channels)
+        self.train_precision = "fp32"       # train() mode with grad enabled: "bf16" = bf16 operands, fp32 accumulation in all three
+                                            # passes of every convolution but the 3-channel stem (train.precision_scope)
         self.batched_wgrad = False          # train() mode: True defers the weight gradients of a DenseNet block to the end
                                             # of its backward walk and computes them in one batched launch (train._DenseBlockFn)
         self.grouped_conv_train = False     # train() mode, ResNeXt: True runs every stride-1 grouped 3x3 with <= 16 channels per
@@ -774,6 +780,19 @@ class BtsModel(nn.Module):
     @grouped_conv_train.setter
     def grouped_conv_train(self, on: bool):
         self.encoder.grouped_conv_train = bool(on)
+
+    @property
+    def train_precision(self) -> str:
+        """Arithmetic of the training step's convolutions (encoder.train_precision and bts.train_precision, set together):
+        "fp32" (default) or "bf16" -- bf16 operands with fp32 accumulation in the forward, input-gradient and weight-gradient
+        pass of every convolution the bf16 inference mode takes; parameters, optimiser state, saved activations
+        and BN stay fp32.  Read only by a grad-enabled train-mode forward, where "bf16" needs conv_precision "fp32" (else
+        BtsHipError); eval forwards, conv_precision and every other switch keep their meaning and their bits."""
+        return self.decoder.train_precision
+
+    @train_precision.setter
+    def train_precision(self, value: str):
+        self.encoder.train_precision = self.decoder.train_precision = train.check_train_precision(value, "BtsModel.train_precision")
 
     @property
     def batched_wgrad(self) -> bool:

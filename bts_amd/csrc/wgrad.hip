@@ -13,7 +13,9 @@
 //
 // Three entry points share the tile body (wgrad_tile), the tile table, the split rules and the split sum:
 // bts_conv_wgrad_f32 (one problem), bts_upconv_wgrad_f32 (the sub-pixel upconv's four class gradients, folded) and
-// bts_conv_wgrad_batch_f32, which runs many problems (a DenseNet block's 2*L weight gradients) in one launch per tile
+// bts_conv_wgrad_batch_f32; bts_conv_wgrad_bf16_f32 / bts_conv_wgrad_batch_bf16_f32 are the first and the last with the
+// tile body's BF16 form (bf16 operands, fp32 accumulation; same plan, same split sum).
+// bts_conv_wgrad_batch_f32 runs many problems (a DenseNet block's 2*L weight gradients) in one launch per tile
 // shape plus one reduction launch; its planner sees the whole batch.  The weight packs live in pack.hip.
 // Batch planner, the rule kept:
 //   tile   per problem, by the single planner's shape terms alone: useful fraction of the padded tile grid x per-tile
@@ -69,6 +71,20 @@ struct WgradArgs {
                                  // [j*c_in, ..), gradient channels [j*c_out, ..) and writes dense block j of [c_out][N]
 };
 
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
+// Four channels of two pixels as four dwords of bf16 pairs, rounded to nearest even (a plain conversion: hipcc emits
+// v_cvt_pk_bf16_f32, two values per instruction); low half = the even pixel.
+__device__ __forceinline__ u32x4 pack_pairs(const f32x4 even, const f32x4 odd) {
+    u32x4 r;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) r[c] = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{even[c], odd[c]}, bf16x2));
+    return r;
+}
+
 // One workgroup = 4 waves arranged WM x WN over a BM x BN tile of dw; each wave owns (BM/WM) x (BN/WN).  The body is
 // shared by the single-problem launch (tile / split / bundle = blockIdx.x / .y / .z) and the batched launch (all three
 // derived from the workgroup's rank inside its problem).
@@ -77,21 +93,38 @@ struct WgradArgs {
 // K axis walks the B*h*w SOURCE pixels (g.H x g.W = g.Hs x g.Ws = the source map), the A operand of pixel (b, Y, X) is
 // dy at (b, 2Y+py, 2X+px) of the [B, 2h, 2w] gradient, and the 2x2 taps gather x at (Y-1+py+ty, X-1+px+tx); neither
 // operand is offset by the class, and the class results land in dense blocks [split][class][c_out][4*c_in] of a.out.
-template <int BM, int BN, int WM, int WN, bool SUBPIX = false>
+//
+// BF16 (bts_conv_wgrad_bf16_f32): both operands are rounded to the nearest bf16 (ties to even) on their way to LDS -- x
+// after its prologue and zero padding -- and a 32x32 block takes one v_mfma_f32_32x32x16_bf16 per 16 pixels, accumulated in
+// fp32.  That instruction wants 8 consecutive k per lane while both operands are K-major in memory, so the K-step is staged
+// as pixel PAIRS: a loader thread owns pixels 2r and 2r+1 of the step for its four channels and writes one 16-byte store of
+// four dwords (pixel 2r in the low half, 2r+1 in the high half) into an image [16 pair-rows][BM or BN] of dwords -- half the
+// LDS of the fp32 body.  Lane l's fragment of the 16-k block kb is then four ds_read_b32: pair-rows 8 kb + 4 (l >> 5) + 0..3,
+// column l & 31 (k = 8 (l >> 5) + j in element j, the map of both operands).  The order of k inside a block is free as long
+// as A and B agree, and they are staged by the same rule.  A pixel past the split's end is a zero partner.  Tile, split,
+// guards, epilogue and the registers' double staging are the fp32 body's.
+template <int BM, int BN, int WM, int WN, bool SUBPIX = false, bool BF16 = false>
 __device__ __forceinline__ void wgrad_tile(const WgradArgs& a, const unsigned tile, const unsigned split_idx,
                                            const unsigned bundle) {
     static_assert(WM * WN == 4, "4 waves");
     constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
     static_assert(TM >= 1 && TN >= 1, "wave tile must be at least 32x32");
     constexpr int ACOLS = BM / 4, BCOLS = BN / 4;          // float4 columns per tile row
-    constexpr int AROWS = 256 / ACOLS, BROWS = 256 / BCOLS;  // rows covered per pass
+    // fp32: rows covered per pass, register p of a thread is row a_row + p * AROWS.  BF16: pair-rows covered per pass (at
+    // most the 16 of a K-step: a 32-wide operand is loaded by the first 128 threads), registers 2q and 2q+1 are the two
+    // pixels of pair-row a_row + q * AROWS.
+    constexpr int AROWS = BF16 ? (256 / ACOLS < WBK / 2 ? 256 / ACOLS : WBK / 2) : 256 / ACOLS;
+    constexpr int BROWS = BF16 ? (256 / BCOLS < WBK / 2 ? 256 / BCOLS : WBK / 2) : 256 / BCOLS;
     constexpr int PA = WBK / AROWS, PB = WBK / BROWS;
     static_assert(PA >= 1 && PB >= 1, "tile too wide for 256 loader threads");
+    static_assert(!BF16 || (PA % 2 == 0 && PB % 2 == 0), "pixel pairs");
     const WgradGeom& g = a.g;
 
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* As = lds;                       // [2][WBK][BM]
     float* Bs = lds + 2 * WBK * BM;        // [2][WBK][BN]
+    [[maybe_unused]] unsigned* Au = reinterpret_cast<unsigned*>(lds);     // BF16: [2][WBK / 2][BM] pixel pairs
+    [[maybe_unused]] unsigned* Bu = Au + WBK * BM;                        //       [2][WBK / 2][BN]
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm0 = (wave / WN) * (BM / WM), wn0 = (wave % WN) * (BN / WN);
@@ -105,10 +138,13 @@ __device__ __forceinline__ void wgrad_tile(const WgradArgs& a, const unsigned ti
     // ---- loader roles (fixed for the whole K walk) ----
     const int a_col = (tid % ACOLS) * 4, a_row = tid / ACOLS;
     const int b_col = (tid % BCOLS) * 4, b_row = tid / BCOLS;
-    const bool a_ok = m0 + a_col < g.c_out;                 // c_out % 4 == 0: a float4 is all real or all padding
+    const bool a_act = !BF16 || a_row < AROWS, b_act = !BF16 || b_row < BROWS;
+    auto a_rowof = [&](int p) __attribute__((always_inline)) { return BF16 ? 2 * (a_row + (p >> 1) * AROWS) + (p & 1) : a_row + p * AROWS; };
+    auto b_rowof = [&](int p) __attribute__((always_inline)) { return BF16 ? 2 * (b_row + (p >> 1) * BROWS) + (p & 1) : b_row + p * BROWS; };
+    const bool a_ok = m0 + a_col < g.c_out && a_act;        // c_out % 4 == 0: a float4 is all real or all padding
     const int a_m = a_ok ? m0 + a_col : 0;
     const int n4 = n0 + b_col;
-    const bool b_ok = n4 < g.N;
+    const bool b_ok = n4 < g.N && b_act;
     const int nn = b_ok ? n4 : 0;
     const int tap = nn / g.c_in, ci = nn - tap * g.c_in;    // c_in % 4 == 0: a float4 never straddles a tap
     const int ky = tap / g.ksize, kx = tap - ky * g.ksize;
@@ -132,7 +168,7 @@ __device__ __forceinline__ void wgrad_tile(const WgradArgs& a, const unsigned ti
     int pb[PB], py[PB], px[PB];             // (frame, row, column) of each gathered row's output pixel at the next step
 #pragma unroll
     for (int p = 0; p < PB; ++p) {
-        const unsigned pix = k_begin + b_row + p * BROWS;
+        const unsigned pix = k_begin + b_rowof(p);
         const unsigned b = pix / HW, rem = pix - b * HW;
         pb[p] = (int)b;
         py[p] = (int)(rem / (unsigned)g.W);
@@ -142,7 +178,7 @@ __device__ __forceinline__ void wgrad_tile(const WgradArgs& a, const unsigned ti
     if constexpr (SUBPIX) {
 #pragma unroll
         for (int p = 0; p < PA; ++p) {
-            const unsigned pix = k_begin + a_row + p * AROWS;
+            const unsigned pix = k_begin + a_rowof(p);
             const unsigned b = pix / HW, rem = pix - b * HW;
             qb[p] = (int)b;
             qy[p] = (int)(rem / (unsigned)g.W);
@@ -151,9 +187,10 @@ __device__ __forceinline__ void wgrad_tile(const WgradArgs& a, const unsigned ti
     }
     auto issue = [&](int it, f32x4 (&ra)[PA], f32x4 (&rb)[PB]) __attribute__((always_inline)) {
         const unsigned base = k_begin + (unsigned)it * WBK;
+        if (!BF16 || a_act)                                              // BF16 32-wide A: threads 128.. load nothing
 #pragma unroll
         for (int p = 0; p < PA; ++p) {
-            const unsigned pix = base + a_row + p * AROWS;
+            const unsigned pix = base + a_rowof(p);
             const bool ok = a_ok && pix < k_end;
             size_t row = ok ? pix : 0u;
             if constexpr (SUBPIX) {                                      // dy lives at (2Y+py, 2X+px) of the [B,2h,2w] map
@@ -168,7 +205,7 @@ __device__ __forceinline__ void wgrad_tile(const WgradArgs& a, const unsigned ti
         }
 #pragma unroll
         for (int p = 0; p < PB; ++p) {
-            const unsigned pix = base + b_row + p * BROWS;
+            const unsigned pix = base + b_rowof(p);
             const int iy = py[p] * g.stride + off_y, ix = px[p] * g.stride + off_x;
             const bool ok = b_ok && pix < k_end && iy >= 0 && iy < g.Hs && ix >= 0 && ix < g.Ws;
             const int sb = ok ? pb[p] : 0, sy = ok ? (iy >> g.ups) : 0, sx = ok ? (ix >> g.ups) : 0;
@@ -186,6 +223,19 @@ __device__ __forceinline__ void wgrad_tile(const WgradArgs& a, const unsigned ti
         }
     };
     auto stage = [&](int buf, const f32x4 (&ra)[PA], const f32x4 (&rb)[PB]) __attribute__((always_inline)) {
+        if constexpr (BF16) {
+            if (a_act) {
+#pragma unroll
+                for (int q = 0; q < PA / 2; ++q)
+                    *reinterpret_cast<u32x4*>(&Au[(buf * (WBK / 2) + a_row + q * AROWS) * BM + a_col]) = pack_pairs(ra[2 * q], ra[2 * q + 1]);
+            }
+            if (b_act) {
+#pragma unroll
+                for (int q = 0; q < PB / 2; ++q)
+                    *reinterpret_cast<u32x4*>(&Bu[(buf * (WBK / 2) + b_row + q * BROWS) * BN + b_col]) = pack_pairs(rb[2 * q], rb[2 * q + 1]);
+            }
+            return;
+        }
 #pragma unroll
         for (int p = 0; p < PA; ++p)
             *reinterpret_cast<f32x4*>(&As[(buf * WBK + a_row + p * AROWS) * BM + a_col]) = ra[p];
@@ -201,6 +251,28 @@ __device__ __forceinline__ void wgrad_tile(const WgradArgs& a, const unsigned ti
         for (int j = 0; j < TN; ++j) acc[i][j] = (f32x16)(0.f);
 
     auto mfma_step = [&](int cur) __attribute__((always_inline)) {
+        if constexpr (BF16) {
+            const unsigned* Ac = Au + cur * (WBK / 2) * BM + wm0 + l31;
+            const unsigned* Bc = Bu + cur * (WBK / 2) * BN + wn0 + l31;
+#pragma unroll
+            for (int kb = 0; kb < WBK / 16; ++kb) {
+                u32x4 av[TM], bv[TN];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+#pragma unroll
+                    for (int i = 0; i < TM; ++i) av[i][e] = Ac[(8 * kb + 4 * khalf + e) * BM + 32 * i];
+#pragma unroll
+                    for (int j = 0; j < TN; ++j) bv[j][e] = Bc[(8 * kb + 4 * khalf + e) * BN + 32 * j];
+                }
+#pragma unroll
+                for (int i = 0; i < TM; ++i)
+#pragma unroll
+                    for (int j = 0; j < TN; ++j)
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, av[i]), __builtin_bit_cast(bf16x8, bv[j]),
+                                                                            acc[i][j], 0, 0, 0);
+            }
+            return;
+        }
         const float* Ac = As + cur * WBK * BM + wm0 + l31;
         const float* Bc = Bs + cur * WBK * BN + wn0 + l31;
 #pragma unroll
@@ -252,9 +324,9 @@ __device__ __forceinline__ void wgrad_tile(const WgradArgs& a, const unsigned ti
         }
 }
 
-template <int BM, int BN, int WM, int WN>
+template <int BM, int BN, int WM, int WN, bool BF16 = false>
 __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const WgradArgs a) {
-    wgrad_tile<BM, BN, WM, WN>(a, blockIdx.x, blockIdx.y, blockIdx.z);
+    wgrad_tile<BM, BN, WM, WN, false, BF16>(a, blockIdx.x, blockIdx.y, blockIdx.z);
 }
 
 template <int BM, int BN, int WM, int WN>
@@ -421,17 +493,18 @@ template <typename T> long wgrad_tile_grid(WgradGeom& g) {
     return (long)((g.c_out + T::BM - 1) / T::BM) * g.n_ntiles;
 }
 
-// Enqueue a wgrad_tile kernel of tile T: its LDS (two stages of both operands), raised above the default where needed.
+// Enqueue a wgrad_tile kernel of tile T: its LDS (two stages of both operands; BF16: as pixel pairs, half the bytes), raised
+// above the default where needed.
 // Returns that step's error, or 0 with the kernel enqueued; the caller reads hipGetLastError after its last launch.
-template <typename T, auto Kern, typename... Args> int launch_wgrad_tiles(dim3 grid, hipStream_t s, Args... args) {
-    return bts_launch<Kern>(grid, dim3(256), (size_t)2 * WBK * (T::BM + T::BN) * sizeof(float), s, args...);
+template <typename T, auto Kern, bool BF16 = false, typename... Args> int launch_wgrad_tiles(dim3 grid, hipStream_t s, Args... args) {
+    return bts_launch<Kern>(grid, dim3(256), (size_t)2 * WBK * (T::BM + T::BN) * (BF16 ? sizeof(unsigned) / 2 : sizeof(float)), s, args...);
 }
 
 // `a` and `split` come from prepare_wgrad: a.g.pix_per_split and the split count are final here.
-template <typename T> int launch_wgrad(WgradArgs a, long split, float* dw, float* ws, hipStream_t s) {
+template <typename T, bool BF16 = false> int launch_wgrad(WgradArgs a, long split, float* dw, float* ws, hipStream_t s) {
     const long tiles = wgrad_tile_grid<T>(a.g);
     a.out = split > 1 ? ws : dw;
-    if (const int rc = launch_wgrad_tiles<T, conv_wgrad_kernel<T::BM, T::BN, T::WM, T::WN>>(
+    if (const int rc = launch_wgrad_tiles<T, conv_wgrad_kernel<T::BM, T::BN, T::WM, T::WN, BF16>, BF16>(
             dim3((unsigned)tiles, (unsigned)split, (unsigned)a.n_bundles), s, a); rc != 0) return rc;
     if (split > 1) {
         const long count4 = (long)a.g.c_out * a.g.N * a.n_bundles / 4;      // N % 4 == 0
@@ -537,6 +610,18 @@ extern "C" int bts_conv_wgrad_plan_f32(const bts_conv_wgrad_desc* d, int* bm, in
     return report_plan(p, a, bm, bn, split, pix_per_split);
 }
 
+// bf16 operands, fp32 accumulation: the descriptor, the checks, the tile, the split and the split sum of bts_conv_wgrad_f32.
+extern "C" int bts_conv_wgrad_bf16_f32(const bts_conv_wgrad_desc* d, bts_stream_t stream) {
+    WgradArgs a;
+    WgradPlan p;
+    if (const int rc = prepare_wgrad(d, a, p); rc != 0) return rc;
+    return for_wgrad_tile(p.variant, [&](auto t) { return launch_wgrad<decltype(t), true>(a, p.split, d->dw, d->ws, (hipStream_t)stream); });
+}
+
+extern "C" int bts_conv_wgrad_bf16_plan_f32(const bts_conv_wgrad_desc* d, int* bm, int* bn, long* split, long* pix_per_split) {
+    return bts_conv_wgrad_plan_f32(d, bm, bn, split, pix_per_split);      // no shape class is declined
+}
+
 extern "C" int bts_upconv_wgrad_f32(const float* x, long x_pix_stride, int B, int h, int w, int c_in, const float* dy,
                                     long dy_pix_stride, int c_out, float* dw, float* ws, long ws_floats, bts_stream_t stream) {
     WgradArgs a;
@@ -598,7 +683,7 @@ __device__ __forceinline__ const char* wgrad_base(const WgradBases& b, int i) { 
     return p;
 }
 
-template <int BM, int BN, int WM, int WN>
+template <int BM, int BN, int WM, int WN, bool BF16 = false>
 __global__ __launch_bounds__(256, 2) void conv_wgrad_batch_kernel(const WgradBatchEntry* __restrict__ table, int n,
                                                                   const WgradBases bases, float* __restrict__ ws) {
     // uniform: read once, into scalar registers
@@ -616,7 +701,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_batch_kernel(const WgradBat
     a.n_bundles = e.n_bundles;
     const unsigned rank = (unsigned)((long)blockIdx.x - e.first_wg);      // < tiles * split * n_bundles
     const unsigned tile = rank % (unsigned)e.tiles, rest = rank / (unsigned)e.tiles;
-    wgrad_tile<BM, BN, WM, WN>(a, tile, rest % (unsigned)e.split, rest / (unsigned)e.split);
+    wgrad_tile<BM, BN, WM, WN, false, BF16>(a, tile, rest % (unsigned)e.split, rest / (unsigned)e.split);
 }
 
 // wgrad_reduce_kernel for every split problem of a batch in one launch: the block finds its problem in the table
@@ -812,8 +897,12 @@ extern "C" int bts_conv_wgrad_batch_plan_f32(const bts_conv_wgrad_desc* descs, i
     return wgrad_batch_layout(items, wgrad_batch_quantum(items, ws_floats), n_bases, ws_floats, hdr, (WgradBatchEntry*)(hdr + 1), plan);
 }
 
-extern "C" int bts_conv_wgrad_batch_f32(const void* table_host, const void* table_dev, int n, const void* const* bases,
-                                        int n_bases, float* ws, bts_stream_t stream) {
+namespace {
+
+// Both batch launches: the table's grids with the fp32 or the bf16 tile body, then the one reduction launch.
+template <bool BF16>
+int launch_wgrad_batch(const void* table_host, const void* table_dev, int n, const void* const* bases, int n_bases, float* ws,
+                       bts_stream_t stream) {
     const WgradBatchHeader* hdr = (const WgradBatchHeader*)table_host;
     if (!hdr || hdr->magic != WGRAD_BATCH_MAGIC || hdr->n != n || hdr->n_bases != n_bases || n < 0) return BTS_ERR_INVALID;
     if (n == 0) return 0;
@@ -831,8 +920,8 @@ extern "C" int bts_conv_wgrad_batch_f32(const void* table_host, const void* tabl
         if (cnt <= 0 || hdr->wgs[v] <= 0) continue;
         const int rc = for_wgrad_tile(v, [&](auto t) {
             using T = decltype(t);
-            const int e = launch_wgrad_tiles<T, conv_wgrad_batch_kernel<T::BM, T::BN, T::WM, T::WN>>(dim3((unsigned)hdr->wgs[v]), s,
-                                                                                                    entries + hdr->first[v], cnt, b, ws);
+            const int e = launch_wgrad_tiles<T, conv_wgrad_batch_kernel<T::BM, T::BN, T::WM, T::WN, BF16>, BF16>(
+                dim3((unsigned)hdr->wgs[v]), s, entries + hdr->first[v], cnt, b, ws);
             return e != 0 ? e : (int)hipGetLastError();
         });
         if (rc != 0) return rc;
@@ -843,4 +932,17 @@ extern "C" int bts_conv_wgrad_batch_f32(const void* table_host, const void* tabl
         return (int)hipGetLastError();
     }
     return 0;
+}
+
+}  // namespace
+
+extern "C" int bts_conv_wgrad_batch_f32(const void* table_host, const void* table_dev, int n, const void* const* bases,
+                                        int n_bases, float* ws, bts_stream_t stream) {
+    return launch_wgrad_batch<false>(table_host, table_dev, n, bases, n_bases, ws, stream);
+}
+
+// The same table (bts_conv_wgrad_batch_plan_f32) and the same reduction launch, the tiles with bf16 operands.
+extern "C" int bts_conv_wgrad_batch_bf16_f32(const void* table_host, const void* table_dev, int n, const void* const* bases,
+                                             int n_bases, float* ws, bts_stream_t stream) {
+    return launch_wgrad_batch<true>(table_host, table_dev, n, bases, n_bases, ws, stream);
 }

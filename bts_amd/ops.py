@@ -8,7 +8,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import threading
-from typing import List, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -1918,11 +1918,33 @@ def _wgrad_desc(B: int, h_in: int, w_in: int, c_in: int, c_out: int, ksize: int,
     return d
 
 
-def conv_wgrad_plan_desc(d: ConvWgradDesc) -> Tuple[int, int, int, int]:
-    """bts_conv_wgrad_plan_f32 on a filled descriptor: (bm, bn, split, pix_per_split).  Host arithmetic only."""
+_WGRAD_PRECISIONS = {None: 0, "fp32": 0, 0: 0, "bf16": 2, 2: 2}
+
+
+def wgrad_precision(precision, who: str = "conv_wgrad") -> int:
+    """The weight-gradient arithmetic a caller names: 0 (``None`` / "fp32" / 0: the fp32-input MFMA) or 2 ("bf16" / 2: bf16
+    operands, fp32 accumulation).  An argument of the call, never read from the launch_config in force: autograd runs
+    ``backward`` on another thread, where the scope a model opened is not in force."""
+    try:
+        return _WGRAD_PRECISIONS[precision]
+    except (KeyError, TypeError):
+        raise BtsHipError("%s: precision must be 'fp32' / 0 or 'bf16' / 2" % who) from None
+
+
+BTS_ERR_UNSUPPORTED = -2      # include/bts_hip.h
+
+
+def conv_wgrad_plan_desc(d: ConvWgradDesc, precision=None) -> Optional[Tuple[int, int, int, int]]:
+    """bts_conv_wgrad_plan_f32 on a filled descriptor: (bm, bn, split, pix_per_split).  Host arithmetic only.
+    ``precision`` "bf16": bts_conv_wgrad_bf16_plan_f32 -- the same answer, or None for a shape class the bf16 body declines
+    (the caller then launches in fp32)."""
     bm, bn, split, pps = C.c_int(0), C.c_int(0), C.c_long(0), C.c_long(0)
-    _lib.check(_lib.load_real().bts_conv_wgrad_plan_f32(C.byref(d), C.byref(bm), C.byref(bn), C.byref(split), C.byref(pps)),
-               "bts_conv_wgrad_plan_f32")
+    name = "bts_conv_wgrad_bf16_plan_f32" if wgrad_precision(precision, "conv_wgrad_plan") == 2 else "bts_conv_wgrad_plan_f32"
+    rc = getattr(_lib.load_real(), name)(C.byref(d), C.byref(bm), C.byref(bn), C.byref(split), C.byref(pps))
+    if rc == BTS_ERR_UNSUPPORTED and name == "bts_conv_wgrad_bf16_plan_f32" and _lib.load_real().bts_conv_wgrad_plan_f32(
+            C.byref(d), None, None, None, None) == 0:
+        return None
+    _lib.check(rc, name)
     return bm.value, bn.value, split.value, pps.value
 
 
@@ -1932,11 +1954,12 @@ _PLAN_DUMMY_PTR = 1 << 20      # non-null, 16-byte aligned; a plan query checks 
 def conv_wgrad_plan(B: int, h_in: int, w_in: int, c_in: int, c_out: int, ksize: int, dil: int = 1, stride: int = 1,
                     pad: Optional[int] = None, up: int = 1, ws_floats: Optional[int] = None, n_bundles: int = 1,
                     pre: bool = False, pre_relu: bool = False, x_pix_stride: Optional[int] = None,
-                    dy_pix_stride: Optional[int] = None) -> Tuple[int, int, int, int]:
+                    dy_pix_stride: Optional[int] = None, precision=None) -> Optional[Tuple[int, int, int, int]]:
     """Which tile and pixel split conv_wgrad will run for this geometry: (bm, bn, split, pix_per_split), from the
     library's own planner (bts_conv_wgrad_plan_f32).  No tensors and no GPU: the geometry arguments are conv_wgrad's,
     ``ws_floats`` is the size of the workspace it would get (None = no workspace), ``pre`` says whether an input
-    prologue rides along, and the pixel strides default to the dense ``n_bundles * c``."""
+    prologue rides along, and the pixel strides default to the dense ``n_bundles * c``.  ``precision`` "bf16": the bf16
+    query (conv_wgrad_plan_desc) -- None where conv_wgrad(..., precision="bf16") runs the fp32 launch."""
     if pad is None:
         pad = dil * (ksize // 2)
     nb = max(n_bundles, 1)
@@ -1948,17 +1971,27 @@ def conv_wgrad_plan(B: int, h_in: int, w_in: int, c_in: int, c_out: int, ksize: 
         d.pre_relu = int(bool(pre_relu))
     if ws_floats is not None:
         d.ws, d.ws_floats = _PLAN_DUMMY_PTR, ws_floats
-    return conv_wgrad_plan_desc(d)
+    return conv_wgrad_plan_desc(d, precision)
+
+
+_WGRAD_BF16_TAKES: Dict[tuple, bool] = {}      # conv_wgrad geometry -> whether bts_conv_wgrad_bf16_plan_f32 takes it
 
 
 def conv_wgrad(x2d: torch.Tensor, B: int, h_in: int, w_in: int, c_in: int, dy2d: torch.Tensor, c_out: int,
                ksize: int, dil: int = 1, stride: int = 1, pad: Optional[int] = None, up: int = 1,
                ws: Optional[torch.Tensor] = None, tag: str = "wgrad", n_bundles: int = 1,
-               pre: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, pre_relu: bool = False) -> torch.Tensor:
+               pre: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, pre_relu: bool = False, precision=None,
+               dw: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Weight gradient of one bias-free convolution (bts_conv_wgrad_f32): returns dw as [c_out, ksize*ksize, c_in]
     (OHWI).  x2d: [B*h_in*w_in, >=c_in] NHWC view of the forward input, dy2d: [B*H*W, >=c_out] NHWC view of the
     output gradient; c_in and c_out multiples of 4 (pad with zero channels).  ``n_bundles`` > 1: grouped convolution
-    as channel bundles (c_in / c_out per bundle): returns the dense blocks [n_bundles, c_out, ksize*ksize, c_in]."""
+    as channel bundles (c_in / c_out per bundle): returns the dense blocks [n_bundles, c_out, ksize*ksize, c_in].
+    ``precision`` "bf16": both operands rounded to bf16 (x after its prologue), fp32 accumulation, same tile and split
+    (bts_conv_wgrad_bf16_f32); a shape class its plan query declines runs the fp32 launch.  ``dw``: the buffer that
+    receives the gradient instead of a fresh tensor, as conv_grouped_wgrad and WgradBatch take one (a contiguous, 16-byte
+    aligned view of exactly that many floats, returned reshaped): a caller that keeps one flat gradient buffer per block or
+    bucket has the launch write into it."""
+    pr = wgrad_precision(precision)
     xs, xc = _rows2d(x2d, "conv_wgrad")
     ds, dc = _rows2d(dy2d, "conv_wgrad")
     if pad is None:
@@ -1970,7 +2003,13 @@ def conv_wgrad(x2d: torch.Tensor, B: int, h_in: int, w_in: int, c_in: int, dy2d:
         raise BtsHipError("conv_wgrad: views %s / %s do not match B=%d %dx%d -> %dx%d"
                           % (tuple(x2d.shape), tuple(dy2d.shape), B, h_in, w_in, H, W))
     shape = (c_out, ksize * ksize, c_in) if n_bundles <= 1 else (n_bundles, c_out, ksize * ksize, c_in)
-    dw = torch.empty(shape, dtype=torch.float32, device=x2d.device)
+    if dw is None:
+        dw = torch.empty(shape, dtype=torch.float32, device=x2d.device)
+    else:
+        _need(dw, "conv_wgrad")
+        if dw.numel() != int(torch.Size(shape).numel()) or not dw.is_contiguous() or dw.data_ptr() % 16 or dw.device != x2d.device:
+            raise BtsHipError("conv_wgrad: dw must be a contiguous, 16-byte aligned view of %d floats" % int(torch.Size(shape).numel()))
+        dw = dw.view(shape)
     d = _wgrad_desc(B, h_in, w_in, c_in, c_out, ksize, dil, stride, pad, up, n_bundles, xs, ds)
     if pre is not None:                       # the forward conv saw [relu](x*scale + shift): gather the same thing
         if pre[0].numel() != c_in * max(n_bundles, 1) or pre[1].numel() != pre[0].numel():
@@ -1983,7 +2022,22 @@ def conv_wgrad(x2d: torch.Tensor, B: int, h_in: int, w_in: int, c_in: int, dy2d:
     taps = ksize * ksize
     flops = 2.0 * B * H * W * c_out * c_in * taps * max(n_bundles, 1)
     nbytes = 4.0 * (B * h_in * w_in * c_in + B * H * W * c_out + taps * c_out * c_in) * max(n_bundles, 1)
-    _enqueue("bts_conv_wgrad_f32", x2d, (C.byref(d),), trace=("conv_wgrad_kernel", tag, flops, nbytes, None))
+    if pr == 2:
+        # does the bf16 plan query take this shape class?  A function of the geometry and the workspace size alone: asked
+        # once per geometry, not once per launch
+        key = (B, h_in, w_in, c_in, c_out, ksize, dil, stride, pad, up, n_bundles, xs, ds, pre is not None, bool(pre_relu),
+               None if ws is None else ws.numel())
+        ok = _WGRAD_BF16_TAKES.get(key)
+        if ok is None:
+            if len(_WGRAD_BF16_TAKES) >= 4096:
+                _WGRAD_BF16_TAKES.clear()
+            ok = _WGRAD_BF16_TAKES[key] = conv_wgrad_plan_desc(d, 2) is not None
+        if not ok:
+            pr = 0
+    if pr == 2:
+        _enqueue("bts_conv_wgrad_bf16_f32", x2d, (C.byref(d),), trace=("conv_wgrad_kernel<bf16>", tag, flops, nbytes, None))
+    else:
+        _enqueue("bts_conv_wgrad_f32", x2d, (C.byref(d),), trace=("conv_wgrad_kernel", tag, flops, nbytes, None))
     return dw
 
 
@@ -2085,10 +2139,12 @@ def upconv_dgrad_plan(B: int, h: int, w: int, c_out: int, c_in: int, splitk_ws_f
 
 
 def upconv_dgrad(dy2d: torch.Tensor, B: int, h: int, w: int, w_dgrad: torch.Tensor, c_out: int, c_in: int, dx2d: torch.Tensor,
-                 splitk_ws: Optional[torch.Tensor] = None, tag: str = "upconv.dgrad") -> torch.Tensor:
+                 splitk_ws: Optional[torch.Tensor] = None, tag: str = "upconv.dgrad", precision=None) -> torch.Tensor:
     """Input gradient of the sub-pixel upconv (bts_upconv_dgrad_f32): dy2d [B*2h*2w, >= c_out] NHWC view -> dx2d
     [B*h*w, c_in] NHWC view (channel slices of wider buffers are fine), one 4x4 / stride-2 convolution with ``w_dgrad``
-    from upconv_train_pack.  fp32 or bf16x3 by the launch_config in force; ``splitk_ws`` lets small maps split K."""
+    from upconv_train_pack.  fp32 or bf16x3 by the launch_config in force; ``splitk_ws`` lets small maps split K.
+    ``precision=2``: dy and the pack both rounded to bf16, as the node that recorded train_precision "bf16" in its forward
+    asks for by name -- never taken from the launch_config, where "bf16" is the inference mode."""
     ds, dc = _rows2d(dy2d, "upconv_dgrad")
     xs, xc = _rows2d(dx2d, "upconv_dgrad")
     _need(w_dgrad, "upconv_dgrad")
@@ -2100,6 +2156,10 @@ def upconv_dgrad(dy2d: torch.Tensor, B: int, h: int, w: int, w_dgrad: torch.Tens
     ff, pr = current_launch_config()
     if pr == 2:
         raise BtsHipError("upconv_dgrad: conv_precision 'bf16' is an inference mode")
+    if precision is not None:
+        if precision != 2:
+            raise BtsHipError("upconv_dgrad: precision is None (the launch_config in force) or 2")
+        pr = 1 if _ENV_PRECISION else 2
     ws_ptr, ws_n = None, 0
     if splitk_ws is not None:
         _need(splitk_ws, "upconv_dgrad")
@@ -2108,7 +2168,7 @@ def upconv_dgrad(dy2d: torch.Tensor, B: int, h: int, w: int, w_dgrad: torch.Tens
         ws_ptr, ws_n = splitk_ws.data_ptr(), splitk_ws.numel()
     kern = "conv"
     if _trace is not None:
-        bm, bn, _, sk = upconv_dgrad_plan(B, h, w, c_out, c_in, ws_n)
+        bm, bn, _, sk = upconv_dgrad_plan(B, h, w, c_out, c_in, ws_n, precision=pr)
         kern = "conv_fwd_kernel<%d,%d,k4s2>%s" % (bm, bn, "+splitk" if sk else "")
     flops = 2.0 * 36 * B * h * w * c_out * c_in               # the reference's 3x3 adjoint on the upsampled map
     nbytes = 4.0 * (4 * B * h * w * c_out + B * h * w * c_in + 16 * c_out * c_in)
@@ -2252,7 +2312,9 @@ class WgradBatch:
         if self.n:
             self._table_dev = torch.frombuffer(self._table, dtype=torch.uint8).to(self.device)      # the one upload
 
-    def run(self, bases: Sequence[torch.Tensor], ws: Optional[torch.Tensor]) -> List[torch.Tensor]:
+    def run(self, bases: Sequence[torch.Tensor], ws: Optional[torch.Tensor], precision=None) -> List[torch.Tensor]:
+        """``precision`` "bf16": the same table on bts_conv_wgrad_batch_bf16_f32 (bf16 operands, fp32 accumulation)."""
+        pr = wgrad_precision(precision, "WgradBatch.run")
         if len(bases) != len(self.base_numel):
             raise BtsHipError("WgradBatch.run: %d bases, planned with %d" % (len(bases), len(self.base_numel)))
         if self.n == 0:
@@ -2266,8 +2328,10 @@ class WgradBatch:
             if ws.numel() < self.ws_used or not ws.is_contiguous() or ws.device != self.device:
                 raise BtsHipError("WgradBatch.run: the workspace must hold %d floats" % self.ws_used)
         bp = (C.c_void_p * len(bases))(*[b.data_ptr() for b in bases])
-        _enqueue("bts_conv_wgrad_batch_f32", bases[0], (self._table, self._table_dev.data_ptr(), self.n, bp, len(bases), _ptr(ws)),
-                 trace=("conv_wgrad_batch_kernel", self.tag, self.flops, self.nbytes, None))
+        name, kern = (("bts_conv_wgrad_batch_bf16_f32", "conv_wgrad_batch_kernel<bf16>") if pr == 2 else
+                      ("bts_conv_wgrad_batch_f32", "conv_wgrad_batch_kernel"))
+        _enqueue(name, bases[0], (self._table, self._table_dev.data_ptr(), self.n, bp, len(bases), _ptr(ws)),
+                 trace=(kern, self.tag, self.flops, self.nbytes, None))
         return [bases[j].view(-1)[off:off + int(torch.Size(sh).numel())].view(sh) for j, off, sh in self._dw]
 
 

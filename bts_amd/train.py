@@ -18,6 +18,8 @@ There is no CPU path here: non-CUDA tensors raise.
 """
 from __future__ import annotations
 
+import contextlib
+import threading
 import weakref
 from typing import Dict, Tuple
 
@@ -308,11 +310,63 @@ def refuse_bf16(where: str) -> None:
         raise BtsHipError("%s: conv_precision 'bf16' is an inference mode; training runs in 'fp32' or 'bf16x3'" % where)
 
 
+# ---- train_precision: bf16 operands in all three passes of the training step (opt-in) -----------------------
+# ``BtsModel.train_precision = "bf16"`` (forwarded to encoder.train_precision and bts.train_precision) is a switch of its
+# own, not a value of conv_precision: a train-mode forward under conv_precision "bf16" still raises (refuse_bf16).  The
+# encoder / decoder training forwards open ``precision_scope`` around themselves; every autograd node reads the value in
+# force ONCE, in its forward, records what it ran in its ctx and applies that explicitly in backward -- autograd runs
+# backward on another thread, where neither this scope nor the model's launch_config is in force.
+TRAIN_PRECISIONS = {"fp32": 0, "bf16": 2}
+_tp_tls = threading.local()
+
+
+def check_train_precision(value, who: str = "train_precision") -> str:
+    if not isinstance(value, str) or value not in TRAIN_PRECISIONS:
+        raise BtsHipError("%s must be 'fp32' or 'bf16', got %r" % (who, value))
+    return value
+
+
+def current_train_precision() -> int:
+    """0 (fp32) or 2 (bf16 operands, fp32 accumulation): what a node whose forward runs now on this thread takes."""
+    return getattr(_tp_tls, "value", 0)
+
+
+class precision_scope:
+    """``with train.precision_scope("bf16"):`` around a training forward (this thread only).  Only a grad-enabled forward
+    reads the switch; "bf16" needs the launch precision "fp32" -- with conv_precision "bf16x3" (or "bf16", which training
+    refuses anyway) it raises; $BTS_CONV_PRECISION=1 keeps its precedence: the whole step then runs emulated, as ever."""
+
+    def __init__(self, value):
+        self._new = TRAIN_PRECISIONS[check_train_precision(value)]
+
+    def __enter__(self):
+        self._prev = getattr(_tp_tls, "value", None)
+        new = self._new if torch.is_grad_enabled() and not ops._ENV_PRECISION else 0
+        if new == 2 and ops.current_launch_config()[1] != 0:
+            raise BtsHipError("train_precision 'bf16' needs conv_precision 'fp32' (the launch precision in force is %r)"
+                              % (ops.current_launch_config()[1],))
+        _tp_tls.value = new
+        return self
+
+    def __exit__(self, *exc):
+        if self._prev is None:
+            del _tp_tls.value
+        else:
+            _tp_tls.value = self._prev
+        return False
+
+
+def _launch_precision(pr: int):
+    """The launch_config scope of a node's convolution launches: precision 2 where the node recorded it, else whatever is in
+    force (the fp32 / bf16x3 behaviour of before)."""
+    return ops.launch_config(precision=2) if pr == 2 else contextlib.nullcontext()
+
+
 class _ConvFn(torch.autograd.Function):
     """y = conv2d(nearest_up(x, up), w, stride, padding, dilation, groups), bias-free, on libbts_hip.so."""
 
     @staticmethod
-    def forward(ctx, x, weight, stride, padding, dilation, up, tag, groups, act=ops.ACT_NONE, grouped_native=False):
+    def forward(ctx, x, weight, stride, padding, dilation, up, tag, groups, act=ops.ACT_NONE, grouped_native=False, bf16=True):
         refuse_bf16("train.conv2d")
         ops._need(x, "train.conv2d")
         ops._need(weight, "train.conv2d")
@@ -326,24 +380,28 @@ class _ConvFn(torch.autograd.Function):
         y = torch.empty((B, H, W, cout), dtype=torch.float32, device=x.device)
         if act not in (ops.ACT_NONE, ops.ACT_ELU):
             raise BtsHipError("train.conv2d: only ELU can ride in the epilogue (its derivative is a function of y)")
+        native = False
         if groups > 1:
             if up != 1 or cout != C or act != ops.ACT_NONE:
                 raise BtsHipError("train.conv2d: grouped convolutions need cin == cout, no upsample, no activation")
             native = _grouped_native_layer(grouped_native, C, groups, k, stride, padding, dilation)
+        # train_precision "bf16": every layer but the ones the caller keeps in fp32 (``bf16=False``), the 3-channel stem and
+        # the native grouped kernels (their weight gradient is fp32: the layer stays fp32 in all three passes)
+        pr = 2 if current_train_precision() == 2 and bf16 and C > 4 and not native else 0
+        with _launch_precision(pr):
             if native:
                 wp = _PACKER.get(weight, 0, WeightPacker.FWD_NATIVE, groups)
                 ops.conv_grouped_forward(x2d, B, h, w, wp, C, groups, y2d=y.view(B * H * W, cout), tag=tag + ".fwd")
-            else:
+            elif groups > 1:
                 cb = WeightPacker.bundle_channels(weight, groups)
                 wp = _PACKER.get(weight, cb, WeightPacker.FWD, groups)
                 ops.conv_forward(x2d, B, h, w, wp, cb, k, dil=dilation, c_in_ld=cb, y2d=y.view(B * H * W, cout), stride=stride,
                                  pad=padding, tag=tag + ".fwd", c_in_real=cin_g, n_bundles=C // cb)
-        else:
-            native = False
-            wp = _PACKER.get(weight, c4, WeightPacker.FWD)
-            ops.conv_forward(x2d, B, h, w, wp, cout, k, dil=dilation, up=up, c_in_ld=c4, y2d=y.view(B * H * W, cout),
-                             stride=stride, pad=padding, tag=tag + ".fwd", c_in_real=C, act=act,
-                             splitk_ws=_splitk_workspace(x.device))
+            else:
+                wp = _PACKER.get(weight, c4, WeightPacker.FWD)
+                ops.conv_forward(x2d, B, h, w, wp, cout, k, dil=dilation, up=up, c_in_ld=c4, y2d=y.view(B * H * W, cout),
+                                 stride=stride, pad=padding, tag=tag + ".fwd", c_in_real=C, act=act,
+                                 splitk_ws=_splitk_workspace(x.device))
         out = y.permute(0, 3, 1, 2)           # [B,cout,H,W] channels_last view
         if act == ops.ACT_ELU:
             ctx.save_for_backward(x2d, out)   # ELU'(v) = 1 (y > 0) or y + 1: the pre-activation is never stored
@@ -353,6 +411,7 @@ class _ConvFn(torch.autograd.Function):
         ctx.geom = (B, C, h, w, c4, cout, k, stride, padding, dilation, up, H, W, tag, groups)
         ctx.act = act
         ctx.grouped_native = native           # decided once, in forward: all three passes of a layer take the same form
+        ctx.precision = pr                    # likewise the arithmetic: backward runs on another thread, outside every scope
         return out
 
     @staticmethod
@@ -380,18 +439,19 @@ class _ConvFn(torch.autograd.Function):
                                               else grad_out.permute(0, 2, 3, 1))      # a strided view has co4 == cout
                 g2d, gh, gw = u.view(B * Hs * Ws, co4), Hs, Ws
             dxu = torch.empty((B, Hs, Ws, C), dtype=torch.float32, device=dev)
-            if ctx.grouped_native:          # the adjoint is the same operator with flipped taps and transposed groups
-                wp = _PACKER.get(weight, 0, WeightPacker.DGRAD_NATIVE, groups)
-                ops.conv_grouped_forward(g2d, B, gh, gw, wp, C, groups, y2d=dxu.view(B * Hs * Ws, C), tag=tag + ".dgrad")
-            elif groups > 1:
-                cb = WeightPacker.bundle_channels(weight, groups)
-                wp = _PACKER.get(weight, cb, WeightPacker.DGRAD, groups)
-                ops.conv_forward(g2d, B, gh, gw, wp, cb, k, dil=dilation, c_in_ld=cb, y2d=dxu.view(B * Hs * Ws, C),
-                                 pad=pad_t, tag=tag + ".dgrad", c_in_real=weight.shape[1], n_bundles=C // cb)
-            else:
-                wp = _PACKER.get(weight, co4, WeightPacker.DGRAD)        # flipped, transposed kernel [cin][taps*co4]
-                ops.conv_forward(g2d, B, gh, gw, wp, C, k, dil=dilation, c_in_ld=co4, y2d=dxu.view(B * Hs * Ws, C),
-                                 pad=pad_t, tag=tag + ".dgrad", c_in_real=cout, splitk_ws=_splitk_workspace(dev))
+            with _launch_precision(ctx.precision):   # bf16: dy' and the flipped weights both rounded, the forward's kernels
+                if ctx.grouped_native:      # the adjoint is the same operator with flipped taps and transposed groups
+                    wp = _PACKER.get(weight, 0, WeightPacker.DGRAD_NATIVE, groups)
+                    ops.conv_grouped_forward(g2d, B, gh, gw, wp, C, groups, y2d=dxu.view(B * Hs * Ws, C), tag=tag + ".dgrad")
+                elif groups > 1:
+                    cb = WeightPacker.bundle_channels(weight, groups)
+                    wp = _PACKER.get(weight, cb, WeightPacker.DGRAD, groups)
+                    ops.conv_forward(g2d, B, gh, gw, wp, cb, k, dil=dilation, c_in_ld=cb, y2d=dxu.view(B * Hs * Ws, C),
+                                     pad=pad_t, tag=tag + ".dgrad", c_in_real=weight.shape[1], n_bundles=C // cb)
+                else:
+                    wp = _PACKER.get(weight, co4, WeightPacker.DGRAD)        # flipped, transposed kernel [cin][taps*co4]
+                    ops.conv_forward(g2d, B, gh, gw, wp, C, k, dil=dilation, c_in_ld=co4, y2d=dxu.view(B * Hs * Ws, C),
+                                     pad=pad_t, tag=tag + ".dgrad", c_in_real=cout, splitk_ws=_splitk_workspace(dev))
             if up == 2:                                                 # adjoint of the nearest-2x upsample
                 dxu = dxu.view(B, h, 2, w, 2, C).sum(dim=(2, 4))
             dx = dxu.permute(0, 3, 1, 2)
@@ -402,17 +462,17 @@ class _ConvFn(torch.autograd.Function):
                 cb = WeightPacker.bundle_channels(weight, groups)
                 cg, nb = weight.shape[1], C // cb
                 gpb = cb // cg
-                g = ops.conv_wgrad(x2d, B, h, w, cb, dy2d, cb, k, dil=dilation, stride=stride, pad=padding,
-                                   ws=_workspace(dev), tag=tag + ".wgrad", n_bundles=nb)   # [nb, cb, taps, cb] dense blocks
+                g = ops.conv_wgrad(x2d, B, h, w, cb, dy2d, cb, k, dil=dilation, stride=stride, pad=padding, ws=_workspace(dev),
+                                   tag=tag + ".wgrad", n_bundles=nb, precision=ctx.precision)   # [nb, cb, taps, cb] dense blocks
                 g6 = g.view(nb, gpb, cg, k * k, gpb, cg)
                 idx = torch.arange(gpb, device=dev)
                 diag = g6[:, idx, :, :, idx, :]                         # [gpb, nb, cg_out, taps, cg_in]: each group's own block
                 dw = diag.permute(1, 0, 2, 4, 3).reshape(cout, cg, k, k).contiguous()
             else:
                 g = ops.conv_wgrad(x2d, B, h, w, c4, dy2d, co4, k, dil=dilation, stride=stride, pad=padding, up=up,
-                                   ws=_workspace(dev), tag=tag + ".wgrad")
+                                   ws=_workspace(dev), tag=tag + ".wgrad", precision=ctx.precision)
                 dw = g[:cout, :, :C].reshape(cout, k, k, C).permute(0, 3, 1, 2).contiguous()   # OIHW, the layout DDP buckets expect
-        return dx, dw, None, None, None, None, None, None, None, None
+        return dx, dw, None, None, None, None, None, None, None, None, None
 
 
 def _grouped_native_layer(asked, c, groups, k, stride, padding, dilation) -> bool:
@@ -424,13 +484,16 @@ def _grouped_native_layer(asked, c, groups, k, stride, padding, dilation) -> boo
 
 
 def conv2d(x: torch.Tensor, weight: torch.Tensor, padding: int = 0, dilation: int = 1, stride: int = 1,
-           up: int = 1, tag: str = "conv", groups: int = 1, act: int = ops.ACT_NONE, grouped_native: bool = False) -> torch.Tensor:
+           up: int = 1, tag: str = "conv", groups: int = 1, act: int = ops.ACT_NONE, grouped_native: bool = False,
+           bf16: bool = True) -> torch.Tensor:
     """Differentiable bias-free convolution on the HIP kernels; ``up=2`` folds a nearest-2x upsample of ``x`` into
     the gather (reference upconv, bts.py:90-92); ``groups`` > 1: ResNeXt's grouped 3x3 as channel bundles, or, with
     ``grouped_native`` on the layers _grouped_native_layer names, on the native grouped kernels in all three passes;
     ``act=ops.ACT_ELU``: the ELU that follows every decoder convolution (bts.py:93, 183-221) applied in the epilogue.
+    ``bf16=False``: a layer that stays fp32 under train_precision "bf16" (precision_scope); the 3-channel stem and the
+    native grouped layers stay fp32 whatever it says.
     Returns a channels_last [B,c_out,H,W] tensor."""
-    return _ConvFn.apply(x, weight, stride, padding, dilation, up, tag, groups, act, grouped_native)
+    return _ConvFn.apply(x, weight, stride, padding, dilation, up, tag, groups, act, grouped_native, bf16)
 
 
 _BN_WS: Dict[Tuple[str, int], torch.Tensor] = {}
@@ -554,11 +617,14 @@ class _UpconvFn(torch.autograd.Function):
         x2d, _ = _nhwc_rows(x.detach())
         wf, wd = _UPCONV_PACKER.get(weight)
         y = torch.empty((B, 2 * h, 2 * w, cout), dtype=torch.float32, device=x.device)
-        ops.conv_forward(x2d, B, h, w, wf, cout, 3, up=2, c_in_ld=C, y2d=y.view(B * 4 * h * w, cout), subpixel=True,
-                         act=ops.ACT_ELU, tag=tag + ".fwd", c_in_real=C)
+        pr = current_train_precision()        # bf16: forward and input gradient; the class weight gradients stay fp32
+        with _launch_precision(pr):
+            ops.conv_forward(x2d, B, h, w, wf, cout, 3, up=2, c_in_ld=C, y2d=y.view(B * 4 * h * w, cout), subpixel=True,
+                             act=ops.ACT_ELU, tag=tag + ".fwd", c_in_real=C)
         out = y.permute(0, 3, 1, 2)
         ctx.save_for_backward(x2d, out, wd)   # ELU'(v) = 1 (y > 0) or y + 1; wd: this step's pack (refills happen between steps)
         ctx.geom = (B, C, h, w, cout, tag)
+        ctx.precision = pr
         return out
 
     @staticmethod
@@ -571,7 +637,8 @@ class _UpconvFn(torch.autograd.Function):
         dx = dw = None
         if ctx.needs_input_grad[0]:
             dxr = torch.empty((B, h, w, C), dtype=torch.float32, device=dev)
-            ops.upconv_dgrad(dy2d, B, h, w, wd, cout, C, dxr.view(B * h * w, C), splitk_ws=_splitk_workspace(dev), tag=tag + ".dgrad")
+            ops.upconv_dgrad(dy2d, B, h, w, wd, cout, C, dxr.view(B * h * w, C), splitk_ws=_splitk_workspace(dev), tag=tag + ".dgrad",
+                             precision=2 if ctx.precision == 2 else None)
             dx = dxr.permute(0, 3, 1, 2)
         if ctx.needs_input_grad[1]:
             g = ops.upconv_wgrad(x2d, B, h, w, C, dy2d, cout, _workspace(dev), tag=tag + ".wgrad")
@@ -597,11 +664,11 @@ def reduction_forward(m, net):
     """reduction_1x1.forward, bts.py:124-136: the 1x1 stack, then (non-final) the plane-parameter transform."""
     for layer in m.reduc:
         if isinstance(layer, torch.nn.Conv2d):                       # plane_params
-            net = conv2d(net, layer.weight, tag="reduc")
+            net = conv2d(net, layer.weight, tag="reduc", bf16=False)
         elif isinstance(layer[1], torch.nn.ELU) and layer[1].alpha == 1.0:
-            net = conv2d(net, layer[0].weight, tag="reduc", act=ops.ACT_ELU)   # inter_*: ELU in the epilogue
+            net = conv2d(net, layer[0].weight, tag="reduc", act=ops.ACT_ELU, bf16=False)   # inter_*: ELU in the epilogue
         else:
-            net = layer[1](conv2d(net, layer[0].weight, tag="reduc"))   # Sigmoid (final)
+            net = layer[1](conv2d(net, layer[0].weight, tag="reduc", bf16=False))   # Sigmoid (final)
     if m.is_final:
         return net
     import math
@@ -644,13 +711,13 @@ def fused_reduction_final(reduc_mod, feat, batched_wgrad=False):
                                         *_reduc_weights(reduc_mod))
 
 
-def _conv_elu(seq, x, tag):
-    return conv2d(x, seq[0].weight, padding=1, tag=tag, act=ops.ACT_ELU)
+def _conv_elu(seq, x, tag, bf16=True):
+    return conv2d(x, seq[0].weight, padding=1, tag=tag, act=ops.ACT_ELU, bf16=bf16)
 
 
 def decoder_forward(dec, features, focal):
     """bts.forward in train() mode (bts.py:223-293): same dataflow as the inference path, as an autograd graph."""
-    with _deferred_batch_counts():
+    with _deferred_batch_counts(), precision_scope(getattr(dec, "train_precision", "fp32")):
         return _decoder_forward(dec, features, focal)
 
 
@@ -687,18 +754,20 @@ def _decoder_forward(dec, features, focal):
 
     depth_8x8 = lpg_scale(dec.reduc8x8, dec.lpg8x8, daspp_feat)
     x = _bn(upconv_forward(dec.upconv3, daspp_feat, sub), dec.bn3)
-    iconv3 = _conv_elu(dec.conv3, torch.cat([x, skip1, depth_8x8[:, :, ::4, ::4]], 1), "conv3")
+    # conv3 / conv2 / conv1 (the planar-tail layers of the inference path), the reduction chains and get_depth are what the
+    # inference bf16 mode keeps in fp32: they stay fp32 under train_precision "bf16" too
+    iconv3 = _conv_elu(dec.conv3, torch.cat([x, skip1, depth_8x8[:, :, ::4, ::4]], 1), "conv3", bf16=False)
     depth_4x4 = lpg_scale(dec.reduc4x4, dec.lpg4x4, iconv3)
     x = _bn(upconv_forward(dec.upconv2, iconv3, sub), dec.bn2)
-    iconv2 = _conv_elu(dec.conv2, torch.cat([x, skip0, depth_4x4[:, :, ::2, ::2]], 1), "conv2")
+    iconv2 = _conv_elu(dec.conv2, torch.cat([x, skip0, depth_4x4[:, :, ::2, ::2]], 1), "conv2", bf16=False)
     depth_2x2 = lpg_scale(dec.reduc2x2, dec.lpg2x2, iconv2)
     upconv1 = upconv_forward(dec.upconv1, iconv2, sub)
     if fused and fused_reduction_available(dec.reduc1x1, 0):
         reduc1x1 = fused_reduction_final(dec.reduc1x1, upconv1, batched)
     else:
         reduc1x1 = reduction_forward(dec.reduc1x1, upconv1)
-    iconv1 = _conv_elu(dec.conv1, torch.cat([upconv1, reduc1x1, depth_2x2, depth_4x4, depth_8x8], 1), "conv1")
-    final_depth = md * torch.sigmoid(conv2d(iconv1, dec.get_depth[0].weight, padding=1, tag="get_depth"))
+    iconv1 = _conv_elu(dec.conv1, torch.cat([upconv1, reduc1x1, depth_2x2, depth_4x4, depth_8x8], 1), "conv1", bf16=False)
+    final_depth = md * torch.sigmoid(conv2d(iconv1, dec.get_depth[0].weight, padding=1, tag="get_depth", bf16=False))
     if dec.params.dataset == 'kitti':
         final_depth = final_depth * focal.view(-1, 1, 1, 1).float() / 715.0873
     return depth_8x8, depth_4x4, depth_2x2, reduc1x1, final_depth, iconv1
@@ -731,6 +800,7 @@ class _DenseBlockFn(torch.autograd.Function):
         saved = []
         ws = _bn_workspace(dev, ops.bn_train_ws_floats(npix, Ct))
         sk = _splitk_workspace(dev)
+        pr = current_train_precision()
         if batched:      # one slab per kind, so that the deferred weight gradients of all layers address six buffers
             T1 = torch.empty((len(layers), npix, mid), dtype=torch.float32, device=dev)
             stats = torch.empty((len(layers), 8, max(Ct, mid)), dtype=torch.float32, device=dev)   # rows 0-3 norm1, 4-7 norm2
@@ -742,13 +812,15 @@ class _DenseBlockFn(torch.autograd.Function):
             # norm + ReLU ride in the convolutions' prologue (applied on the way to LDS): the normalised tensors are
             # never written in the forward pass
             t1 = T1[i] if batched else torch.empty((npix, mid), dtype=torch.float32, device=dev)
-            ops.conv_forward(buf[:, :Ci], B, H, W, _PACKER.get(L.conv1.weight, Ci, WeightPacker.FWD), mid, 1, c_in_ld=Ci,
-                             pre=(s1[2], s1[3]), pre_relu=True, y2d=t1, tag="enc.fwd", splitk_ws=sk)
+            with _launch_precision(pr):
+                ops.conv_forward(buf[:, :Ci], B, H, W, _PACKER.get(L.conv1.weight, Ci, WeightPacker.FWD), mid, 1, c_in_ld=Ci,
+                                 pre=(s1[2], s1[3]), pre_relu=True, y2d=t1, tag="enc.fwd", splitk_ws=sk)
             s2 = ops.bn_train_stats(t1, mid, L.norm2.weight.detach(), L.norm2.bias.detach(), L.norm2.eps,
                                     L.norm2.momentum, L.norm2.running_mean, L.norm2.running_var, ws,
                                     out=stats[i, 4:8, :mid] if batched else None)
-            ops.conv_forward(t1, B, H, W, _PACKER.get(L.conv2.weight, mid, WeightPacker.FWD), g, 3, c_in_ld=mid,
-                             pre=(s2[2], s2[3]), pre_relu=True, y2d=buf[:, Ci:Ci + g], tag="enc.fwd", splitk_ws=sk)
+            with _launch_precision(pr):
+                ops.conv_forward(t1, B, H, W, _PACKER.get(L.conv2.weight, mid, WeightPacker.FWD), g, 3, c_in_ld=mid,
+                                 pre=(s2[2], s2[3]), pre_relu=True, y2d=buf[:, Ci:Ci + g], tag="enc.fwd", splitk_ws=sk)
             for bn in (L.norm1, L.norm2):
                 if bn.num_batches_tracked is not None:
                     _count_batch(bn)
@@ -759,6 +831,7 @@ class _DenseBlockFn(torch.autograd.Function):
         ctx.save_for_backward(buf, *saved)
         ctx.block = block
         ctx.batched_wgrad = batched
+        ctx.precision = pr
         ctx.geom = (B, C0, H, W, g, mid, Ct)
         return buf.view(B, H, W, Ct).permute(0, 3, 1, 2)
 
@@ -785,6 +858,7 @@ class _DenseBlockFn(torch.autograd.Function):
         sk = _splitk_workspace(dev)
         grads = [None] * (6 * len(layers))
         need = ctx.needs_input_grad
+        pr = ctx.precision
         for i in range(len(layers) - 1, -1, -1):
             L = layers[i]
             Ci = C0 + i * g
@@ -793,21 +867,24 @@ class _DenseBlockFn(torch.autograd.Function):
             else:
                 t1, s1, s2 = saved[3 * i], saved[3 * i + 1], saved[3 * i + 2]
             gy = G[:, Ci:Ci + g]                                               # this layer's output gradient, in place
-            ops.conv_forward(gy, B, H, W, _PACKER.get(L.conv2.weight, g, WeightPacker.DGRAD), mid, 3, c_in_ld=g, y2d=d_a2,
-                             pad=1, tag="enc.dgrad", splitk_ws=sk)
+            with _launch_precision(pr):
+                ops.conv_forward(gy, B, H, W, _PACKER.get(L.conv2.weight, g, WeightPacker.DGRAD), mid, 3, c_in_ld=g, y2d=d_a2,
+                                 pad=1, tag="enc.dgrad", splitk_ws=sk)
             if need[3 + 6 * i + 5] and not batched:   # the weight-gradient gather re-applies norm2 + ReLU to t1 on the fly
-                w2 = ops.conv_wgrad(t1, B, H, W, mid, gy, g, 3, ws=wws, tag="enc.wgrad", pre=(s2[2], s2[3]), pre_relu=True)
+                w2 = ops.conv_wgrad(t1, B, H, W, mid, gy, g, 3, ws=wws, tag="enc.wgrad", pre=(s2[2], s2[3]), pre_relu=True,
+                                    precision=pr)
                 grads[6 * i + 5] = w2.reshape(g, 3, 3, mid).permute(0, 3, 1, 2).contiguous()
             dg2, db2 = ops.bn_train_backward(t1, d_a2, mid, s2[0], s2[1], s2[2], s2[3], True, ws, d_t1)
             if need[3 + 6 * i + 3]:
                 grads[6 * i + 3] = dg2
             if need[3 + 6 * i + 4]:
                 grads[6 * i + 4] = db2
-            ops.conv_forward(d_t1, B, H, W, _PACKER.get(L.conv1.weight, mid, WeightPacker.DGRAD), Ci, 1, c_in_ld=mid,
-                             y2d=d_a1[:, :Ci], pad=0, tag="enc.dgrad", splitk_ws=sk)
+            with _launch_precision(pr):
+                ops.conv_forward(d_t1, B, H, W, _PACKER.get(L.conv1.weight, mid, WeightPacker.DGRAD), Ci, 1, c_in_ld=mid,
+                                 y2d=d_a1[:, :Ci], pad=0, tag="enc.dgrad", splitk_ws=sk)
             if need[3 + 6 * i + 2] and not batched:
                 w1 = ops.conv_wgrad(buf[:, :Ci], B, H, W, Ci, d_t1, mid, 1, ws=wws, tag="enc.wgrad", pre=(s1[2], s1[3]),
-                                    pre_relu=True)
+                                    pre_relu=True, precision=pr)
                 grads[6 * i + 2] = w1.reshape(mid, Ci, 1, 1)
             dg1, db1 = ops.bn_train_backward(buf[:, :Ci], d_a1[:, :Ci], Ci, s1[0], s1[1], s1[2], s1[3], True, ws, dpre[:, :Ci])
             if need[3 + 6 * i + 0]:
@@ -819,7 +896,7 @@ class _DenseBlockFn(torch.autograd.Function):
             # Deferring is safe: buf, T1 and the norm vectors are read-only in backward, D_T1[i] is written once, and layer
             # i's columns of G are final when layer i is processed (layers below only add onto columns < C_i).
             mask = tuple((bool(need[3 + 6 * i + 2]), bool(need[3 + 6 * i + 5])) for i in range(len(layers)))
-            dws = iter(_dense_wgrad_batch(ctx.geom, mask, buf, G, T1, D_T1, stats, wws))
+            dws = iter(_dense_wgrad_batch(ctx.geom, mask, buf, G, T1, D_T1, stats, wws, pr))
             for i, (n1, n2) in enumerate(mask):
                 if n1:
                     grads[6 * i + 2] = next(dws).reshape(mid, C0 + i * g, 1, 1)
@@ -834,11 +911,11 @@ class _DenseBlockFn(torch.autograd.Function):
 _DENSE_WGRAD_BATCHES = ops.BatchCache(64)
 
 
-def _dense_wgrad_batch(geom, mask, buf, G, T1, D_T1, stats, wws):
+def _dense_wgrad_batch(geom, mask, buf, G, T1, D_T1, stats, wws, precision=0):
     """Every wanted weight gradient of one dense block in ONE batched launch over the bases buf, G, T1, D_T1, stats and
     a flat DW (the return value's views, in layer order: 1x1 then 3x3).  The batch -- plan and device table -- is built
     on the first step of a (geometry, need mask) and only launched afterwards; frozen layers are not in it, and a block
-    with nothing to compute launches nothing."""
+    with nothing to compute launches nothing.  ``precision`` 2: the same table on the bf16 launch."""
     B, C0, H, W, g, mid, Ct = geom
     sizes = []
     for i, (n1, n2) in enumerate(mask):
@@ -862,7 +939,7 @@ def _dense_wgrad_batch(geom, mask, buf, G, T1, D_T1, stats, wws):
                                      c_out=g, ksize=3, pre=(stats[i, 6, :mid], stats[i, 7, :mid]), pre_relu=True))
                 at += g * 9 * mid
         batch = _DENSE_WGRAD_BATCHES.put(key, ops.WgradBatch(problems, bases, wws.numel(), tag="enc.wgrad"))
-    return batch.run(bases, wws)
+    return batch.run(bases, wws, precision=precision)
 
 
 def _dense_block(block, x, batched_wgrad=False):
@@ -935,7 +1012,7 @@ def densenet_encoder_forward(enc, x):
     begin_step()
     taps = [x]
     cur = x.float().contiguous(memory_format=torch.channels_last)
-    with _deferred_batch_counts():
+    with _deferred_batch_counts(), precision_scope(getattr(enc, "train_precision", "fp32")):
         _run_children(list(enc.base_model.named_children()), cur,
                       tapped=lambda name: any(fragment in name for fragment in enc.feat_names), taps=taps,
                       batched_wgrad=bool(getattr(enc, "batched_wgrad", False)))
@@ -967,7 +1044,7 @@ def resnet_encoder_forward(enc, x):
     cur = x.float().contiguous(memory_format=torch.channels_last)
     c1 = m.conv1
     native = bool(getattr(enc, "grouped_conv_train", False))
-    with _deferred_batch_counts():
+    with _deferred_batch_counts(), precision_scope(getattr(enc, "train_precision", "fp32")):
         cur = _bn(conv2d(cur, c1.weight, padding=c1.padding[0], stride=c1.stride[0], tag="enc"), m.bn1, relu=True)
         taps = [x, cur]
         cur = m.maxpool(cur)

@@ -545,6 +545,23 @@ int  bts_conv_wgrad_batch_plan_f32(const bts_conv_wgrad_desc* descs, int n, cons
 int  bts_conv_wgrad_batch_f32(const void* table_host, const void* table_dev, int n, const void* const* bases, int n_bases,
                               float* ws, bts_stream_t stream);
 
+/* The weight gradient with bf16 operands and fp32 accumulation (the training step's opt-in train_precision "bf16"):
+ *
+ *   dw[co][tap][ci] = sum_p bf16(dy[p][co]) * bf16(x'[q(p,tap)][ci])
+ *
+ * x' is the gathered input after pre_scale / pre_shift / pre_relu with the zero padding applied after that prologue; both
+ * operands are rounded to the nearest bf16 (ties to even) on their way to the matrix cores (v_mfma_f32_32x32x16_bf16),
+ * products of bf16 pairs are exact in fp32 and the sums are fp32.  Everything in memory stays fp32.  Descriptor, checks,
+ * tile, split, pix_per_split, workspace use and the fixed-order split sum are EXACTLY those of bts_conv_wgrad_f32 -- a
+ * value that is representable in bf16 gives the fp32 entry point's result up to the order of the fp32 additions inside a
+ * split.  bts_conv_wgrad_bf16_plan_f32 answers what bts_conv_wgrad_plan_f32 answers, or BTS_ERR_UNSUPPORTED for a shape
+ * class the bf16 body is not offered for (none today): the caller then launches bts_conv_wgrad_f32.
+ * bts_conv_wgrad_batch_bf16_f32 consumes the table of bts_conv_wgrad_batch_plan_f32 unchanged. */
+int  bts_conv_wgrad_bf16_f32(const bts_conv_wgrad_desc* desc, bts_stream_t stream);
+int  bts_conv_wgrad_bf16_plan_f32(const bts_conv_wgrad_desc* desc, int* bm, int* bn, long* split, long* pix_per_split);
+int  bts_conv_wgrad_batch_bf16_f32(const void* table_host, const void* table_dev, int n, const void* const* bases, int n_bases,
+                                   float* ws, bts_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Sub-pixel upconv in the training step (reference upconv, pytorch/bts.py:83-94: nearest-2x + 3x3 convolution).  With
  * S_0 = [[1,0,0],[0,1,1]], S_1 = [[1,1,0],[0,0,1]] and the class filters g_(py,px) = S_py w S_px^T (2x2, the filters of

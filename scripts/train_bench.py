@@ -46,6 +46,9 @@ def main():
     ap.add_argument("--grouped-native", action="store_true",
                     help="ResNeXt's stride-1 grouped 3x3 layers on the native grouped kernels in all three passes "
                          "(BtsModel.grouped_conv_train)")
+    ap.add_argument("--train-precision", choices=("fp32", "bf16"), default="fp32",
+                    help="bf16: bf16 operands, fp32 accumulation in the forward, input-gradient and weight-gradient pass of "
+                         "the convolutions (BtsModel.train_precision)")
     a = ap.parse_args()
     # BASELINE config 5 (B=32 over 8 GPUs = 4 per GPU, DDP): launch with
     #   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 scripts/train_bench.py
@@ -70,6 +73,7 @@ def main():
     model.batched_wgrad = a.batched_wgrad
     model.subpixel_upconv_train = a.subpixel_upconv
     model.grouped_conv_train = a.grouped_native
+    model.train_precision = a.train_precision
     loss_fn = M.silog_loss(0.85, native=a.native_loss)
     if not a.no_freeze:
         trainer.set_misc(model, a.encoder)          # the reference freezes the stem conv and the encoder norm affines
@@ -127,7 +131,8 @@ def main():
                loss="silog native (HIP)" if a.native_loss else "silog torch",
                config=dict(encoder=a.encoder, batch_per_gpu=B, height=H, width=W, decoder_only=a.decoder_only,
                            fused_reduc=a.fused_reduc, batched_wgrad=a.batched_wgrad, native_optim=a.native_optim,
-                           subpixel_upconv=a.subpixel_upconv, grouped_native=a.grouped_native),
+                           subpixel_upconv=a.subpixel_upconv, grouped_native=a.grouped_native,
+                           train_precision=a.train_precision),
                peak_mem_gb=torch.cuda.max_memory_allocated() / 2**30)
     if a.trace:
         tr = ops.KernelTrace()

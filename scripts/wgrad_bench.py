@@ -1,11 +1,17 @@
 #!/usr/bin/env python3
 """Per-shape timing of bts_conv_wgrad_f32 on the training configuration's layers (B=4, 352x704, DenseNet161-BTS), then
 one line per DenseNet161 block: the block's 2*L weight gradients as single launches against one batched launch
-(bts_conv_wgrad_batch_f32) on the same buffers."""
+(bts_conv_wgrad_batch_f32) on the same buffers.
+
+``--precision fp32 | bf16 | both`` (default fp32): the arithmetic -- "bf16" times bts_conv_wgrad_bf16_f32 /
+bts_conv_wgrad_batch_bf16_f32 (train_precision "bf16"), "both" times the two in turn on the same buffers and prints the
+ratio.  ``--json PATH`` writes the per-shape and per-block figures."""
+import argparse
+import json
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from bts_amd import ops
+from bts_amd import _lib, ops
 
 SHAPES = [  # name, B, h, w, cin, cout, k, dil, up
     ("b1 1x1", 4, 88, 176, 192, 192, 1, 1, 1), ("b1 3x3", 4, 88, 176, 192, 48, 3, 1, 1),
@@ -36,7 +42,7 @@ def _time(fn, n=10):
     return s.elapsed_time(e) / n * 1e3
 
 
-def blocks(dev, ws, B=4, g=48, mid=192):
+def blocks(dev, ws, precisions, out, B=4, g=48, mid=192):
     """The problems train._DenseBlockFn hands the weight-gradient kernels, on buffers laid out as it lays them out."""
     for name, H, W, C0, L in BLOCKS:
         npix, Ct = B * H * W, C0 + L * g
@@ -56,42 +62,54 @@ def blocks(dev, ws, B=4, g=48, mid=192):
         bases = [buf, G, T1, D_T1, stats, DW]
         batch = ops.WgradBatch(problems, bases, ws.numel())
 
-        def singles():
+        def singles(pr):
             for p in problems:
-                ops.conv_wgrad(p["x"], B, H, W, p["c_in"], p["dy"], p["c_out"], p["ksize"], ws=ws, pre=p["pre"], pre_relu=True)
+                ops.conv_wgrad(p["x"], B, H, W, p["c_in"], p["dy"], p["c_out"], p["ksize"], ws=ws, pre=p["pre"], pre_relu=True,
+                               precision=pr)
 
-        us_single, us_batch = _time(singles), _time(lambda: batch.run(bases, ws))
         splits = sorted({p[2] for p in batch.plan})
         wgs = sum(-(-p["c_out"] // pl[0]) * -(-(p["c_in"] * p["ksize"] ** 2) // pl[1]) * pl[2] for p, pl in zip(problems, batch.plan))
-        print("%-8s px %6d  %2d problems  single launches %8.1f us  one batch %8.1f us  (x%.2f)  batch: %d workgroups, split %s, "
-              "%.1f MB of partials" % (name, npix, len(problems), us_single, us_batch, us_single / us_batch, wgs,
-                                       "-".join(str(v) for v in (splits[0], splits[-1])) if len(splits) > 1 else splits[0],
-                                       4e-6 * batch.ws_used), flush=True)
+        row = dict(name=name, pixels=npix, problems=len(problems), workgroups=wgs)
+        for pr in precisions:
+            us_single, us_batch = _time(lambda: singles(pr)), _time(lambda: batch.run(bases, ws, precision=pr))
+            row[pr] = dict(single_us=us_single, batch_us=us_batch)
+            print("%-8s %-4s px %6d  %2d problems  single launches %8.1f us  one batch %8.1f us  (x%.2f)  batch: %d workgroups, "
+                  "split %s, %.1f MB of partials" % (name, pr, npix, len(problems), us_single, us_batch, us_single / us_batch, wgs,
+                                                     "-".join(str(v) for v in (splits[0], splits[-1])) if len(splits) > 1 else splits[0],
+                                                     4e-6 * batch.ws_used), flush=True)
+        out.append(row)
         del buf, G, T1, D_T1, stats, DW, batch, problems
 
 
 def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--precision", choices=("fp32", "bf16", "both"), default="fp32")
+    ap.add_argument("--json", default=None)
+    a = ap.parse_args()
+    precisions = ("fp32", "bf16") if a.precision == "both" else (a.precision,)
     dev = torch.device("cuda:0")
     ws = torch.empty(48 << 20, device=dev)
+    shapes, per_block = [], []
     for name, B, h, w, cin, cout, k, dil, up in SHAPES:
         H, W = h * up, w * up
         x = torch.randn(B * h * w, cin, device=dev)
         dy = torch.randn(B * H * W, cout, device=dev)
-        for _ in range(3):
-            ops.conv_wgrad(x, B, h, w, cin, dy, cout, k, dil=dil, up=up, ws=ws)
-        torch.cuda.synchronize()
-        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        n = 20
-        s.record()
-        for _ in range(n):
-            ops.conv_wgrad(x, B, h, w, cin, dy, cout, k, dil=dil, up=up, ws=ws)
-        e.record()
-        torch.cuda.synchronize()
-        us = s.elapsed_time(e) / n * 1e3
         fl = 2.0 * B * H * W * cout * cin * k * k
         by = 4.0 * (B * h * w * cin + B * H * W * cout)
-        print("%-14s px %7d  M=%4d N=%6d  %8.1f us  %6.1f TF/s  %6.0f GB/s" % (name, B * H * W, cout, cin * k * k, us, fl / us / 1e6, by / us / 1e3), flush=True)
-    blocks(dev, ws)
+        bm, bn, split, pps = ops.conv_wgrad_plan(B, h, w, cin, cout, k, dil=dil, up=up, ws_floats=ws.numel())
+        row = dict(name=name, pixels=B * H * W, M=cout, N=cin * k * k, tile=[bm, bn], split=split)
+        for pr in precisions:
+            us = _time(lambda: ops.conv_wgrad(x, B, h, w, cin, dy, cout, k, dil=dil, up=up, ws=ws, precision=pr), n=20)
+            row[pr] = us
+            print("%-14s %-4s px %7d  M=%4d N=%6d  tile %3dx%3d split %4d  %8.1f us  %6.1f TF/s  %6.0f GB/s"
+                  % (name, pr, B * H * W, cout, cin * k * k, bm, bn, split, us, fl / us / 1e6, by / us / 1e3), flush=True)
+        if len(precisions) == 2:
+            print("%-14s fp32 / bf16 = %.2f" % (name, row["fp32"] / row["bf16"]), flush=True)
+        shapes.append(row)
+    blocks(dev, ws, precisions, per_block)
+    if a.json:
+        with open(a.json, "w") as fh:
+            json.dump(dict(source_hash=_lib.source_hash(), shapes=shapes, blocks=per_block), fh, indent=1)
 
 if __name__ == "__main__":
     main()
