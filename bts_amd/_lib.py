@@ -128,6 +128,9 @@ ABI: Dict[str, Entry] = {
     "bts_conv_grouped_wgrad_plan": _query(_i, _i, _i, _i, _i, _i, _l64, _pi, _pl),
     "bts_conv1x1_bf16_fwd_f32": _launch(_vp, _l64, _l64, _i, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _l64, _vp),
     "bts_conv1x1_bf16_plan": _query(_i, _i, _i, _i, _i, _i, _pi, _pi, _pl),
+    "bts_conv1x1_bf16_wide_fwd_f32": _launch(_vp, _l64, _l64, _i, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _l64, _i, _vp, _l64,
+                                             _vp, _l64, _i, _vp),
+    "bts_conv1x1_bf16_wide_plan": _query(_i, _i, _i, _i, _i, _i, _i, _pi, _pi, _pl),
     "bts_conv_plan_f32": _query(_i, _conv, _pi, _pi, _pi),
     "bts_conv_plan_ksteps_f32": _query(_i, _conv, _pl, _pl),
     "bts_conv_wgrad_f32": _launch(_wgrad, _vp),

@@ -736,8 +736,10 @@ class BtsModel(nn.Module):
         self.bf16_wide_1x1 = False          # DenseNet161's bottleneck 1x1 layers (eval forward, conv_precision "bf16" only): True runs
                                             # the ones ops.conv1x1_bf16_plan accepts on the wide bf16 tile
                                             # (ops.conv1x1_bf16_forward); nothing changes under "fp32" / "bf16x3", for
-                                            # transitions, ASPP, ResNe(X)t or DenseNet121.  A plan cannot replay the launch: with
-                                            # use_plans the bf16 forward raises BtsHipError
+                                            # transitions, ASPP, ResNe(X)t or DenseNet121.  "all": those, plus every 1x1 layer
+                                            # ops.conv1x1_bf16_wide_plan accepts (ops.conv1x1_bf16_wide_forward: DenseNet121's
+                                            # 128-wide bottlenecks; ResNe(X)t's conv1, conv3 and stride-1 downsample).  A plan
+                                            # cannot replay the launch: with use_plans the bf16 forward raises BtsHipError
         self._plans = PlanCache()
         self._fp_state = [0, None, -1]      # workspace.tensor_fingerprint: [structure token, cached tensor list, its token]
         self._origin = [self]               # reaches DataParallel replicas through replicate()'s shallow __dict__ copy
@@ -770,6 +772,18 @@ class BtsModel(nn.Module):
     @bf16_tail_convs.setter
     def bf16_tail_convs(self, on: bool):
         self.decoder.bf16_tail_convs = bool(on)
+
+    @property
+    def bf16_wide_1x1(self):
+        """False (default), True or "all": which 1x1 encoder layers an eval forward under conv_precision "bf16" runs on the
+        wide bf16 tile (see __init__); any other value raises BtsHipError."""
+        return self.__dict__.get("_bf16_wide_1x1", False)
+
+    @bf16_wide_1x1.setter
+    def bf16_wide_1x1(self, value):
+        if not (isinstance(value, (bool, int)) and value in (0, 1)) and value != "all":
+            raise BtsHipError("BtsModel.bf16_wide_1x1 must be False, True or \"all\", got %r" % (value,))
+        self.__dict__["_bf16_wide_1x1"] = value if value == "all" else bool(value)
 
     @property
     def grouped_conv_train(self) -> bool:
@@ -811,9 +825,9 @@ class BtsModel(nn.Module):
     def _forward_native(self, x, focal, slot, outs=None, abs_mins=None):
         if self.use_plans and ops._trace is None and not _lib_mod.is_recording():
             if (self.bf16_wide_1x1 and ops.current_launch_config()[1] == 2
-                    and not isinstance(self.encoder.base_model, encoders.ResNet)):
-                raise BtsHipError("BtsModel: bf16_wide_1x1 launches bts_conv1x1_bf16_fwd_f32, which a plan cannot replay; "
-                                  "set use_plans = False or bf16_wide_1x1 = False")
+                    and (self.bf16_wide_1x1 == "all" or not isinstance(self.encoder.base_model, encoders.ResNet))):
+                raise BtsHipError("BtsModel: bf16_wide_1x1 launches bts_conv1x1_bf16_fwd_f32 / bts_conv1x1_bf16_wide_fwd_f32, which a "
+                                  "plan cannot replay; set use_plans = False or bf16_wide_1x1 = False")
             r = self._plans.forward(self, x, focal, slot, outs)
             if abs_mins is not None:
                 dec = self.decoder
@@ -834,8 +848,9 @@ class BtsModel(nn.Module):
         plan.bind(base, key_module=src_base)
         if cls is ResNetHip:
             plan.grouped_conv = self.grouped_conv
+            plan.bf16_wide_1x1 = self.bf16_wide_1x1 == "all"
         else:
-            plan.bf16_wide_1x1 = bool(self.bf16_wide_1x1)
+            plan.bf16_wide_1x1 = self.bf16_wide_1x1
         plan._ws.max_entries = max(plan._ws.max_entries, 2 * int(self.sub_batches))
         B, _, H, W = x.shape
         dec = self.decoder

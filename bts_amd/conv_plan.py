@@ -75,6 +75,12 @@ def wide_1x1_bf16_kernel_name(bn: int = 192) -> str:
     return "conv1x1_bf16_kernel<%d>" % bn
 
 
+def wide_1x1_bf16_tile(c_out: int) -> int:
+    """The tile bts_conv1x1_bf16_wide_fwd_f32 launches for ``bn`` = 0 (csrc/conv_1x1_bf16.inc: c1w_bn; the plan query's *bn
+    for a layer it accepts), for KernelTrace's kernel name."""
+    return 192 if c_out % 192 == 0 else 128
+
+
 def grouped_kernel_name(cg: int) -> str:
     """The kernel bts_conv_grouped_fwd_f32 launches for ``cg`` channels per group (its own entry point: no bts_conv_plan_f32
     kind), as KernelTrace records it."""

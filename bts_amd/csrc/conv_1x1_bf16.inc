@@ -29,7 +29,13 @@
 // workgroups of the CU (three per CU by registers), not by a deeper ring: the K loop is 3 .. 66 steps long.
 //
 // Sum order: ascending k in 16-k MFMA blocks, whatever the grid: a pixel's bits depend neither on npix nor on its
-// position in the launch.
+// position in the launch -- nor on BN.
+//
+// The same body is instantiated at BN = 128 and 256 for the second entry point (bts_conv1x1_bf16_wide_fwd_f32: ResNe(X)t's
+// conv1 / conv3 / stride-1 downsample, DenseNet121's 128-wide bottlenecks), which also has the bottleneck epilogue
+// (conv1x1_bf16_epi_kernel: y = act(e1(acc) + res), the same values to y2 -- bts_conv_desc.res / .y2).  The epilogue is a
+// template flag, so the kernel the first entry point launches is the code it was.  gfx950, registers / waves per SIMD / scratch:
+//   BN 128: 120 / 4 / 0     BN 192: 152 / 3 / 0     BN 256: 188 (epilogue: 189) / 2 / 0;   LDS 2 * BN * 64 B + 8 B per channel.
 struct Conv1x1Bf16Args {
     const float* x; long x_pix_stride; long npix; int c_in;
     const unsigned short* w; int k_pad;           // bf16 [c_out_pad][k_pad]
@@ -38,6 +44,8 @@ struct Conv1x1Bf16Args {
     const float* e1_scale; const float* e1_shift; int act;
     float* y; long y_pix_stride;
     int n_ntiles;
+    const float* res; long res_pix_stride;        // bottleneck epilogue (conv1x1_bf16_epi_kernel only): bts_conv_desc.res / .y2
+    float* y2; long y2_pix_stride;
 };
 
 constexpr int C1B_BM = 128;                       // pixels per workgroup (4 waves x 32)
@@ -48,7 +56,9 @@ template <int BN> inline size_t c1b_lds_bytes(int c_in, bool has_pre) {
 }
 
 // One wave's 32 pixels x BN channels to the NHWC slice: a wave-uniform 64-bit row base plus one per-lane 32-bit offset
-template <int ACT, int TN, typename AccT>
+// EPI: y = act(e1(acc) + res[p][n]) (one fp32 add, after e1 and before the activation), and the same values to y2; either
+// operand may be null.  A residual value is loaded only where its output is stored: rows >= npix are never touched.
+template <int ACT, int TN, bool EPI, typename AccT>
 __device__ __forceinline__ void c1b_store(const Conv1x1Bf16Args& a, const AccT (&acc)[TN], long pix0, int nvalid, int ncol0, int li, int lh) {
     float* const yb = a.y + pix0 * a.y_pix_stride;                                      // wave-uniform
     const int nv = nvalid - 4 * lh;                                                     // slots this lane's half may write
@@ -59,17 +69,42 @@ __device__ __forceinline__ void c1b_store(const Conv1x1Bf16Args& a, const AccT (
         float b1 = a.e1_scale != nullptr ? a.e1_shift[n] : 0.f;
         asm volatile("" : "+v"(s1), "+v"(b1));          // waited for HERE, once (see tail_bf16_store)
         const unsigned lane_y = (unsigned)(4 * lh) * (unsigned)a.y_pix_stride + (unsigned)n;
+        if constexpr (!EPI) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int qu = (r & 3) + 8 * (r >> 2);
-            const float v = act_fn<ACT>(fmaf(acc[j][r], s1, b1));
-            if (qu < nv) (yb + (long)qu * a.y_pix_stride)[lane_y] = v;
+            for (int r = 0; r < 16; ++r) {
+                const int qu = (r & 3) + 8 * (r >> 2);
+                const float v = act_fn<ACT>(fmaf(acc[j][r], s1, b1));
+                if (qu < nv) (yb + (long)qu * a.y_pix_stride)[lane_y] = v;
+            }
+        } else {
+            float rv[16];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {                 // the 16 residual loads of this column in flight together
+                const int qu = (r & 3) + 8 * (r >> 2);
+                rv[r] = 0.f;
+                if (a.res != nullptr && qu < nv) rv[r] = a.res[(pix0 + 4 * lh + qu) * a.res_pix_stride + n];
+            }
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int qu = (r & 3) + 8 * (r >> 2);
+                float v = fmaf(acc[j][r], s1, b1);
+                if (a.res != nullptr) v += rv[r];
+                v = act_fn<ACT>(v);
+                if (qu < nv) {
+                    (yb + (long)qu * a.y_pix_stride)[lane_y] = v;
+                    if (a.y2 != nullptr) a.y2[(pix0 + 4 * lh + qu) * a.y2_pix_stride + n] = v;
+                }
+            }
         }
     }
 }
 
-template <int BN>
-__global__ __launch_bounds__(256, 2) void conv1x1_bf16_kernel(const Conv1x1Bf16Args a) {
+// Workgroups per CU the register file is asked to hold: BN = 128 (64 accumulator registers) four, BN = 192 (96) and
+// BN = 256 (128 + 32 for the B fragments) two -- 192 takes 152 registers and gets three by itself, 256 cannot get three.
+template <int BN> constexpr int c1b_min_wgs_per_cu() { return BN <= 128 ? 4 : 2; }
+
+template <int BN, bool EPI>
+__device__ __forceinline__ void c1b_body(const Conv1x1Bf16Args& a) {
     constexpr int TN = BN / 32, STAGE = c1b_stage_bytes<BN>();
     constexpr int NIW = BN / 16 / 4;                      // DMA wave-instructions per stage and wave (16 rows x 64 B each)
     static_assert(BN % 64 == 0, "the four waves share a stage's DMA evenly");
@@ -196,8 +231,14 @@ __global__ __launch_bounds__(256, 2) void conv1x1_bf16_kernel(const Conv1x1Bf16A
     // ---------------------------------------------------------------- epilogue (NHWC slice)
     const long left = a.npix - pix0;
     const int nvalid = left >= 32 ? 32 : (left > 0 ? (int)left : 0);
-    dispatch_act(a.act, [&](auto act) { c1b_store<decltype(act)::value, TN>(a, acc, pix0, nvalid, n0, li, lh); });
+    dispatch_act(a.act, [&](auto act) { c1b_store<decltype(act)::value, TN, EPI>(a, acc, pix0, nvalid, n0, li, lh); });
 }
+
+template <int BN>
+__global__ __launch_bounds__(256, c1b_min_wgs_per_cu<BN>()) void conv1x1_bf16_kernel(const Conv1x1Bf16Args a) { c1b_body<BN, false>(a); }
+// the same tile with the bottleneck epilogue (a.res and / or a.y2 set)
+template <int BN>
+__global__ __launch_bounds__(256, c1b_min_wgs_per_cu<BN>()) void conv1x1_bf16_epi_kernel(const Conv1x1Bf16Args a) { c1b_body<BN, true>(a); }
 
 // The layers the encoder hands to this kernel under BtsModel.bf16_wide_1x1 (bts_conv1x1_bf16_plan).  Structural: whole
 // 192-channel N tiles, whole 16-k MFMA blocks.  Measured: a declared launch of at least kC1bMinWgs workgroups.
@@ -224,11 +265,57 @@ inline bool c1b_eligible(int H, int W, int c_in, int c_out, int ff, long* wgs_pe
     return (long)ff * *wgs_per_frame >= kC1bMinWgs;
 }
 
+// ---- the other widths (bts_conv1x1_bf16_wide_fwd_f32 / _plan; BtsModel.bf16_wide_1x1 = "all")
+// Structural: whole 128- or 192-channel N tiles, whole 16-k MFMA blocks.  The tile of bn = 0 is a pure function of c_out: 192
+// where it divides c_out (the instantiation measured first), else 128.
+//
+// Source of everything below: profiles/conv1x1_bf16_wide_bench.txt (scripts/conv1x1_bf16_wide_bench.py: isolated launches
+// against the row-tiled bf16 path on the 1x1 layer classes of ResNeXt-101 and ResNet-50 at 416x544 and DenseNet121 at 352x1216,
+// fill_frames 16, as the B = 16 launch and as the B = 4 sub-batch launch; a class enters only if it wins by more than the
+// run-to-run spread at B = 16 and does not lose at B = 4 -- the rule that set kC1bMinWgs).
+//   128 against 256, per width over all of its measured classes: where the tile wins at all, 256 beats 128 at B = 16 on the
+//   forms without a residual (+7 ... +45 %), loses 6-22 % on the accepted conv3 classes (residual epilogue at two waves per
+//   SIMD), and loses 8-37 % at B = 4 on every 52x68 and 26x34 class but one (half the workgroups).  Every width has classes on
+//   which 256 loses at B = 4, so bn = 0 never picks 256; it runs when forced.
+//   Tile 128, declared workgroups = fill_frames x ceil(h w / 128) x c_out / 128, and K = c_in (gain at B = 16 / at B = 4):
+//     enters: 7104 K256 +17 / +32 %; 3552 K64-256 +9...+53 / +26...+70 % (conv1, conv3, conv3 + skip tap, downsample);
+//       3584 K512 +11 / +38 %; 3344 K64-224 +20...+41 / +62...+75 % (DenseNet121 block 1); 1792 K128-512 +15...+28 /
+//       -0.2 (within spread) ...+11 %; 1776 K256 +8 / +14 %
+//     marginal at B = 4, left out: 896 K512 +36 / +1.0 % (within spread), 896 K256 with residual +38 / -1.7 % (loses), 848
+//       K480 +42 / -1.7 % (loses; DenseNet121 block 2) -- although 848 K128 wins +69 / +35 %
+//     stays: K >= 992 wherever it was measured -- 1792 K1024 +9 / -5 %, 896 K1024 +23...+26 / -13...-16 %, 512 K2048 -5...-9 /
+//       -35...-37 %, 224 K992-1024 -4...-7 / -30...-32 %; and at most 512 declared workgroups -- 512 K512 -2 / -31 %, 448 K512
+//       +5 / -8 %, 448 K1024 -5 / -23 %, 128 K2048 -35 / -63 %
+//   kC1wMinWgs = 1024 (four workgroups per CU of the declared launch: what the register file holds of this tile) sits between
+//   the measured edges 896 (marginal) and 1776 (wins); kC1wMaxK = 512 is the largest K measured to win (the next one measured,
+//   992, loses: the K loop is not pipelined deeper than two stages, and nothing else hides a long loop of a small launch).
+//   Also left out although it won in isolation: DenseNet121's block 3 at K 256 (224 workgroups, +70 / +52 %) -- the same block
+//   loses at K 992 and nothing between was measured.
+//   Whole model with these constants (profiles/bf16_wide_1x1_all_bench.json): configs[2] +6.8 %, DenseNet121 +2.5 %, both
+//   outside the spread (0.9 %, 0.7 %).
+//   Tile 192 with a residual was not measured: refused.
+inline bool c1w_supported(int c_in, int c_out) { return c_in > 0 && c_out > 0 && (c_out % 128 == 0 || c_out % 192 == 0) && (c_in % 16) == 0; }
+constexpr long kC1wMinWgs = 1024;
+constexpr int kC1wMaxK = 512;
+inline int c1w_bn(int c_out) { return c_out % 192 == 0 ? 192 : 128; }
+inline bool c1w_eligible(int H, int W, int c_in, int c_out, bool has_res, int ff, int* bn, long* wgs_per_frame) {
+    *wgs_per_frame = 0; *bn = 0;
+    if (H <= 0 || W <= 0 || !c1w_supported(c_in, c_out)) return false;
+    const int tile = c1w_bn(c_out);
+    const long wgs = (((long)H * W + C1B_BM - 1) / C1B_BM) * (c_out / tile);
+    const bool ok = tile == 192 ? (!has_res && (long)ff * wgs >= kC1bMinWgs) : ((long)ff * wgs >= kC1wMinWgs && c_in <= kC1wMaxK);
+    if (!ok) return false;
+    *bn = tile; *wgs_per_frame = wgs;
+    return true;
+}
+
 template <int BN>
 int launch_conv1x1_bf16(Conv1x1Bf16Args a, const ConvRun& r) {
     const long n_mtiles = (a.npix + C1B_BM - 1) / C1B_BM;
     a.n_ntiles = a.c_out / BN;
     const long nwg = n_mtiles * a.n_ntiles;
     const size_t lds = c1b_lds_bytes<BN>(a.c_in, a.pre_scale != nullptr);
+    if (a.res != nullptr || a.y2 != nullptr)
+        return conv_launch<conv1x1_bf16_epi_kernel<BN>>(r, ConvChoice{}, BTS_ERR_UNSUPPORTED, nwg, nwg, 256, lds, a);
     return conv_launch<conv1x1_bf16_kernel<BN>>(r, ConvChoice{}, BTS_ERR_UNSUPPORTED, nwg, nwg, 256, lds, a);
 }

@@ -1302,26 +1302,68 @@ extern "C" int bts_conv1x1_bf16_plan(int h, int w, int c_in, int c_out, int fill
     return 0;
 }
 
-extern "C" int bts_conv1x1_bf16_fwd_f32(const float* x, long x_pix_stride, long npix, int c_in, const void* w_bf16, int k_pad,
-                                        int c_out, int c_out_pad, const float* pre_scale, const float* pre_shift, int pre_relu,
-                                        const float* e1_scale, const float* e1_shift, int act, float* y, long y_pix_stride,
-                                        bts_stream_t stream) {
+// Both wide-1x1 entry points: every check, then the launch at tile width `bn` (192 from the first entry point; the second
+// adds res / y2 and the other widths).  A stride given for a null res / y2 is ignored.
+static int conv1x1_bf16_run(const float* x, long x_pix_stride, long npix, int c_in, const void* w_bf16, int k_pad, int c_out,
+                            int c_out_pad, const float* pre_scale, const float* pre_shift, int pre_relu, const float* e1_scale,
+                            const float* e1_shift, const float* res, long res_pix_stride, int act, float* y, long y_pix_stride,
+                            float* y2, long y2_pix_stride, int bn, bool any_width, bts_stream_t stream) {
     if (!x || !w_bf16 || !y || npix <= 0 || c_in <= 0 || c_out <= 0 || k_pad <= 0 || c_out_pad < c_out) return BTS_ERR_INVALID;
     if ((pre_scale == nullptr) != (pre_shift == nullptr) || !act_e2_ok(act, e1_scale, e1_shift)) return BTS_ERR_INVALID;
     if (!nhwc_view_ok(x, x_pix_stride, c_in) || (y_pix_stride & 3) || y_pix_stride < c_out || ((uintptr_t)y & 3) ||
         ((uintptr_t)w_bf16 & 15) || ((uintptr_t)pre_scale & 3) || ((uintptr_t)pre_shift & 3) || ((uintptr_t)e1_scale & 3) ||
         ((uintptr_t)e1_shift & 3)) return BTS_ERR_INVALID;
-    if (!c1b_supported(c_in, c_out) || (k_pad % BK) || k_pad < c_in) return BTS_ERR_UNSUPPORTED;
+    if (res == nullptr) res_pix_stride = 0;
+    if (y2 == nullptr) y2_pix_stride = 0;
+    if (res != nullptr && ((res_pix_stride & 3) || res_pix_stride < c_out || ((uintptr_t)res & 3))) return BTS_ERR_INVALID;
+    if (y2 != nullptr && ((y2_pix_stride & 3) || y2_pix_stride < c_out || ((uintptr_t)y2 & 3))) return BTS_ERR_INVALID;
+    if (bn != 0 && bn != 128 && bn != 192 && bn != 256) return BTS_ERR_INVALID;
+    if (!(any_width ? c1w_supported(c_in, c_out) : c1b_supported(c_in, c_out)) || (k_pad % BK) || k_pad < c_in) return BTS_ERR_UNSUPPORTED;
+    if (bn == 0) bn = c1w_bn(c_out);
+    if (c_out % bn) return BTS_ERR_UNSUPPORTED;
     // pixel rows are addressed in 64 bits; the kernel adds 32-bit offsets inside a 32-pixel row block and inside the weight
     // plane, and keeps the prologue vectors of all c_in channels in LDS (more workgroups than a grid holds: conv_launch)
-    if (x_pix_stride >= (1L << 26) || y_pix_stride >= (1L << 26) || !fits_u32((double)c_out_pad * (double)k_pad) ||
-        c1b_lds_bytes<192>(c_in, true) > 160 * 1024) return BTS_ERR_UNSUPPORTED;
+    const size_t lds = bn == 128 ? c1b_lds_bytes<128>(c_in, true) : bn == 192 ? c1b_lds_bytes<192>(c_in, true) : c1b_lds_bytes<256>(c_in, true);
+    if (x_pix_stride >= (1L << 26) || y_pix_stride >= (1L << 26) || res_pix_stride >= (1L << 26) || y2_pix_stride >= (1L << 26) ||
+        !fits_u32((double)c_out_pad * (double)k_pad) || lds > 160 * 1024) return BTS_ERR_UNSUPPORTED;
     Conv1x1Bf16Args a;
     a.x = x; a.x_pix_stride = x_pix_stride; a.npix = npix; a.c_in = c_in;
     a.w = static_cast<const unsigned short*>(w_bf16); a.k_pad = k_pad; a.c_out = c_out; a.c_out_pad = c_out_pad;
     a.pre_scale = pre_scale; a.pre_shift = pre_shift; a.pre_relu = pre_relu;
     a.e1_scale = e1_scale; a.e1_shift = e1_shift; a.act = act; a.y = y; a.y_pix_stride = y_pix_stride; a.n_ntiles = 0;
-    return launch_conv1x1_bf16<192>(a, launch_on(stream));
+    a.res = res; a.res_pix_stride = res_pix_stride; a.y2 = y2; a.y2_pix_stride = y2_pix_stride;
+    const ConvRun run = launch_on(stream);
+    return bn == 128 ? launch_conv1x1_bf16<128>(a, run) : bn == 192 ? launch_conv1x1_bf16<192>(a, run) : launch_conv1x1_bf16<256>(a, run);
+}
+
+extern "C" int bts_conv1x1_bf16_fwd_f32(const float* x, long x_pix_stride, long npix, int c_in, const void* w_bf16, int k_pad,
+                                        int c_out, int c_out_pad, const float* pre_scale, const float* pre_shift, int pre_relu,
+                                        const float* e1_scale, const float* e1_shift, int act, float* y, long y_pix_stride,
+                                        bts_stream_t stream) {
+    return conv1x1_bf16_run(x, x_pix_stride, npix, c_in, w_bf16, k_pad, c_out, c_out_pad, pre_scale, pre_shift, pre_relu, e1_scale,
+                            e1_shift, nullptr, 0, act, y, y_pix_stride, nullptr, 0, 192, false, stream);
+}
+
+// ---- the same tile at 128 / 192 / 256 output channels per workgroup with the bottleneck epilogue (res, y2): ResNe(X)t's
+//      conv1 / conv3 / stride-1 downsample 1x1 layers and DenseNet121's bottlenecks under BtsModel.bf16_wide_1x1 = "all"
+extern "C" int bts_conv1x1_bf16_wide_plan(int h, int w, int c_in, int c_out, int has_res, int fill_frames, int* bm, int* bn,
+                                          long* workgroups) {
+    int ff, prec;
+    if (!bm || !bn || !workgroups || !resolve_declaration(fill_frames, 0, &ff, &prec)) return BTS_ERR_INVALID;
+    long wgs = 0;
+    int tile = 0;
+    const bool ok = c1w_eligible(h, w, c_in, c_out, has_res != 0, ff, &tile, &wgs);
+    *bm = ok ? C1B_BM : 0; *bn = ok ? tile : 0; *workgroups = ok ? wgs : 0;
+    return 0;
+}
+
+extern "C" int bts_conv1x1_bf16_wide_fwd_f32(const float* x, long x_pix_stride, long npix, int c_in, const void* w_bf16, int k_pad,
+                                             int c_out, int c_out_pad, const float* pre_scale, const float* pre_shift, int pre_relu,
+                                             const float* e1_scale, const float* e1_shift, const float* res, long res_pix_stride,
+                                             int act, float* y, long y_pix_stride, float* y2, long y2_pix_stride, int bn,
+                                             bts_stream_t stream) {
+    return conv1x1_bf16_run(x, x_pix_stride, npix, c_in, w_bf16, k_pad, c_out, c_out_pad, pre_scale, pre_shift, pre_relu, e1_scale,
+                            e1_shift, res, res_pix_stride, act, y, y_pix_stride, y2, y2_pix_stride, bn, true, stream);
 }
 
 // ---- conv1 (32 features + planar tail -> 32, NCHW) as a fused Winograd F(2x2,3x3) kernel (conv_wino_tail.inc): its own opt-in

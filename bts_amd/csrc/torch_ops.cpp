@@ -434,6 +434,63 @@ void conv1x1_bf16(const Tensor& x, const Tensor& w_plane, OptTensor pre_scale, O
                                       ps, pb, (int)(pre_relu != 0), es, eb, (int)act, y.data_ptr<float>(), ys, current_stream()), op);
 }
 
+// ---------------------------------------------------------- wide 1x1, bf16 operands, 128 / 192 / 256 wide, bottleneck epilogue
+// act(e1(conv1x1(bf16(pre(x)))) + res), also written to y2, as one launch of bts_conv1x1_bf16_wide_fwd_f32.  The operands of
+// conv1x1_bf16 above, plus res / y2: optional [npix, c_out] NHWC views.  geom = {npix, c_in, c_out, pre_relu, act, bn}.
+void conv1x1_bf16_wide(const Tensor& x, const Tensor& w_plane, OptTensor pre_scale, OptTensor pre_shift, OptTensor e1_scale,
+                       OptTensor e1_shift, OptTensor res, Tensor y, OptTensor y2, std::vector<int64_t> geom) {
+    const char* op = "bts_hip::conv1x1_bf16_wide";
+    TORCH_CHECK(geom.size() == 6, op, ": geom must hold 6 integers, got ", geom.size());
+    const int64_t npix = geom[0], c_in = geom[1], c_out = geom[2], pre_relu = geom[3], act = geom[4], bn = geom[5];
+    TORCH_CHECK(npix > 0 && c_in > 0 && c_out > 0, op, ": non-positive dimension");
+    TORCH_CHECK(c_in % 16 == 0 && (c_out % 128 == 0 || c_out % 192 == 0), op,
+                ": needs c_in % 16 == 0 and c_out a multiple of 128 or 192, got ", c_in, " -> ", c_out);
+    TORCH_CHECK(bn == 0 || ((bn == 128 || bn == 192 || bn == 256) && c_out % bn == 0), op,
+                ": bn must be 0 or one of 128 / 192 / 256 that divides c_out, got ", bn);
+    const long xs = rows2d_stride(x, op, "x"), ys = rows2d_stride(y, op, "y");
+    TORCH_CHECK(w_plane.is_cuda(), op, ": w_plane must be a CUDA(ROCm) tensor (no CPU fallback)");
+    TORCH_CHECK(w_plane.scalar_type() == at::kShort || w_plane.scalar_type() == at::kBFloat16, op,
+                ": w_plane must hold bf16 bits (int16 from ops.round_bf16, or bfloat16), got ", w_plane.scalar_type());
+    same_device(x, w_plane, op, "w_plane");
+    same_device(x, y, op, "y");
+    TORCH_CHECK(x.size(0) == npix && x.size(1) >= c_in, op, ": x (", x.sizes(), ") is not a [npix, >= c_in] view");
+    TORCH_CHECK(y.size(0) == npix && y.size(1) == c_out, op, ": y (", y.sizes(), ") is not a [npix, c_out] view");
+    auto view = [&](const OptTensor& t, const char* what, long* stride) -> float* {
+        *stride = 0;
+        if (!(t.has_value() && t->defined())) return nullptr;
+        *stride = rows2d_stride(*t, op, what);
+        same_device(x, *t, op, what);
+        TORCH_CHECK(t->size(0) == npix && t->size(1) == c_out, op, ": ", what, " (", t->sizes(), ") is not a [npix, c_out] view");
+        return t->data_ptr<float>();
+    };
+    long rs = 0, y2s = 0;
+    const float* rp = view(res, "res", &rs);
+    float* y2p = view(y2, "y2", &y2s);
+    const int64_t wd = w_plane.dim();
+    TORCH_CHECK(w_plane.is_contiguous() && (wd == 2 || (wd == 3 && w_plane.size(0) == 1)), op,
+                ": w_plane must be contiguous [c_out_pad, k_pad] or [1, c_out_pad, k_pad] (ops.round_bf16), got ", w_plane.sizes());
+    const int64_t c_out_pad = w_plane.size(wd - 2), k_pad = w_plane.size(wd - 1);
+    TORCH_CHECK(c_out_pad >= c_out && k_pad >= c_in && k_pad % 32 == 0, op, ": w_plane ", w_plane.sizes(), " does not hold ", c_out, " rows of ",
+                c_in, " channels padded to a multiple of 32");
+    TORCH_CHECK(act >= 0 && act <= 2, op, ": act must be 0 (none), 1 (ReLU) or 2 (ELU), got ", act);
+    auto vec = [&](const OptTensor& t, const char* what, int64_t n) -> const float* {
+        if (!(t.has_value() && t->defined())) return nullptr;
+        need_f32_cuda(*t, op, what);
+        same_device(x, *t, op, what);
+        TORCH_CHECK(t->is_contiguous() && t->numel() >= n, op, ": ", what, " must be a contiguous vector of at least ", n, " floats");
+        return t->data_ptr<float>();
+    };
+    const float* ps = vec(pre_scale, "pre_scale", c_in);
+    const float* pb = vec(pre_shift, "pre_shift", c_in);
+    const float* es = vec(e1_scale, "e1_scale", c_out);
+    const float* eb = vec(e1_shift, "e1_shift", c_out);
+    TORCH_CHECK((ps == nullptr) == (pb == nullptr) && (es == nullptr) == (eb == nullptr), op, ": give both vectors of an affine or neither");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+    check_rc(bts_conv1x1_bf16_wide_fwd_f32(x.data_ptr<float>(), xs, (long)npix, (int)c_in, w_plane.data_ptr(), (int)k_pad, (int)c_out,
+                                           (int)c_out_pad, ps, pb, (int)(pre_relu != 0), es, eb, rp, rs, (int)act, y.data_ptr<float>(), ys,
+                                           y2p, y2s, (int)bn, current_stream()), op);
+}
+
 // ------------------------------------------------------------------------------------------------------ training losses
 // silog_loss / depth_l1_loss (pytorch/bts.py:41-63) over the valid pixels of the whole batch, csrc/loss.hip: no boolean gather, no host
 // sync.  kind 0 = silog (param = variance_focus), 1 = asymmetric L1 (param = inbalance_to_closer); mask bool / uint8 or None (gt > gt_min).
@@ -507,6 +564,8 @@ TORCH_LIBRARY(bts_hip, m) {
     m.def("conv_tail_bf16(Tensor x, Tensor w_main, Tensor w_tail, Tensor tail, Tensor? e2_scale, Tensor? e2_shift, Tensor(a!) y, int[] geom) -> ()");
     m.def("conv1x1_bf16(Tensor x, Tensor w_plane, Tensor? pre_scale, Tensor? pre_shift, Tensor? e1_scale, Tensor? e1_shift, Tensor(a!) y, "
           "int[] geom) -> ()");
+    m.def("conv1x1_bf16_wide(Tensor x, Tensor w_plane, Tensor? pre_scale, Tensor? pre_shift, Tensor? e1_scale, Tensor? e1_shift, Tensor? res, "
+          "Tensor(a!) y, Tensor(b!)? y2, int[] geom) -> ()");
     m.def("depth_loss(Tensor est, Tensor gt, Tensor? mask, float gt_min, int kind, float param) -> (Tensor loss, Tensor stats)");
     m.def("depth_loss_backward(Tensor est, Tensor gt, Tensor? mask, float gt_min, int kind, float param, Tensor stats, Tensor grad_loss) -> Tensor");
 }
@@ -523,6 +582,7 @@ TORCH_LIBRARY_IMPL(bts_hip, CUDA, m) {
     m.impl("upconv_up9", &upconv_up9);
     m.impl("conv_tail_bf16", &conv_tail_bf16);
     m.impl("conv1x1_bf16", &conv1x1_bf16);
+    m.impl("conv1x1_bf16_wide", &conv1x1_bf16_wide);
     m.impl("depth_loss", &depth_loss);
     m.impl("depth_loss_backward", &depth_loss_backward);
 }

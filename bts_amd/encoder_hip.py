@@ -44,7 +44,8 @@ class DenseNetHip:
     ``bf16_wide_1x1`` (BtsModel.bf16_wide_1x1 sets it): True runs the bottleneck 1x1 of every dense layer that
     ops.conv1x1_bf16_plan accepts on the wide bf16 tile (ops.conv1x1_bf16_forward: 192 output channels per workgroup, the
     pre-rounded weight plane) -- under the bf16 launch precision only; fp32 / bf16x3 forwards, transitions and bottlenecks of
-    another width (DenseNet121: 128) stay on ops.conv_forward whatever the switch says."""
+    another width (DenseNet121: 128) stay on ops.conv_forward.  "all": also every bottleneck ops.conv1x1_bf16_wide_plan accepts
+    (ops.conv1x1_bf16_wide_forward: DenseNet121's 128-wide ones); transitions stay."""
 
     def __init__(self, features: nn.Sequential, key_module: Optional[nn.Module] = None):
         self.features = features
@@ -158,7 +159,7 @@ class DenseNetHip:
             if skip_dst[i] is None:
                 skip_dst[i] = torch.empty((B * hs[i] * wss[i], taps_c[i]), dtype=torch.float32, device=dev)
         RELU = ops.ACT_RELU
-        wide_bf16 = bool(self.bf16_wide_1x1) and ops.current_launch_config()[1] == 2
+        wide_bf16 = self.bf16_wide_1x1 if ops.current_launch_config()[1] == 2 else False
 
         # stem: conv0 7x7/2 + norm0 + relu0 -> skip0 slot; pool0 -> block-1 prefix (+ skip1 slot)
         ops.nchw_to_nhwc(x, ws["img"][:, :3])
@@ -178,6 +179,12 @@ class DenseNetHip:
                     wb = ops._derived_weight(L["w1"], "_bts_round1", ops.round_bf16)      # cached on the packed weight
                     ops.conv1x1_bf16_forward(buf[:, :cin], B * h * w, cin, wb, self.c_mid, mid, pre=L["pre"], pre_relu=True,
                                              e1=L["e1"], act=RELU, tag="enc_b%d_1x1" % (bi + 1))
+                elif wide_bf16 == "all" and ops.conv1x1_bf16_wide_plan(h, w, cin, self.c_mid).eligible:
+                    if not P.get("planes_made"):
+                        self._round_bottleneck_planes(P, dev)
+                    wb = ops._derived_weight(L["w1"], "_bts_round1", ops.round_bf16)
+                    ops.conv1x1_bf16_wide_forward(buf[:, :cin], B * h * w, cin, wb, self.c_mid, mid, pre=L["pre"], pre_relu=True,
+                                                  e1=L["e1"], act=RELU, tag="enc_b%d_1x1" % (bi + 1))
                 else:
                     ops.conv_forward(buf[:, :cin], B, h, w, L["w1"], self.c_mid, 1, pre=L["pre"], pre_relu=True, e1=L["e1"],
                                      act=RELU, y2d=mid, tag="enc_b%d_1x1" % (bi + 1), splitk_ws=ws["splitk"])
@@ -222,13 +229,19 @@ class ResNetHip:
     (ops.conv_grouped_forward, 16-channel MFMA blocks) on the layers ops.conv_grouped_plan finds eligible; "native" = on
     every layer its entry point supports (stride 1, at most 16 channels per group, width % 64 == 0, fp32 launch config).
     Stride-2 blocks, groups of 32 / 64 channels (nothing redundant to remove) and the bf16 / bf16x3 precisions stay on
-    bundles in every mode; the training graph (bts_amd/train.py) never reads the attribute."""
+    bundles in every mode; the training graph (bts_amd/train.py) never reads the attribute.
+
+    ``bf16_wide_1x1`` (BtsModel sets it, True for its "all"): under the bf16 launch precision conv1, conv3 (identity, final ReLU
+    and skip tap in the epilogue) and a stride-1 downsample 1x1 run on the wide bf16 tile (ops.conv1x1_bf16_wide_forward)
+    wherever ops.conv1x1_bf16_wide_plan accepts the layer; stride-2 downsamples, the 3x3 / grouped layers, the stem and widths
+    that are no multiple of 128 (ResNet-50/101's 64-wide layer-1 conv1) stay on ops.conv_forward."""
 
     GROUPED_MODES = ("bundles", "auto", "native")
 
     def __init__(self, model: nn.Module, key_module: Optional[nn.Module] = None):
         self.model = model
         self.grouped_conv = "bundles"
+        self.bf16_wide_1x1 = False
         self.key_module = key_module if key_module is not None else model
         self._pack = None
         self._pack_key = None
@@ -291,6 +304,28 @@ class ResNetHip:
                     b["w2n"] = ops.pack_grouped_native(b["conv2"].weight.detach(), b["groups"])
         torch.cuda.current_stream(device).synchronize()
 
+    def _round_1x1_planes(self, P, device):
+        """The one-plane bf16 form (ops.round_bf16, cached on the packed weight as ``_bts_round1``) of every 1x1 weight the
+        wide bf16 tile may take -- conv1, conv3, stride-1 downsamples -- all at once on the first forward that needs one,
+        and finished before this returns: see DenseNetHip._round_bottleneck_planes."""
+        for blocks in P["layers"]:
+            for b in blocks:
+                for wp in (b["w1"], b["w3"]) + ((b["down"]["w"],) if b["down"] is not None and b["down"]["stride"] == 1 else ()):
+                    ops._derived_weight(wp, "_bts_round1", ops.round_bf16)
+        torch.cuda.current_stream(device).synchronize()
+        P["planes_made"] = True
+
+    def _wide_1x1(self, P, device, x2d, npix, h, w, c_in, wp, c_out, e1, act, y2d, tag, res2d=None, y2_2d=None) -> bool:
+        """Run this 1x1 layer (input map h x w) on the wide bf16 tile if ops.conv1x1_bf16_wide_plan accepts it; False: the caller
+        runs it on ops.conv_forward."""
+        if c_in % 16 or not ops.conv1x1_bf16_wide_plan(h, w, c_in, c_out, has_res=res2d is not None).eligible:
+            return False
+        if not P.get("planes_made"):
+            self._round_1x1_planes(P, device)
+        plane = ops._derived_weight(wp, "_bts_round1", ops.round_bf16)         # cached on the packed weight
+        ops.conv1x1_bf16_wide_forward(x2d, npix, c_in, plane, c_out, y2d, e1=e1, act=act, res2d=res2d, y2_2d=y2_2d, tag=tag)
+        return True
+
     def _grouped_native(self, b, h, w) -> bool:
         """Does this block's grouped 3x3 (input map h x w) take the native kernel under ``self.grouped_conv``?"""
         mode = self.grouped_conv
@@ -339,6 +374,7 @@ class ResNetHip:
                 skip_dst[i] = torch.empty((B * hs[i] * wss[i], taps_c[i]), dtype=torch.float32, device=dev)
         RELU = ops.ACT_RELU
         sk = ws["splitk"]
+        wide = bool(self.bf16_wide_1x1) and ops.current_launch_config()[1] == 2
 
         ops.nchw_to_nhwc(x, ws["img"][:, :3])
         ops.conv_forward(ws["img"], B, H, W, P["stem"]["w"], self.c_stem, 7, stride=2, pad=3, e1=P["stem"]["e1"], act=RELU,
@@ -352,8 +388,11 @@ class ResNetHip:
                 ho, wo = h // s, w // s
                 t1 = ws["t1_%d" % li][: B * h * w]
                 t2 = ws["t2_%d" % li][: B * ho * wo]
-                ops.conv_forward(cur, B, h, w, b["w1"], b["width"], 1, e1=b["e1"], act=RELU, y2d=t1, tag=tag + "_1x1",
-                                 splitk_ws=sk)
+                c_cur = cur.shape[1]
+                if not (wide and self._wide_1x1(P, dev, cur, B * h * w, h, w, c_cur, b["w1"], b["width"], b["e1"], RELU, t1,
+                                                tag + "_1x1")):
+                    ops.conv_forward(cur, B, h, w, b["w1"], b["width"], 1, e1=b["e1"], act=RELU, y2d=t1, tag=tag + "_1x1",
+                                     splitk_ws=sk)
                 if b["nb"] > 1 and self._grouped_native(b, h, w):
                     if b["w2n"] is None:
                         self._pack_grouped_native(P, dev)
@@ -367,14 +406,20 @@ class ResNetHip:
                                      tag=tag + "_3x3", splitk_ws=sk)
                 if b["down"] is not None:
                     idn = ws["idn_%d" % li][: B * ho * wo]
-                    ops.conv_forward(cur, B, h, w, b["down"]["w"], b["c_out"], 1, stride=b["down"]["stride"], pad=0,
-                                     e1=b["down"]["e1"], y2d=idn, tag=tag + "_down", splitk_ws=sk)
+                    if not (wide and b["down"]["stride"] == 1
+                            and self._wide_1x1(P, dev, cur, B * h * w, h, w, c_cur, b["down"]["w"], b["c_out"], b["down"]["e1"],
+                                               ops.ACT_NONE, idn, tag + "_down")):
+                        ops.conv_forward(cur, B, h, w, b["down"]["w"], b["c_out"], 1, stride=b["down"]["stride"], pad=0,
+                                         e1=b["down"]["e1"], y2d=idn, tag=tag + "_down", splitk_ws=sk)
                 else:
                     idn = cur
                 out = ws["a_%d" % li] if (bi % 2 == 0) else ws["b_%d" % li]
                 last = bi == len(blocks) - 1
-                ops.conv_forward(t2, B, ho, wo, b["w3"], b["c_out"], 1, e1=b["e3"], act=RELU, y2d=out, res2d=idn,
-                                 y2_2d=skip_dst[li + 1] if (last and li < 3) else None, tag=tag + "_1x1", splitk_ws=sk)
+                y2 = skip_dst[li + 1] if (last and li < 3) else None
+                if not (wide and self._wide_1x1(P, dev, t2, B * ho * wo, ho, wo, b["width"], b["w3"], b["c_out"], b["e3"], RELU, out,
+                                                tag + "_1x1", res2d=idn, y2_2d=y2)):
+                    ops.conv_forward(t2, B, ho, wo, b["w3"], b["c_out"], 1, e1=b["e3"], act=RELU, y2d=out, res2d=idn,
+                                     y2_2d=y2, tag=tag + "_1x1", splitk_ws=sk)
                 cur, h, w = out, ho, wo
         return dict(dense=cur, norm5=None, skips=skip_dst, B=B, H=H, W=W)
 

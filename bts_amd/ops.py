@@ -1245,6 +1245,76 @@ def conv1x1_bf16_forward(x2d: torch.Tensor, npix: int, c_in: int, w_plane: torch
     return y2d
 
 
+# ---- the same tile at 128 / 192 / 256 channels per workgroup with the bottleneck epilogue (res, y2): ResNe(X)t's 1x1 layers and
+#      DenseNet121's bottlenecks under BtsModel.bf16_wide_1x1 = "all"
+def conv1x1_bf16_wide_plan(h: int, w: int, c_in: int, c_out: int, has_res: bool = False, fill_frames: Optional[int] = None) -> TilePlan:
+    """Should this 1x1 layer take conv1x1_bf16_wide_forward?  Host-only query (bts_conv1x1_bf16_wide_plan) on the per-frame
+    geometry; ``has_res``: the layer adds an identity; ``fill_frames`` defaults to the launch_config in force."""
+    ff, _ = _resolve_launch(None, fill_frames, "conv1x1_bf16_wide_plan")
+    bm, bn, wgs = C.c_int(0), C.c_int(0), C.c_long(0)
+    _lib.check(_lib.load_real().bts_conv1x1_bf16_wide_plan(int(h), int(w), int(c_in), int(c_out), int(bool(has_res)), int(ff),
+                                                            C.byref(bm), C.byref(bn), C.byref(wgs)), "bts_conv1x1_bf16_wide_plan")
+    return TilePlan((bm.value, bn.value, wgs.value))
+
+
+def conv1x1_bf16_wide_forward(x2d: torch.Tensor, npix: int, c_in: int, w_plane: torch.Tensor, c_out: int, y2d: torch.Tensor,
+                              pre: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, pre_relu: bool = False,
+                              e1: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, res2d: Optional[torch.Tensor] = None,
+                              y2_2d: Optional[torch.Tensor] = None, act: int = ACT_NONE, bn: int = 0, tag: str = "conv1x1_bf16_wide"):
+    """act(e1(conv1x1(bf16(pre(x)))) + res) in one launch of the wide bf16 tile (bts_conv1x1_bf16_wide_fwd_f32), also written to
+    y2: the operands of conv1x1_bf16_forward, plus res2d / y2_2d [npix, c_out] NHWC views (channel slices are fine) and
+    ``bn`` = 128 / 192 / 256 to force a tile (0: the library's choice for c_out).  c_out a multiple of 128 or of 192.  Runs
+    whatever the plan query says: callers ask conv1x1_bf16_wide_plan first."""
+    name = "conv1x1_bf16_wide_forward"
+    xs, xc = _rows2d(x2d, name)
+    ys, yc = _rows2d(y2d, name)
+    if not isinstance(w_plane, torch.Tensor) or not w_plane.is_cuda or w_plane.dtype not in (torch.int16, torch.bfloat16):
+        raise BtsHipError("%s: w_plane must be an int16 / bfloat16 CUDA/ROCm tensor (round_bf16 of the packed weight)" % name)
+    if c_in <= 0 or c_in % 16 or c_out <= 0 or (c_out % 128 and c_out % 192):
+        raise BtsHipError("%s: %d -> %d channels; needs c_in %% 16 == 0 and c_out a multiple of 128 or 192" % (name, c_in, c_out))
+    if bn not in (0, 128, 192, 256) or (bn and c_out % bn):
+        raise BtsHipError("%s: bn must be 0 or one of 128 / 192 / 256 that divides c_out = %d, got %r" % (name, c_out, bn))
+    if npix <= 0 or xc < c_in or yc != c_out or x2d.shape[0] != npix or y2d.shape[0] != npix:
+        raise BtsHipError("%s: views %s / %s do not fit %d pixels, %d -> %d channels"
+                          % (name, tuple(x2d.shape), tuple(y2d.shape), npix, c_in, c_out))
+    if xs % 4 or ys % 4 or x2d.data_ptr() % 16 or y2d.data_ptr() % 16:
+        raise BtsHipError("%s: rows must be 16-byte aligned (pixel strides %d / %d, multiples of 4 floats)" % (name, xs, ys))
+    strides = []
+    for t, what in ((res2d, "res2d"), (y2_2d, "y2_2d")):
+        if t is None:
+            strides.append(0)
+            continue
+        ts, tc = _rows2d(t, name)
+        if tc != c_out or t.shape[0] != npix or ts % 4 or t.device != x2d.device:
+            raise BtsHipError("%s: %s %s must be a [%d, %d] view on x2d's device with a pixel stride that is a multiple of 4 floats"
+                              % (name, what, tuple(t.shape), npix, c_out))
+        strides.append(ts)
+    if (w_plane.dim() not in (2, 3) or (w_plane.dim() == 3 and w_plane.shape[0] != 1) or not w_plane.is_contiguous()
+            or w_plane.shape[-2] < c_out or w_plane.shape[-1] < c_in or w_plane.shape[-1] % 32):
+        raise BtsHipError("%s: w_plane %s must be contiguous [1, c_out_pad >= %d, k_pad >= %d (a multiple of 32)]"
+                          % (name, tuple(w_plane.shape), c_out, c_in))
+    cout_pad, k_pad = int(w_plane.shape[-2]), int(w_plane.shape[-1])
+    _check_act3(act, name)
+    ps, pb = _e2_vectors(pre, c_in, name, "pre")
+    es, eb = _e2_vectors(e1, c_out, name, "e1")
+    kern, flops, nbytes, xflops = "conv", 0.0, 0.0, None
+    if _trace is not None:
+        kern = conv_plan.wide_1x1_bf16_kernel_name(bn or conv_plan.wide_1x1_bf16_tile(c_out))
+        flops = 2.0 * npix * c_out * c_in
+        nbytes = 4.0 * npix * (c_in + c_out * (1 + (res2d is not None) + (y2_2d is not None))) + 2.0 * c_out * c_in
+        xflops = 2.0 * (round_up(npix, 128)) * c_out * c_in                    # ragged last tile included
+    tops = torch_ops()
+    run = None
+    if tops is not None:
+        run = lambda: _op(lambda: tops.conv1x1_bf16_wide(x2d, w_plane, ps, pb, es, eb, res2d, y2d, y2_2d,
+                                                         [npix, c_in, c_out, int(bool(pre_relu)), int(act), int(bn)]))
+    _enqueue("bts_conv1x1_bf16_wide_fwd_f32", x2d,
+             (_ptr(x2d), xs, npix, c_in, _ptr(w_plane), k_pad, c_out, cout_pad, _ptr(ps), _ptr(pb), int(bool(pre_relu)), _ptr(es), _ptr(eb),
+              _ptr(res2d), strides[0], int(act), _ptr(y2d), ys, _ptr(y2_2d), strides[1], int(bn)), trace=(kern, tag, flops, nbytes, xflops),
+             run=run)
+    return y2d
+
+
 # ---- conv1 (32 features + planar tail -> 32 channels, NCHW) as a fused Winograd F(2x2,3x3) kernel (csrc/conv_wino_tail.inc)
 _WINO_G =((1.0, 0.0, 0.0), (0.5, 0.5, 0.5), (0.5, -0.5, 0.5), (0.0, 0.0, 1.0))
 _WINO_BT = ((1.0, 0.0, -1.0, 0.0), (0.0, 1.0, 1.0, 0.0), (0.0, -1.0, 1.0, 0.0), (0.0, 1.0, 0.0, -1.0))

@@ -348,6 +348,39 @@ int bts_conv1x1_bf16_fwd_f32(const float* x, long x_pix_stride, long npix, int c
  *   all three 0 when the layer should stay on bts_conv_fwd_f32. */
 int bts_conv1x1_bf16_plan(int h, int w, int c_in, int c_out, int fill_frames, int* bm, int* bn, long* workgroups);
 
+/* The same wide bf16 tile at 128, 192 or 256 output channels per workgroup, with the bottleneck epilogue: ResNe(X)t's conv1 /
+ * conv3 / stride-1 downsample 1x1 layers and DenseNet121's bottlenecks (c_out 128) in the precision-2 arithmetic.  Everything
+ * bts_conv1x1_bf16_fwd_f32 says about x, w_bf16, pre_*, e1_*, y, act, rounding, sum order and non-finite values holds; added:
+ *   y[p][n] = act( e1( sum ... ) + res[p][n] )      ONE fp32 add after e1 and before the activation (bts_conv_desc.res);
+ *                                                   with e1 absent y = act(sum + res)
+ *   res     : NULL, or [npix] NHWC pixels, res_pix_stride >= c_out (a multiple of 4), 4-byte aligned; only [p][0 .. c_out) of
+ *             pixels p < npix is read.  A NaN in res[p][n] reaches y[p][n] (and y2[p][n]) and nothing else.
+ *   y2      : NULL, or a second destination of the same values (bts_conv_desc.y2: the skip tap of layers 1-3), [npix] NHWC
+ *             pixels, y2_pix_stride >= c_out (a multiple of 4), 4-byte aligned; nothing is written outside [p][0 .. c_out)
+ *             A stride given for a NULL res / y2 is ignored.
+ *   bn      : 128, 192 or 256 forces that tile (BTS_ERR_UNSUPPORTED unless it divides c_out; BTS_ERR_INVALID for any other
+ *             value); 0 = the library's choice, a pure function of c_out: 192 where c_out % 192 == 0, else 128 -- the
+ *             per-layer bench has 256 lose to 128 on some class of every width (csrc/conv_1x1_bf16.inc).  A pixel's bits
+ *             do not depend on bn.
+ * BTS_ERR_UNSUPPORTED: c_out a multiple of neither 128 nor 192 (ResNet-50/101's 64-wide layer-1 conv1 stays on
+ * bts_conv_fwd_f32), and everything bts_conv1x1_bf16_fwd_f32 answers it for (res / y2 strides >= 2^26 included).
+ * Any supported shape runs, whatever the plan query says.  bn = 192 without res and y2 is the launch of
+ * bts_conv1x1_bf16_fwd_f32 itself. */
+int bts_conv1x1_bf16_wide_fwd_f32(const float* x, long x_pix_stride, long npix, int c_in, const void* w_bf16, int k_pad,
+                                  int c_out, int c_out_pad, const float* pre_scale, const float* pre_shift, int pre_relu,
+                                  const float* e1_scale, const float* e1_shift, const float* res, long res_pix_stride,
+                                  int act, float* y, long y_pix_stride, float* y2, long y2_pix_stride, int bn,
+                                  bts_stream_t stream);
+
+/* Should a 1x1 layer take bts_conv1x1_bf16_wide_fwd_f32 (host-side query, no GPU work, no pointers, no batch: fill_frames as
+ * in bts_conv_desc, 0 = the library default)?  has_res: the layer adds an identity (ResNet's conv3).  Eligible: a supported
+ * width whose layer class the per-layer bench measured to win (csrc/conv_1x1_bf16.inc: the constants and their source); a
+ * class that was not measured to win is refused.
+ *   *bm = 128, *bn = the tile bn = 0 launches, *workgroups = workgroups PER FRAME (ceil(h w / 128) * c_out / bn);
+ *   all three 0 when the layer should stay on bts_conv_fwd_f32. */
+int bts_conv1x1_bf16_wide_plan(int h, int w, int c_in, int c_out, int has_res, int fill_frames, int* bm, int* bn,
+                               long* workgroups);
+
 /* The decoder's full-resolution planar-tail 3x3 convolution (conv1: stride 1, padding 1, 32 NHWC feature channels plus up to
  * four dense depth planes in, 32 channels out, activation, NCHW result) in one launch of a fused Winograd F(2x2,3x3) kernel
  * (csrc/conv_wino_tail.inc):
