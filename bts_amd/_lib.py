@@ -156,6 +156,8 @@ ABI: Dict[str, Entry] = {
     "bts_bn_train_stats_f32": _launch(_vp, _l64, _l64, _i, _vp, _vp, _f, _f, _vp, _vp, _vp, _l64, _vp, _vp, _vp, _vp, _vp),
     "bts_bn_apply_nhwc_f32": _launch(_vp, _l64, _l64, _i, _vp, _vp, _i, _vp, _l64, _vp),
     "bts_bn_train_bwd_f32": _launch(_vp, _l64, _vp, _l64, _l64, _i, _vp, _vp, _vp, _vp, _i, _vp, _l64, _vp, _vp, _vp, _l64, _vp),
+    "bts_bn_frozen_vectors_f32": _launch(_vp, _vp, _vp, _vp, _f, _i, _vp, _vp, _vp, _vp, _vp),
+    "bts_bn_frozen_bwd_f32": _launch(_vp, _l64, _vp, _l64, _l64, _i, _vp, _vp, _vp, _vp, _i, _vp, _l64, _vp, _vp, _vp, _l64, _i, _vp),
     "bts_nchw_to_nhwc_f32": _launch(_vp, _i, _i, _l64, _vp, _l64, _i, _vp, plan=(5, "nchw_to_nhwc")),
     "bts_nhwc_to_nchw_f32": _launch(_vp, _l64, _i, _i, _l64, _vp, _vp, plan=(6, "nhwc_to_nchw")),
     "bts_pack_planes_f32": _launch(_vp, _vp, _vp, _vp, _i, _l64, _vp, _l64, _vp),

@@ -394,6 +394,8 @@ class bts(nn.Module):
                                                         # DESIGN 3a); needs conv_precision "fp32"; eval forwards never read it
         self.batched_wgrad = False                      # train() mode, with fused_reduction_train: True computes the weight
                                                         # gradients of one scale's layers in one batched launch (ops.WgradBatch)
+        self.native_frozen_norm = False                 # train() mode: True runs eval()-mode norm layers (bn_no_track_stats)
+                                                        # on the HIP kernels instead of ATen (train.frozen_norm_scope)
         self.subpixel_upconv_train = False              # train() mode: True runs the ratio-2 upconvs in sub-pixel form in the
                                                         # forward, input-gradient and weight-gradient passes (train._UpconvFn;
                                                         # 16 products per source pixel instead of 36)
@@ -676,6 +678,8 @@ class encoder(nn.Module):
                                             # passes of every convolution but the 3-channel stem (train.precision_scope)
         self.batched_wgrad = False          # train() mode: True defers the weight gradients of a DenseNet block to the end
                                             # of its backward walk and computes them in one batched launch (train._DenseBlockFn)
+        self.native_frozen_norm = False     # train() mode: True runs eval()-mode norm layers (bn_no_track_stats) on the HIP kernels
+                                            # and keeps dense blocks that hold them on the fused node (train.frozen_norm_scope)
         self.grouped_conv_train = False     # train() mode, ResNeXt: True runs every stride-1 grouped 3x3 with <= 16 channels per
                                             # group (width % 64 == 0) on the native grouped kernels in all three passes
                                             # (train.conv2d(grouped_native=True)); fp32 only, a shape rule with no fill query
@@ -817,6 +821,17 @@ class BtsModel(nn.Module):
     @batched_wgrad.setter
     def batched_wgrad(self, on: bool):
         self.encoder.batched_wgrad = self.decoder.batched_wgrad = bool(on)
+
+    @property
+    def native_frozen_norm(self) -> bool:
+        """Norm layers with frozen statistics (eval() mode inside the train()-mode model: set_misc(bn_no_track_stats=True))
+        on the HIP kernels, fused dense blocks included (encoder.native_frozen_norm and bts.native_frozen_norm, set
+        together), default False: such layers then run on ATen and their dense blocks on the layer-by-layer graph."""
+        return self.encoder.native_frozen_norm and self.decoder.native_frozen_norm
+
+    @native_frozen_norm.setter
+    def native_frozen_norm(self, on: bool):
+        self.encoder.native_frozen_norm = self.decoder.native_frozen_norm = bool(on)
 
     def _native_ok(self, x):
         return (self.native_encoder and not self.training and isinstance(x, torch.Tensor) and x.is_cuda

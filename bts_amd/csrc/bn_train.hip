@@ -11,6 +11,13 @@
 //             (y = [relu](x*scale + shift))
 //   backward: bn_bwd_reduce (sum dy', sum dy'*xhat; dy' = dy masked by the fused ReLU)  ->  finalize
 //             ->  bn_bwd_apply (dx = gamma*invstd*(dy' - mean(dy') - xhat*mean(dy'*xhat)))
+//
+// Frozen statistics (an eval()-mode nn.BatchNorm2d inside a train()-mode model: bts_main.py --bn_no_track_stats):
+//   forward : bn_frozen_vectors (the same four vectors from the running buffers, which are only read)  ->  bn_apply
+//   backward: bn_frozen_bwd -- dx = scale*dy' depends on no sum, so ONE streaming pass over x and dy writes dx (or adds it
+//             onto what is there) and, where gamma / beta take a gradient, leaves the chunk partials of sum dy' and
+//             sum dy'*xhat for the same finalize kernel.  12 bytes per element (16 accumulating, 8 sums only) against the
+//             20 of the batch-statistic backward.
 #include "common.h"
 #include <stdint.h>
 
@@ -281,6 +288,102 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
     }
 }
 
+// Frozen statistics: mean = running_mean, invstd, scale, shift in the form bn_stats_finalize_kernel writes them; one
+// thread per channel, 32 channels per block.  The running buffers are read only.
+__global__ __launch_bounds__(32) void bn_frozen_vectors_kernel(const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                               const float* __restrict__ running_mean,
+                                                               const float* __restrict__ running_var, float eps, int C,
+                                                               float* __restrict__ mean_o, float* __restrict__ invstd_o,
+                                                               float* __restrict__ scale_o, float* __restrict__ shift_o) {
+    const int c = blockIdx.x * 32 + threadIdx.x;
+    if (c >= C) return;
+    const float mean = running_mean[c];
+    const float invstd = 1.f / sqrtf(running_var[c] + eps);
+    const float g = gamma ? gamma[c] : 1.f, b = beta ? beta[c] : 0.f;
+    mean_o[c] = mean;
+    invstd_o[c] = invstd;
+    scale_o[c] = g * invstd;
+    shift_o[c] = b - mean * g * invstd;
+}
+
+// Backward of a frozen norm layer (+ fused ReLU) in one pass on bn_bwd_reduce_kernel's chunk grid: dy' = dy masked by the
+// forward's x*scale + shift > 0; DX: dx = scale*dy' (ACC: added onto dx), written by the lane that loaded it; SUMS: the
+// chunk's (sum dy', sum dy'*xhat) -> ws[(chunk*2 + {0,1})*C + c], summed in bn_bwd_reduce_kernel's order.  dx may share a
+// wide buffer with dy (other columns), so neither pointer is __restrict__.
+template <int LX, bool SUMS, bool DX, bool ACC>
+__global__ __launch_bounds__(256) void bn_frozen_bwd_kernel(const float* __restrict__ x, long xs, const float* dy, long dys,
+                                                            long npix, int C, const float* __restrict__ mean,
+                                                            const float* __restrict__ invstd, const float* __restrict__ scale,
+                                                            const float* __restrict__ shift, int relu, long rows_per_chunk,
+                                                            float* __restrict__ ws, float* dx, long dxs) {
+    constexpr int RYv = 256 / LX, CGv = LX * 4;
+    const int cx = threadIdx.x % LX, ry = threadIdx.x / LX;
+    const int c4 = blockIdx.x * CGv + cx * 4;
+    const bool active = c4 < C;
+    const long p0 = (long)blockIdx.y * rows_per_chunk;
+    const long p1 = min(npix, p0 + rows_per_chunk);
+    f32x4 s1 = (f32x4)(0.f), s2 = (f32x4)(0.f);
+    if (active) {
+        f32x4 mu = (f32x4)(0.f), is = (f32x4)(0.f);
+        if (SUMS) {
+            mu = *reinterpret_cast<const f32x4*>(mean + c4);
+            is = *reinterpret_cast<const f32x4*>(invstd + c4);
+        }
+        const f32x4 sc = *reinterpret_cast<const f32x4*>(scale + c4), sh = *reinterpret_cast<const f32x4*>(shift + c4);
+        auto one = [&](const f32x4 xv, f32x4 g, const f32x4 old, float* o) __attribute__((always_inline)) {
+            if (relu) {
+                const f32x4 z = xv * sc + sh;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) g[j] = z[j] > 0.f ? g[j] : 0.f;
+            }
+            if (SUMS) {
+                s1 += g;
+                s2 += g * ((xv - mu) * is);
+            }
+            if (DX) *reinterpret_cast<f32x4*>(o) = ACC ? old + sc * g : sc * g;
+        };
+        const f32x4 zero = (f32x4)(0.f);
+        long p = p0 + ry;
+        for (; p + RYv < p1; p += 2 * RYv) {                          // two row pairs: four (ACC: six) independent loads in flight
+            float* oa = DX ? dx + p * dxs + c4 : nullptr;
+            float* ob = DX ? dx + (p + RYv) * dxs + c4 : nullptr;
+            const f32x4 xa = *reinterpret_cast<const f32x4*>(x + p * xs + c4);
+            const f32x4 ga = *reinterpret_cast<const f32x4*>(dy + p * dys + c4);
+            const f32x4 xb = *reinterpret_cast<const f32x4*>(x + (p + RYv) * xs + c4);
+            const f32x4 gb = *reinterpret_cast<const f32x4*>(dy + (p + RYv) * dys + c4);
+            const f32x4 da = ACC ? *reinterpret_cast<const f32x4*>(oa) : zero;
+            const f32x4 db = ACC ? *reinterpret_cast<const f32x4*>(ob) : zero;
+            one(xa, ga, da, oa);
+            one(xb, gb, db, ob);
+        }
+        for (; p < p1; p += RYv) {
+            float* o = DX ? dx + p * dxs + c4 : nullptr;
+            one(*reinterpret_cast<const f32x4*>(x + p * xs + c4), *reinterpret_cast<const f32x4*>(dy + p * dys + c4),
+                ACC ? *reinterpret_cast<const f32x4*>(o) : zero, o);
+        }
+    }
+    if (SUMS) {
+        __shared__ float red[RYv][CGv][2];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            red[ry][cx * 4 + j][0] = s1[j];
+            red[ry][cx * 4 + j][1] = s2[j];
+        }
+        __syncthreads();
+        if (threadIdx.x < CGv) {
+            const int c = blockIdx.x * CGv + threadIdx.x;
+            if (c < C) {
+                float a = 0.f, b = 0.f;
+#pragma unroll 8
+                for (int r = 0; r < RYv; ++r) { a += red[r][threadIdx.x][0]; b += red[r][threadIdx.x][1]; }
+                float* o = ws + (size_t)blockIdx.y * 2 * C;
+                o[c] = a;
+                o[C + c] = b;
+            }
+        }
+    }
+}
+
 // float4 lanes per pixel row for a channel count: the widest of 32/16/8 that the tensor fills
 inline int lanes_for(int C) { return C >= 112 ? 32 : (C >= 48 ? 16 : 8); }
 
@@ -305,6 +408,23 @@ inline bool bad_rows(const float* p, long stride, int C) {
 inline unsigned elem_blocks(long total) {
     long b = (total + 255) / 256;
     return (unsigned)(b > 8192 ? 8192 : (b < 1 ? 1 : b));
+}
+
+template <int LX>
+void launch_frozen_bwd(int form, dim3 grid, hipStream_t s, const float* x, long xs, const float* dy, long dys, long npix, int C,
+                       const float* mean, const float* invstd, const float* scale, const float* shift, int relu, long rows,
+                       float* ws, float* dx, long dxs) {
+#define BTS_FROZEN_BWD(SUMS, DX, ACC)                                                                                         \
+    hipLaunchKernelGGL((bn_frozen_bwd_kernel<LX, SUMS, DX, ACC>), grid, dim3(256), 0, s, x, xs, dy, dys, npix, C, mean, invstd, \
+                       scale, shift, relu, rows, ws, dx, dxs)
+    switch (form) {                                                  // bit 0: sums, bit 1: dx, bit 2: accumulate
+    case 1: BTS_FROZEN_BWD(true, false, false); break;
+    case 2: BTS_FROZEN_BWD(false, true, false); break;
+    case 3: BTS_FROZEN_BWD(true, true, false); break;
+    case 6: BTS_FROZEN_BWD(false, true, true); break;
+    default: BTS_FROZEN_BWD(true, true, true); break;
+    }
+#undef BTS_FROZEN_BWD
 }
 
 }  // namespace
@@ -374,5 +494,45 @@ extern "C" int bts_bn_train_bwd_f32(const float* x, long x_pix_stride, const flo
     if (dx)
         hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(elem_blocks(npix * (C >> 2))), dim3(256), 0, s, x, x_pix_stride, dy,
                            dy_pix_stride, npix, C, mean, invstd, scale, shift, relu, dbeta, dgamma, dx, dx_pix_stride);
+    return (int)hipGetLastError();
+}
+
+extern "C" int bts_bn_frozen_vectors_f32(const float* gamma, const float* beta, const float* running_mean,
+                                         const float* running_var, float eps, int C, float* mean, float* invstd,
+                                         float* scale, float* shift, bts_stream_t stream) {
+    if (C <= 0 || (C & 3) || !running_mean || !running_var || !mean || !invstd || !scale || !shift) return BTS_ERR_INVALID;
+    if (((uintptr_t)scale & 15) || ((uintptr_t)shift & 15) || ((uintptr_t)mean & 15) || ((uintptr_t)invstd & 15))
+        return BTS_ERR_INVALID;
+    hipLaunchKernelGGL(bn_frozen_vectors_kernel, dim3((C + 31) / 32), dim3(32), 0, (hipStream_t)stream, gamma, beta,
+                       running_mean, running_var, eps, C, mean, invstd, scale, shift);
+    return (int)hipGetLastError();
+}
+
+extern "C" int bts_bn_frozen_bwd_f32(const float* x, long x_pix_stride, const float* dy, long dy_pix_stride, long npix, int C,
+                                     const float* mean, const float* invstd, const float* scale, const float* shift,
+                                     int relu, float* ws, long ws_floats, float* dgamma, float* dbeta, float* dx,
+                                     long dx_pix_stride, int accumulate, bts_stream_t stream) {
+    if (npix <= 0 || C <= 0 || (C & 3) || bad_rows(x, x_pix_stride, C) || bad_rows(dy, dy_pix_stride, C)) return BTS_ERR_INVALID;
+    if (!mean || !invstd || !scale || !shift) return BTS_ERR_INVALID;
+    if (((uintptr_t)mean & 15) || ((uintptr_t)invstd & 15) || ((uintptr_t)scale & 15) || ((uintptr_t)shift & 15))
+        return BTS_ERR_INVALID;
+    if (!dgamma != !dbeta || (!dgamma && !dx)) return BTS_ERR_INVALID;
+    const bool sums = dgamma != nullptr;
+    if (sums && (((uintptr_t)dgamma & 15) || ((uintptr_t)dbeta & 15))) return BTS_ERR_INVALID;
+    if (dx && bad_rows(dx, dx_pix_stride, C)) return BTS_ERR_INVALID;
+    long rows; int nchunks;
+    plan_chunks(npix, C, &rows, &nchunks);
+    if (sums && (!ws || ws_floats < (long)nchunks * 2 * C)) return BTS_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    const int lx = lanes_for(C);
+    const dim3 grid((C + lx * 4 - 1) / (lx * 4), nchunks);
+    const int form = (sums ? 1 : 0) | (dx ? 2 : 0) | (dx && accumulate ? 4 : 0);
+    if (lx == 32) launch_frozen_bwd<32>(form, grid, s, x, x_pix_stride, dy, dy_pix_stride, npix, C, mean, invstd, scale, shift,
+                                        relu, rows, ws, dx, dx_pix_stride);
+    else if (lx == 16) launch_frozen_bwd<16>(form, grid, s, x, x_pix_stride, dy, dy_pix_stride, npix, C, mean, invstd, scale,
+                                             shift, relu, rows, ws, dx, dx_pix_stride);
+    else launch_frozen_bwd<8>(form, grid, s, x, x_pix_stride, dy, dy_pix_stride, npix, C, mean, invstd, scale, shift, relu,
+                              rows, ws, dx, dx_pix_stride);
+    if (sums) hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 31) / 32), dim3(256), 0, s, ws, nchunks, C, dbeta, dgamma);
     return (int)hipGetLastError();
 }

@@ -2468,6 +2468,73 @@ def bn_train_backward(x2d: torch.Tensor, dy2d: torch.Tensor, C: int, mean, invst
     return g[0], g[1]
 
 
+def bn_frozen_vectors(C: int, gamma, beta, running_mean: torch.Tensor, running_var: torch.Tensor, eps: float,
+                      out: Optional[torch.Tensor] = None):
+    """The four vectors of a norm layer with frozen statistics (bts_bn_frozen_vectors_f32): returns (mean, invstd, scale,
+    shift), each [C], from the running buffers, which are only read.  gamma / beta None = 1 / 0.  ``out``: optional [4, C]
+    view (unit channel stride, rows 16-byte aligned) that receives the four vectors instead of a fresh tensor."""
+    if not isinstance(C, int) or C <= 0 or C % 4:
+        raise BtsHipError("bn_frozen_vectors: C must be a positive multiple of 4, got %r" % (C,))
+    for v, what in ((running_mean, "running_mean"), (running_var, "running_var")):
+        _channel_vec(v, C, "bn_frozen_vectors", what, aligned=False)
+    for v, what in ((gamma, "gamma"), (beta, "beta")):
+        if v is not None:
+            _channel_vec(v, C, "bn_frozen_vectors", what, aligned=False)
+    if out is None:
+        out = torch.empty((4, C), dtype=torch.float32, device=running_mean.device)
+    else:
+        _need(out, "bn_frozen_vectors")
+        if tuple(out.shape) != (4, C) or out.stride(1) != 1 or out.stride(0) % 4 or out.data_ptr() % 16:
+            raise BtsHipError("bn_frozen_vectors: out must be a [4, %d] view with unit channel stride and 16-byte aligned rows" % C)
+    _enqueue("bts_bn_frozen_vectors_f32", running_mean,
+             (_ptr(gamma), _ptr(beta), running_mean.data_ptr(), running_var.data_ptr(), float(eps), C,
+              out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), out[3].data_ptr()),
+             trace=("bn_frozen_vectors_kernel", "bn.frozen", 4.0 * C, 32.0 * C, None))
+    return out[0], out[1], out[2], out[3]
+
+
+def bn_frozen_backward(x2d: torch.Tensor, dy2d: torch.Tensor, C: int, mean, invstd, scale, shift, relu: bool,
+                       ws: Optional[torch.Tensor], dx2d: Optional[torch.Tensor], sums: bool = True, accumulate: bool = False,
+                       out: Optional[torch.Tensor] = None):
+    """Backward of a norm layer with frozen statistics (+ fused ReLU), one streaming pass (bts_bn_frozen_bwd_f32):
+    dx2d (or None) = scale*dy', added onto dx2d when ``accumulate``; ``sums``: returns (dgamma, dbeta) -- which need ``ws``
+    (bn_train_ws_floats) -- else (None, None) and no reduction runs.  ``out``: optional [2, C] view (unit channel stride,
+    rows 16-byte aligned) that receives (dgamma, dbeta) instead of a fresh tensor."""
+    npix = x2d.shape[0] if isinstance(x2d, torch.Tensor) and x2d.dim() == 2 else 0
+    xs = _rows2d_c(x2d, C, npix, "bn_frozen_backward")
+    ds = _rows2d_c(dy2d, C, npix, "bn_frozen_backward")
+    for v, what in ((mean, "mean"), (invstd, "invstd"), (scale, "scale"), (shift, "shift")):
+        _channel_vec(v, C, "bn_frozen_backward", what)
+    if not sums and dx2d is None:
+        raise BtsHipError("bn_frozen_backward: nothing to compute (no sums and no dx)")
+    dxs = 0
+    if dx2d is not None:
+        dxs = _rows2d_c(dx2d, C, npix, "bn_frozen_backward")
+    elif accumulate:
+        raise BtsHipError("bn_frozen_backward: accumulate needs dx")
+    g = None
+    if sums:
+        _need(ws, "bn_frozen_backward")
+        if ws.numel() < bn_train_ws_floats(npix, C) or not ws.is_contiguous():
+            raise BtsHipError("bn_frozen_backward: the workspace must hold %d floats" % bn_train_ws_floats(npix, C))
+        if out is None:
+            g = torch.empty((2, C), dtype=torch.float32, device=x2d.device)
+        else:
+            _need(out, "bn_frozen_backward")
+            if tuple(out.shape) != (2, C) or out.stride(1) != 1 or out.stride(0) % 4 or out.data_ptr() % 16:
+                raise BtsHipError("bn_frozen_backward: out must be a [2, %d] view with unit channel stride and 16-byte aligned rows" % C)
+            g = out
+    elif out is not None:
+        raise BtsHipError("bn_frozen_backward: out is for the sums")
+    nbytes = 4.0 * npix * C * (2 + (dx2d is not None) + bool(accumulate))
+    _enqueue("bts_bn_frozen_bwd_f32", x2d,
+             (x2d.data_ptr(), xs, dy2d.data_ptr(), ds, npix, C, mean.data_ptr(), invstd.data_ptr(), scale.data_ptr(), shift.data_ptr(),
+              int(bool(relu)), _ptr(ws if sums else None), ws.numel() if sums else 0, _ptr(None if g is None else g[0]),
+              _ptr(None if g is None else g[1]), _ptr(dx2d), dxs, int(bool(accumulate))),
+             trace=("bn_frozen_bwd_kernel", "bn.frozen_bwd", (6.0 if sums else 2.0) * npix * C, nbytes, None))
+    return (g[0], g[1]) if sums else (None, None)
+
+
 # ------------------------------------------------------------------------------ tail
 def pack_planes(planes: Sequence[torch.Tensor], dst2d: torch.Tensor):
     """Interleave 1-channel maps ([B,1,H,W] contiguous each) into dst2d [npix, n] (an NHWC slice)."""

@@ -356,6 +356,38 @@ class precision_scope:
         return False
 
 
+# ---- native_frozen_norm: norm layers with frozen statistics on the HIP kernels (opt-in) ----------------------
+# ``BtsModel.native_frozen_norm = True`` (forwarded to encoder.native_frozen_norm and bts.native_frozen_norm): an eval()-mode
+# BatchNorm2d inside the train()-mode model (bts_main.py --bn_no_track_stats -> bn_init_as_tf) runs on bn_frozen_vectors /
+# bn_apply / bn_frozen_backward instead of ATen, and a dense block with such layers keeps its fused node.  Read once per
+# node, in its forward, like the train precision.
+_fn_tls = threading.local()
+
+
+def current_frozen_norm() -> bool:
+    """Whether a node whose forward runs now on this thread takes frozen norm layers on the HIP kernels."""
+    return getattr(_fn_tls, "value", False)
+
+
+class frozen_norm_scope:
+    """``with train.frozen_norm_scope(True):`` around a training forward (this thread only)."""
+
+    def __init__(self, on):
+        self._new = bool(on)
+
+    def __enter__(self):
+        self._prev = getattr(_fn_tls, "value", None)
+        _fn_tls.value = self._new
+        return self
+
+    def __exit__(self, *exc):
+        if self._prev is None:
+            del _fn_tls.value
+        else:
+            _fn_tls.value = self._prev
+        return False
+
+
 def _launch_precision(pr: int):
     """The launch_config scope of a node's convolution launches: precision 2 where the node recorded it, else whatever is in
     force (the fp32 / bf16x3 behaviour of before)."""
@@ -579,12 +611,57 @@ class _BnFn(torch.autograd.Function):
                 dbeta if affine and ctx.needs_input_grad[2] else None, None, None)
 
 
+class _FrozenBnFn(torch.autograd.Function):
+    """y = [relu](batch_norm(x)) with the module's running statistics (an eval()-mode layer), on libbts_hip.so: the buffers
+    and the batch counter are only read.  Backward is one streaming pass; the sums run only where gamma / beta take a
+    gradient, dx only where the input does."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, bn, relu):
+        B, C, H, W = x.shape
+        x2d, _ = _nhwc_rows(x.detach())
+        npix = B * H * W
+        vecs = torch.empty((4, C), dtype=torch.float32, device=x.device)
+        ops.bn_frozen_vectors(C, None if gamma is None else gamma.detach(), None if beta is None else beta.detach(),
+                              bn.running_mean, bn.running_var, bn.eps, out=vecs)
+        y = torch.empty((B, H, W, C), dtype=torch.float32, device=x.device)
+        ops.bn_apply(x2d, C, vecs[2], vecs[3], relu, y.view(npix, C))
+        ctx.save_for_backward(x2d, vecs)
+        ctx.meta = (B, C, H, W, relu, gamma is not None)
+        return y.permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x2d, vecs = ctx.saved_tensors
+        B, C, H, W, relu, affine = ctx.meta
+        need = ctx.needs_input_grad
+        sums = affine and (need[1] or need[2])
+        if not sums and not need[0]:
+            return None, None, None, None, None
+        dy2d, _ = _nhwc_rows(grad_out)
+        npix = B * H * W
+        dx = torch.empty((B, H, W, C), dtype=torch.float32, device=grad_out.device) if need[0] else None
+        ws = _bn_workspace(grad_out.device, ops.bn_train_ws_floats(npix, C)) if sums else None
+        dgamma, dbeta = ops.bn_frozen_backward(x2d, dy2d, C, vecs[0], vecs[1], vecs[2], vecs[3], relu, ws,
+                                               None if dx is None else dx.view(npix, C), sums=sums)
+        return (None if dx is None else dx.permute(0, 3, 1, 2), dgamma if sums and need[1] else None,
+                dbeta if sums and need[2] else None, None, None)
+
+
+def _frozen_norm_layer(bn) -> bool:
+    """An eval()-mode BatchNorm2d that normalises with its running buffers (bn_init_as_tf's layers)."""
+    return not bn.training and bn.running_mean is not None and bn.running_var is not None
+
+
 def _bn(x: torch.Tensor, bn: torch.nn.BatchNorm2d, relu: bool = False) -> torch.Tensor:
     """nn.BatchNorm2d (+ the ReLU that follows it) inside the training graph.  train() mode with a fixed momentum and
-    C % 4 == 0 runs on the HIP kernels; a frozen (eval-mode) layer or an exotic configuration runs on ATen's native
-    kernels (MIOpen bypassed: no gfx950 find-db in this image)."""
+    C % 4 == 0 runs on the HIP kernels; so does a frozen (eval-mode) layer under ``frozen_norm_scope`` (native_frozen_norm).
+    Without the switch a frozen layer, and always an exotic configuration, runs on ATen's native kernels (MIOpen
+    bypassed: no gfx950 find-db in this image)."""
     if bn.training and bn.momentum is not None and x.shape[1] % 4 == 0 and x.is_cuda and x.dtype == torch.float32:
         return _BnFn.apply(x, bn.weight, bn.bias, bn, relu)
+    if current_frozen_norm() and _frozen_norm_layer(bn) and x.shape[1] % 4 == 0 and x.is_cuda and x.dtype == torch.float32:
+        return _FrozenBnFn.apply(x, bn.weight, bn.bias, bn, relu)
     with torch.backends.cudnn.flags(enabled=False):
         y = bn(x)
     return F.relu(y) if relu else y
@@ -717,7 +794,8 @@ def _conv_elu(seq, x, tag, bf16=True):
 
 def decoder_forward(dec, features, focal):
     """bts.forward in train() mode (bts.py:223-293): same dataflow as the inference path, as an autograd graph."""
-    with _deferred_batch_counts(), precision_scope(getattr(dec, "train_precision", "fp32")):
+    with _deferred_batch_counts(), precision_scope(getattr(dec, "train_precision", "fp32")), \
+            frozen_norm_scope(getattr(dec, "native_frozen_norm", False)):
         return _decoder_forward(dec, features, focal)
 
 
@@ -801,28 +879,28 @@ class _DenseBlockFn(torch.autograd.Function):
         ws = _bn_workspace(dev, ops.bn_train_ws_floats(npix, Ct))
         sk = _splitk_workspace(dev)
         pr = current_train_precision()
+        # per norm layer: frozen statistics (eval mode, under frozen_norm_scope) or batch statistics; mixed blocks are fine
+        frozen = tuple((not L.norm1.training, not L.norm2.training) for L in layers)
+        if any(f1 or f2 for f1, f2 in frozen) and not current_frozen_norm():
+            raise BtsHipError("train.densenet_block: a frozen norm layer needs native_frozen_norm (frozen_norm_scope)")
         if batched:      # one slab per kind, so that the deferred weight gradients of all layers address six buffers
             T1 = torch.empty((len(layers), npix, mid), dtype=torch.float32, device=dev)
             stats = torch.empty((len(layers), 8, max(Ct, mid)), dtype=torch.float32, device=dev)   # rows 0-3 norm1, 4-7 norm2
         for i, L in enumerate(layers):
             Ci = C0 + i * g
-            s1 = ops.bn_train_stats(buf[:, :Ci], Ci, L.norm1.weight.detach(), L.norm1.bias.detach(), L.norm1.eps,
-                                    L.norm1.momentum, L.norm1.running_mean, L.norm1.running_var, ws,
-                                    out=stats[i, 0:4, :Ci] if batched else None)
+            s1 = _dense_vectors(L.norm1, buf[:, :Ci], Ci, ws, stats[i, 0:4, :Ci] if batched else None, frozen[i][0])
             # norm + ReLU ride in the convolutions' prologue (applied on the way to LDS): the normalised tensors are
             # never written in the forward pass
             t1 = T1[i] if batched else torch.empty((npix, mid), dtype=torch.float32, device=dev)
             with _launch_precision(pr):
                 ops.conv_forward(buf[:, :Ci], B, H, W, _PACKER.get(L.conv1.weight, Ci, WeightPacker.FWD), mid, 1, c_in_ld=Ci,
                                  pre=(s1[2], s1[3]), pre_relu=True, y2d=t1, tag="enc.fwd", splitk_ws=sk)
-            s2 = ops.bn_train_stats(t1, mid, L.norm2.weight.detach(), L.norm2.bias.detach(), L.norm2.eps,
-                                    L.norm2.momentum, L.norm2.running_mean, L.norm2.running_var, ws,
-                                    out=stats[i, 4:8, :mid] if batched else None)
+            s2 = _dense_vectors(L.norm2, t1, mid, ws, stats[i, 4:8, :mid] if batched else None, frozen[i][1])
             with _launch_precision(pr):
                 ops.conv_forward(t1, B, H, W, _PACKER.get(L.conv2.weight, mid, WeightPacker.FWD), g, 3, c_in_ld=mid,
                                  pre=(s2[2], s2[3]), pre_relu=True, y2d=buf[:, Ci:Ci + g], tag="enc.fwd", splitk_ws=sk)
-            for bn in (L.norm1, L.norm2):
-                if bn.num_batches_tracked is not None:
+            for bn, fz in zip((L.norm1, L.norm2), frozen[i]):
+                if bn.num_batches_tracked is not None and not fz:
                     _count_batch(bn)
             if not batched:
                 saved += [t1, torch.stack(s1), torch.stack(s2)]
@@ -832,6 +910,7 @@ class _DenseBlockFn(torch.autograd.Function):
         ctx.block = block
         ctx.batched_wgrad = batched
         ctx.precision = pr
+        ctx.frozen = frozen
         ctx.geom = (B, C0, H, W, g, mid, Ct)
         return buf.view(B, H, W, Ct).permute(0, 3, 1, 2)
 
@@ -852,7 +931,8 @@ class _DenseBlockFn(torch.autograd.Function):
         else:
             d_t1 = torch.empty((npix, mid), dtype=torch.float32, device=dev)
         d_a1 = torch.empty((npix, Ct), dtype=torch.float32, device=dev)
-        dpre = torch.empty((npix, Ct), dtype=torch.float32, device=dev)
+        frozen = ctx.frozen
+        dpre = None if all(f1 for f1, _ in frozen) else torch.empty((npix, Ct), dtype=torch.float32, device=dev)
         ws = _bn_workspace(dev, ops.bn_train_ws_floats(npix, Ct))
         wws = _workspace(dev)
         sk = _splitk_workspace(dev)
@@ -874,7 +954,11 @@ class _DenseBlockFn(torch.autograd.Function):
                 w2 = ops.conv_wgrad(t1, B, H, W, mid, gy, g, 3, ws=wws, tag="enc.wgrad", pre=(s2[2], s2[3]), pre_relu=True,
                                     precision=pr)
                 grads[6 * i + 5] = w2.reshape(g, 3, 3, mid).permute(0, 3, 1, 2).contiguous()
-            dg2, db2 = ops.bn_train_backward(t1, d_a2, mid, s2[0], s2[1], s2[2], s2[3], True, ws, d_t1)
+            if frozen[i][1]:     # dx depends on no sum: one pass, the sums only where gamma / beta take a gradient
+                dg2, db2 = ops.bn_frozen_backward(t1, d_a2, mid, s2[0], s2[1], s2[2], s2[3], True, ws, d_t1,
+                                                  sums=bool(need[3 + 6 * i + 3] or need[3 + 6 * i + 4]))
+            else:
+                dg2, db2 = ops.bn_train_backward(t1, d_a2, mid, s2[0], s2[1], s2[2], s2[3], True, ws, d_t1)
             if need[3 + 6 * i + 3]:
                 grads[6 * i + 3] = dg2
             if need[3 + 6 * i + 4]:
@@ -886,12 +970,16 @@ class _DenseBlockFn(torch.autograd.Function):
                 w1 = ops.conv_wgrad(buf[:, :Ci], B, H, W, Ci, d_t1, mid, 1, ws=wws, tag="enc.wgrad", pre=(s1[2], s1[3]),
                                     pre_relu=True, precision=pr)
                 grads[6 * i + 2] = w1.reshape(mid, Ci, 1, 1)
-            dg1, db1 = ops.bn_train_backward(buf[:, :Ci], d_a1[:, :Ci], Ci, s1[0], s1[1], s1[2], s1[3], True, ws, dpre[:, :Ci])
+            if frozen[i][0]:     # the prefix receives this layer's input gradient straight from the kernel
+                dg1, db1 = ops.bn_frozen_backward(buf[:, :Ci], d_a1[:, :Ci], Ci, s1[0], s1[1], s1[2], s1[3], True, ws, G[:, :Ci],
+                                                  sums=bool(need[3 + 6 * i + 0] or need[3 + 6 * i + 1]), accumulate=True)
+            else:
+                dg1, db1 = ops.bn_train_backward(buf[:, :Ci], d_a1[:, :Ci], Ci, s1[0], s1[1], s1[2], s1[3], True, ws, dpre[:, :Ci])
+                G[:, :Ci] += dpre[:, :Ci]                                      # the prefix receives this layer's input gradient
             if need[3 + 6 * i + 0]:
                 grads[6 * i + 0] = dg1
             if need[3 + 6 * i + 1]:
                 grads[6 * i + 1] = db1
-            G[:, :Ci] += dpre[:, :Ci]                                          # the prefix receives this layer's input gradient
         if batched:
             # Deferring is safe: buf, T1 and the norm vectors are read-only in backward, D_T1[i] is written once, and layer
             # i's columns of G are final when layer i is processed (layers below only add onto columns < C_i).
@@ -904,6 +992,15 @@ class _DenseBlockFn(torch.autograd.Function):
                     grads[6 * i + 5] = next(dws).reshape(g, 3, 3, mid).permute(0, 3, 1, 2).contiguous()
         dx = G[:, :C0].reshape(B, H, W, C0).permute(0, 3, 1, 2) if need[0] else None
         return (dx, None, None) + tuple(grads)
+
+
+def _dense_vectors(bn, x2d, C, ws, out, frozen):
+    """(mean, invstd, scale, shift) of one norm layer of a dense block: from the running buffers when ``frozen`` (nothing
+    is updated), else the batch statistics with the running-buffer update."""
+    if frozen:
+        return ops.bn_frozen_vectors(C, bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var, bn.eps, out=out)
+    return ops.bn_train_stats(x2d, C, bn.weight.detach(), bn.bias.detach(), bn.eps, bn.momentum, bn.running_mean,
+                              bn.running_var, ws, out=out)
 
 
 # (device, block geometry, need mask, workspace floats) -> ops.WgradBatch; the plan depends on the workspace size, so it
@@ -944,15 +1041,18 @@ def _dense_wgrad_batch(geom, mask, buf, G, T1, D_T1, stats, wws, precision=0):
 
 def _dense_block(block, x, batched_wgrad=False):
     """Fused in-place dense block when every norm layer is an ordinary train()-mode BatchNorm2d with affine parameters
-    and channel counts the kernels take (multiples of 4); otherwise the generic layer-by-layer graph.
+    and channel counts the kernels take (multiples of 4) -- or, under ``frozen_norm_scope``, a frozen one (eval mode, running
+    buffers present, affine), layer by layer; otherwise the generic layer-by-layer graph.
     ``batched_wgrad``: the block's weight gradients in one batched launch at the end of its backward walk."""
     nn = torch.nn
     layers = list(block.values())
     ok = x.is_cuda and x.dtype == torch.float32 and x.shape[1] % 4 == 0
+    native = current_frozen_norm()
     for L in layers:
         for bn in (L.norm1, L.norm2):
-            ok = ok and isinstance(bn, nn.BatchNorm2d) and bn.training and bn.momentum is not None and bn.affine \
+            live = isinstance(bn, nn.BatchNorm2d) and bn.training and bn.momentum is not None and bn.affine \
                 and bn.track_running_stats and bn.running_mean is not None
+            ok = ok and (live or (native and isinstance(bn, nn.BatchNorm2d) and bn.affine and _frozen_norm_layer(bn)))
         ok = ok and L.conv1.bias is None and L.conv2.bias is None and L.conv2.out_channels % 4 == 0 \
             and L.conv1.out_channels % 4 == 0 and L.conv2.padding[0] == 1 and L.conv1.kernel_size[0] == 1 \
             and L.conv2.kernel_size[0] == 3
@@ -1012,7 +1112,8 @@ def densenet_encoder_forward(enc, x):
     begin_step()
     taps = [x]
     cur = x.float().contiguous(memory_format=torch.channels_last)
-    with _deferred_batch_counts(), precision_scope(getattr(enc, "train_precision", "fp32")):
+    with _deferred_batch_counts(), precision_scope(getattr(enc, "train_precision", "fp32")), \
+            frozen_norm_scope(getattr(enc, "native_frozen_norm", False)):
         _run_children(list(enc.base_model.named_children()), cur,
                       tapped=lambda name: any(fragment in name for fragment in enc.feat_names), taps=taps,
                       batched_wgrad=bool(getattr(enc, "batched_wgrad", False)))
@@ -1044,7 +1145,8 @@ def resnet_encoder_forward(enc, x):
     cur = x.float().contiguous(memory_format=torch.channels_last)
     c1 = m.conv1
     native = bool(getattr(enc, "grouped_conv_train", False))
-    with _deferred_batch_counts(), precision_scope(getattr(enc, "train_precision", "fp32")):
+    with _deferred_batch_counts(), precision_scope(getattr(enc, "train_precision", "fp32")), \
+            frozen_norm_scope(getattr(enc, "native_frozen_norm", False)):
         cur = _bn(conv2d(cur, c1.weight, padding=c1.padding[0], stride=c1.stride[0], tag="enc"), m.bn1, relu=True)
         taps = [x, cur]
         cur = m.maxpool(cur)

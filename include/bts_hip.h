@@ -696,6 +696,18 @@ int bts_pack_wino_f32(const float* w_packed, int c_out_pad, long k_pad, int c_in
  * bts_bn_apply_nhwc_f32  : y = [relu](x*scale + shift)   (relu != 0 fuses the ReLU that follows the norm layer)
  * bts_bn_train_bwd_f32   : with dy' = dy masked by the fused ReLU (recomputed from x): dbeta = sum dy',
  *     dgamma = sum dy'*xhat, dx = scale*(dy' - dbeta/n - xhat*dgamma/n)  (dx may be NULL: statistics only).
+ *
+ * Frozen statistics (an eval()-mode nn.BatchNorm2d inside a train()-mode model: bts_main.py --bn_no_track_stats, set_misc ->
+ * bn_init_as_tf); the forward is bts_bn_frozen_vectors_f32 followed by bts_bn_apply_nhwc_f32:
+ * bts_bn_frozen_vectors_f32 : the same four vectors from the running buffers, which are read and never written:
+ *     mean = running_mean, invstd = 1/sqrt(running_var+eps), scale = gamma*invstd, shift = beta - mean*scale.  gamma/beta
+ *     NULL = 1/0.  One small launch; the outputs are 16-byte aligned (they may be rows of a wider slab).
+ * bts_bn_frozen_bwd_f32     : dbeta = sum dy', dgamma = sum dy'*xhat, dx = scale*dy' (accumulate != 0: dx += scale*dy').  dx
+ *     depends on no sum, so this is ONE streaming pass over x and dy (plus the finalize of the sums): 12 bytes per element,
+ *     16 accumulating, 8 for the sums alone, against 20 for bts_bn_train_bwd_f32.  dgamma and dbeta are given together
+ *     or both NULL (no reduction, ws unused, a single launch); dx NULL = sums only; all three NULL is invalid.  The sums
+ *     take the chunk plan (ws of bts_bn_train_ws_floats(npix, C) floats) and the summation order of bts_bn_train_bwd_f32:
+ *     deterministic, no atomics.  dx may lie in the same wide buffer as dy in other columns.
  */
 long bts_bn_train_ws_floats(long npix, int C);
 int bts_bn_train_stats_f32(const float* x, long x_pix_stride, long npix, int C, const float* gamma,
@@ -708,6 +720,13 @@ int bts_bn_train_bwd_f32(const float* x, long x_pix_stride, const float* dy, lon
                          const float* mean, const float* invstd, const float* scale, const float* shift, int relu,
                          float* ws, long ws_floats, float* dgamma, float* dbeta, float* dx, long dx_pix_stride,
                          bts_stream_t stream);
+int bts_bn_frozen_vectors_f32(const float* gamma, const float* beta, const float* running_mean,
+                              const float* running_var, float eps, int C,
+                              float* mean, float* invstd, float* scale, float* shift, bts_stream_t stream);
+int bts_bn_frozen_bwd_f32(const float* x, long x_pix_stride, const float* dy, long dy_pix_stride, long npix, int C,
+                          const float* mean, const float* invstd, const float* scale, const float* shift, int relu,
+                          float* ws, long ws_floats, float* dgamma, float* dbeta,
+                          float* dx, long dx_pix_stride, int accumulate, bts_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Layout movers between the NCHW boundary (pytorch/bts.py:347-349 tensors) and the NHWC

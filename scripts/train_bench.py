@@ -49,6 +49,12 @@ def main():
     ap.add_argument("--train-precision", choices=("fp32", "bf16"), default="fp32",
                     help="bf16: bf16 operands, fp32 accumulation in the forward, input-gradient and weight-gradient pass of "
                          "the convolutions (BtsModel.train_precision)")
+    ap.add_argument("--bn-no-track-stats", action="store_true",
+                    help="every norm layer in eval mode inside the train()-mode model (bts_main.py --bn_no_track_stats; "
+                         "set_misc(bn_no_track_stats=True))")
+    ap.add_argument("--native-frozen-norm", action="store_true",
+                    help="frozen norm layers on the HIP kernels, dense blocks that hold them on the fused node "
+                         "(BtsModel.native_frozen_norm)")
     a = ap.parse_args()
     # BASELINE config 5 (B=32 over 8 GPUs = 4 per GPU, DDP): launch with
     #   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 scripts/train_bench.py
@@ -74,9 +80,14 @@ def main():
     model.subpixel_upconv_train = a.subpixel_upconv
     model.grouped_conv_train = a.grouped_native
     model.train_precision = a.train_precision
+    if a.native_frozen_norm:
+        model.native_frozen_norm = True
     loss_fn = M.silog_loss(0.85, native=a.native_loss)
     if not a.no_freeze:
-        trainer.set_misc(model, a.encoder)          # the reference freezes the stem conv and the encoder norm affines
+        # the reference freezes the stem conv and the encoder norm affines
+        trainer.set_misc(model, a.encoder, bn_no_track_stats=a.bn_no_track_stats)
+    elif a.bn_no_track_stats:
+        model.apply(M.bn_init_as_tf)
     opt = trainer.make_optimizer(model, 1e-4, 1e-2, 1e-3, native=a.native_optim)
     core = model
     if use_dist:
@@ -132,7 +143,8 @@ def main():
                config=dict(encoder=a.encoder, batch_per_gpu=B, height=H, width=W, decoder_only=a.decoder_only,
                            fused_reduc=a.fused_reduc, batched_wgrad=a.batched_wgrad, native_optim=a.native_optim,
                            subpixel_upconv=a.subpixel_upconv, grouped_native=a.grouped_native,
-                           train_precision=a.train_precision),
+                           train_precision=a.train_precision, bn_no_track_stats=a.bn_no_track_stats,
+                           native_frozen_norm=a.native_frozen_norm),
                peak_mem_gb=torch.cuda.max_memory_allocated() / 2**30)
     if a.trace:
         tr = ops.KernelTrace()
