@@ -128,6 +128,10 @@ ABI: Dict[str, Entry] = {
     "bts_conv_grouped_wgrad_plan": _query(_i, _i, _i, _i, _i, _i, _l64, _pi, _pl),
     "bts_conv1x1_bf16_fwd_f32": _launch(_vp, _l64, _l64, _i, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _l64, _vp),
     "bts_conv1x1_bf16_plan": _query(_i, _i, _i, _i, _i, _i, _pi, _pi, _pl),
+    # the bf16-resident bottleneck intermediate (BtsModel.bf16_mid_storage): producer, consumer, the consumer's query
+    "bts_conv1x1_bf16_fwd_bf16": _launch(_vp, _l64, _l64, _i, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _l64, _vp),
+    "bts_conv3x3_bf16in_fwd_f32": _launch(_vp, _l64, _i, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _l64, _vp),
+    "bts_conv3x3_bf16in_plan": _query(_i, _i, _i, _i, _i, _i, _pi, _pl),
     "bts_conv1x1_bf16_wide_fwd_f32": _launch(_vp, _l64, _l64, _i, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _l64, _i, _vp, _l64,
                                              _vp, _l64, _i, _vp),
     "bts_conv1x1_bf16_wide_plan": _query(_i, _i, _i, _i, _i, _i, _i, _pi, _pi, _pl),

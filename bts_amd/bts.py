@@ -744,6 +744,12 @@ class BtsModel(nn.Module):
                                             # ops.conv1x1_bf16_wide_plan accepts (ops.conv1x1_bf16_wide_forward: DenseNet121's
                                             # 128-wide bottlenecks; ResNe(X)t's conv1, conv3 and stride-1 downsample).  A plan
                                             # cannot replay the launch: with use_plans the bf16 forward raises BtsHipError
+        self.bf16_mid_storage = False       # DenseNet161's bottleneck intermediate (eval forward, conv_precision "bf16" only): True
+                                            # keeps it in bfloat16 wherever the bottleneck runs on the wide bf16 tile
+                                            # (bf16_wide_1x1) and ops.conv3x3_bf16in_plan accepts the growth convolution
+                                            # (DESIGN 3c); the outputs are bit-identical.  Nothing changes under "fp32" /
+                                            # "bf16x3", in training, or for ResNe(X)t.  A plan cannot replay the launches:
+                                            # with use_plans the bf16 forward raises BtsHipError
         self._plans = PlanCache()
         self._fp_state = [0, None, -1]      # workspace.tensor_fingerprint: [structure token, cached tensor list, its token]
         self._origin = [self]               # reaches DataParallel replicas through replicate()'s shallow __dict__ copy
@@ -788,6 +794,18 @@ class BtsModel(nn.Module):
         if not (isinstance(value, (bool, int)) and value in (0, 1)) and value != "all":
             raise BtsHipError("BtsModel.bf16_wide_1x1 must be False, True or \"all\", got %r" % (value,))
         self.__dict__["_bf16_wide_1x1"] = value if value == "all" else bool(value)
+
+    @property
+    def bf16_mid_storage(self) -> bool:
+        """False (default) or True: whether an eval forward under conv_precision "bf16" keeps DenseNet's bottleneck
+        intermediate in bfloat16 (see __init__); anything but a bool raises BtsHipError."""
+        return self.__dict__.get("_bf16_mid_storage", False)
+
+    @bf16_mid_storage.setter
+    def bf16_mid_storage(self, value):
+        if not isinstance(value, bool):
+            raise BtsHipError("BtsModel.bf16_mid_storage must be False or True, got %r" % (value,))
+        self.__dict__["_bf16_mid_storage"] = value
 
     @property
     def grouped_conv_train(self) -> bool:
@@ -839,6 +857,10 @@ class BtsModel(nn.Module):
 
     def _forward_native(self, x, focal, slot, outs=None, abs_mins=None):
         if self.use_plans and ops._trace is None and not _lib_mod.is_recording():
+            if (self.bf16_mid_storage and self.bf16_wide_1x1 and ops.current_launch_config()[1] == 2
+                    and not isinstance(self.encoder.base_model, encoders.ResNet)):
+                raise BtsHipError("BtsModel: bf16_mid_storage launches bts_conv1x1_bf16_fwd_bf16 / bts_conv3x3_bf16in_fwd_f32, which a "
+                                  "plan cannot replay; set use_plans = False or bf16_mid_storage = False")
             if (self.bf16_wide_1x1 and ops.current_launch_config()[1] == 2
                     and (self.bf16_wide_1x1 == "all" or not isinstance(self.encoder.base_model, encoders.ResNet))):
                 raise BtsHipError("BtsModel: bf16_wide_1x1 launches bts_conv1x1_bf16_fwd_f32 / bts_conv1x1_bf16_wide_fwd_f32, which a "
@@ -866,6 +888,7 @@ class BtsModel(nn.Module):
             plan.bf16_wide_1x1 = self.bf16_wide_1x1 == "all"
         else:
             plan.bf16_wide_1x1 = self.bf16_wide_1x1
+            plan.bf16_mid_storage = self.bf16_mid_storage
         plan._ws.max_entries = max(plan._ws.max_entries, 2 * int(self.sub_batches))
         B, _, H, W = x.shape
         dec = self.decoder

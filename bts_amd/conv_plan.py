@@ -70,9 +70,22 @@ def tail_bf16_kernel_name(bn: int) -> str:
     return "conv_tail_bf16_kernel<%d>" % bn
 
 
-def wide_1x1_bf16_kernel_name(bn: int = 192) -> str:
-    """The kernel bts_conv1x1_bf16_fwd_f32 launches (its own entry point: no bts_conv_plan_f32 kind), as KernelTrace records it."""
-    return "conv1x1_bf16_kernel<%d>" % bn
+def wide_1x1_bf16_kernel_name(bn: int = 192, y_bf16: bool = False) -> str:
+    """The kernel bts_conv1x1_bf16_fwd_f32 (``y_bf16``: bts_conv1x1_bf16_fwd_bf16) launches (its own entry point: no
+    bts_conv_plan_f32 kind), as KernelTrace records it."""
+    return ("conv1x1_bf16_ybf16_kernel<%d>" if y_bf16 else "conv1x1_bf16_kernel<%d>") % bn
+
+
+def bf16in_3x3_tile(c_out: int) -> int:
+    """The column tile bts_conv3x3_bf16in_fwd_f32 launches: 128 where bts_conv_fwd_f32's tile choice (csrc/conv_mfma.hip:
+    choose_tile, least padded width weighted by tile efficiency) picks 128 for ``c_out``, else 64."""
+    cost = {bn: round_up(c_out, bn) * eff for bn, eff in ((128, 1.0), (64, 1.05), (32, 1.2), (48, 1.12)) if bn != 48 or c_out % 48 == 0}
+    return 128 if min(cost, key=lambda bn: (cost[bn], (128, 64, 32, 48).index(bn))) == 128 else 64
+
+
+def bf16in_3x3_kernel_name(bn: int) -> str:
+    """The kernel bts_conv3x3_bf16in_fwd_f32 launches (its own entry point: no bts_conv_plan_f32 kind), as KernelTrace records it."""
+    return "conv3x3_bf16in_kernel<%d>" % bn
 
 
 def wide_1x1_bf16_tile(c_out: int) -> int:

@@ -99,11 +99,61 @@ __device__ __forceinline__ void c1b_store(const Conv1x1Bf16Args& a, const AccT (
     }
 }
 
+// The same tile to a BF16 destination (bts_conv1x1_bf16_fwd_bf16: the bottleneck intermediate of a dense layer, whose only
+// reader -- the 3x3 growth convolution on the bf16 halo tile -- rounds every value to bf16 on its way to LDS anyway).  a.y is
+// then a bf16 buffer and a.y_pix_stride counts bf16 elements.  The value stored is c1b_store's act(e1(acc)) put through
+// pack_bf16_rne: the routine plane_store<1> rounds the halo tile's patch with, so rounding here and copying there gives the
+// consumer's LDS the bits it has today, NaN and infinity included.
+// Two store forms were built and measured (the producer alone, DenseNet161 blocks 1-2 at 352x1216, three K each, B = 16 and
+// B = 4, three forms alternating in one process, 5 rounds x 300 launches, median us per launch; both forms gave the RNE bits
+// of the fp32 kernel's output on every class):
+//   plain : every lane stores its own channel, 2 bytes -- sixteen half-width wave stores per column tile.  152 VGPRs, 3 waves
+//           per SIMD, no scratch.
+//   paired: adjacent lanes (channels n, n + 1; n even) exchange one value per row pair by DPP (quad_perm [1,0,3,2]); the even
+//           lane then stores rows 2t, the odd lane rows 2t + 1, both channels in one 4-byte store: eight stores per lane and
+//           column tile, each wave store as wide as the fp32 kernel's.  Needs a 4-byte aligned row (host: stride % 4 == 0).
+//           154 VGPRs, 3 waves per SIMD, no scratch.
+//                        fp32 store   plain   paired                          fp32 store   plain   paired
+//   B=16 block1 K  96      100.8      81.7    78.6        B=4 block1 K  96       26.8      23.7    22.0
+//               K 240      170.2     148.9   145.5                   K 240       39.9      37.2    35.1
+//               K 336      211.7     190.3   187.4                   K 336       48.7      46.5    44.7
+//        block2 K 192       37.7      32.7    30.7            block2 K 192       15.6      14.3    13.3
+//               K 480       84.8      74.3    74.3                   K 480       28.7      27.8    26.9
+//               K 720      122.4     116.8   115.1                   K 720       37.9      36.9    36.0
+// Paired is ahead of plain on eleven classes of twelve (+1.5 ... +7.5 %, spreads <= 1.0 %) and level on one: it is the form
+// kept; the plain form is not built.
+template <int ACT, int TN, typename AccT>
+__device__ __forceinline__ void c1b_store_bf16(const Conv1x1Bf16Args& a, const AccT (&acc)[TN], long pix0, int nvalid, int ncol0, int li, int lh) {
+    unsigned short* const yb = reinterpret_cast<unsigned short*>(a.y) + pix0 * a.y_pix_stride;      // wave-uniform
+    const int nv = nvalid - 4 * lh;
+    const bool odd = li & 1;
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+        const int n = ncol0 + j * 32 + li;
+        float s1 = a.e1_scale != nullptr ? a.e1_scale[n] : 1.f;
+        float b1 = a.e1_scale != nullptr ? a.e1_shift[n] : 0.f;
+        asm volatile("" : "+v"(s1), "+v"(b1));          // waited for HERE, once (see tail_bf16_store)
+        // this lane's row of the pair (rows 2t + odd) and the 4-byte slot of channels n & ~1, n | 1
+        const unsigned lane_y = (unsigned)(4 * lh + (odd ? 1 : 0)) * (unsigned)a.y_pix_stride + (unsigned)(n & ~1);
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+            const int qu = ((2 * t) & 3) + 8 * ((2 * t) >> 2);                      // row slot of r = 2t; r = 2t + 1 is qu + 1
+            const float v0 = act_fn<ACT>(fmaf(acc[j][2 * t], s1, b1)), v1 = act_fn<ACT>(fmaf(acc[j][2 * t + 1], s1, b1));
+            const float mine = odd ? v1 : v0, send = odd ? v0 : v1;                 // the partner stores the other row
+            const float recv = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, send), 0xB1, 0xF, 0xF, false));
+            const unsigned pk = odd ? pack_bf16_rne(recv, mine) : pack_bf16_rne(mine, recv);      // low half = the even channel
+            if (qu + (odd ? 1 : 0) < nv)
+                *reinterpret_cast<unsigned*>(yb + (long)qu * a.y_pix_stride + lane_y) = pk;
+        }
+    }
+}
+
 // Workgroups per CU the register file is asked to hold: BN = 128 (64 accumulator registers) four, BN = 192 (96) and
 // BN = 256 (128 + 32 for the B fragments) two -- 192 takes 152 registers and gets three by itself, 256 cannot get three.
 template <int BN> constexpr int c1b_min_wgs_per_cu() { return BN <= 128 ? 4 : 2; }
 
-template <int BN, bool EPI>
+// YBF16: the bf16 destination (c1b_store_bf16; no EPI form)
+template <int BN, bool EPI, bool YBF16 = false>
 __device__ __forceinline__ void c1b_body(const Conv1x1Bf16Args& a) {
     constexpr int TN = BN / 32, STAGE = c1b_stage_bytes<BN>();
     constexpr int NIW = BN / 16 / 4;                      // DMA wave-instructions per stage and wave (16 rows x 64 B each)
@@ -231,6 +281,10 @@ __device__ __forceinline__ void c1b_body(const Conv1x1Bf16Args& a) {
     // ---------------------------------------------------------------- epilogue (NHWC slice)
     const long left = a.npix - pix0;
     const int nvalid = left >= 32 ? 32 : (left > 0 ? (int)left : 0);
+    if constexpr (YBF16) {
+        static_assert(!EPI, "the bf16 destination has no residual epilogue");
+        dispatch_act(a.act, [&](auto act) { c1b_store_bf16<decltype(act)::value, TN>(a, acc, pix0, nvalid, n0, li, lh); });
+    } else
     dispatch_act(a.act, [&](auto act) { c1b_store<decltype(act)::value, TN, EPI>(a, acc, pix0, nvalid, n0, li, lh); });
 }
 
@@ -239,6 +293,10 @@ __global__ __launch_bounds__(256, c1b_min_wgs_per_cu<BN>()) void conv1x1_bf16_ke
 // the same tile with the bottleneck epilogue (a.res and / or a.y2 set)
 template <int BN>
 __global__ __launch_bounds__(256, c1b_min_wgs_per_cu<BN>()) void conv1x1_bf16_epi_kernel(const Conv1x1Bf16Args a) { c1b_body<BN, true>(a); }
+
+// the same tile to a bf16 destination (bts_conv1x1_bf16_fwd_bf16)
+template <int BN>
+__global__ __launch_bounds__(256, c1b_min_wgs_per_cu<BN>()) void conv1x1_bf16_ybf16_kernel(const Conv1x1Bf16Args a) { c1b_body<BN, false, true>(a); }
 
 // The layers the encoder hands to this kernel under BtsModel.bf16_wide_1x1 (bts_conv1x1_bf16_plan).  Structural: whole
 // 192-channel N tiles, whole 16-k MFMA blocks.  Measured: a declared launch of at least kC1bMinWgs workgroups.
@@ -310,11 +368,14 @@ inline bool c1w_eligible(int H, int W, int c_in, int c_out, bool has_res, int ff
 }
 
 template <int BN>
-int launch_conv1x1_bf16(Conv1x1Bf16Args a, const ConvRun& r) {
+int launch_conv1x1_bf16(Conv1x1Bf16Args a, const ConvRun& r, bool y_bf16 = false) {
     const long n_mtiles = (a.npix + C1B_BM - 1) / C1B_BM;
     a.n_ntiles = a.c_out / BN;
     const long nwg = n_mtiles * a.n_ntiles;
     const size_t lds = c1b_lds_bytes<BN>(a.c_in, a.pre_scale != nullptr);
+    if constexpr (BN == 192) {               // the bf16 destination: a.y holds bf16, a.y_pix_stride counts bf16 elements
+        if (y_bf16) return conv_launch<conv1x1_bf16_ybf16_kernel<BN>>(r, ConvChoice{}, BTS_ERR_UNSUPPORTED, nwg, nwg, 256, lds, a);
+    }
     if (a.res != nullptr || a.y2 != nullptr)
         return conv_launch<conv1x1_bf16_epi_kernel<BN>>(r, ConvChoice{}, BTS_ERR_UNSUPPORTED, nwg, nwg, 256, lds, a);
     return conv_launch<conv1x1_bf16_kernel<BN>>(r, ConvChoice{}, BTS_ERR_UNSUPPORTED, nwg, nwg, 256, lds, a);

@@ -98,6 +98,25 @@ template <int BASE, int LPP, bool AFFINE> __device__ __forceinline__ void wait_v
         default: wait_vm<0>(r); break;
     }
 }
+// A patch pass whose source is ALREADY bf16 (halo_emu_produce's XBF16: conv3x3_bf16in_kernel): the thread's four channels are
+// 8 bytes, one untracked global_load_dwordx2, and go to LDS as they are.  One vector-memory operation per pass, like the
+// four-register load above (LPP = 1): vmcnt counts operations, not bytes, so every counted wait below keeps its number.
+struct PatchRegsBf16 { u32x2 v = {0u, 0u}; };
+__device__ __forceinline__ void load_untracked(u32x2& dst, const unsigned short* p) {
+    asm volatile("global_load_dwordx2 %0, %1, off" : "=v"(dst) : "v"(p) : "memory");
+}
+template <int N> __device__ __forceinline__ void wait_vm(PatchRegsBf16& r) {
+    asm volatile("s_waitcnt vmcnt(%1)" : "+v"(r.v) : "n"(N) : "memory");
+}
+template <int BASE, int LPP> __device__ __forceinline__ void wait_vm_passes(int k, PatchRegsBf16& r) {
+    switch (k) {
+        case 0: wait_vm<BASE>(r); break;
+        case 1: wait_vm<BASE + LPP>(r); break;
+        case 2: wait_vm<BASE + 2 * LPP>(r); break;
+        case 3: wait_vm<BASE + 3 * LPP>(r); break;
+        default: wait_vm<0>(r); break;
+    }
+}
 // The raw barrier between tap-steps, behind the wait that says what has to be complete by then: every LDS operation of the
 // wave and all but its VM youngest vector-memory operations (NO_VM: a consumer has none)
 constexpr int NO_VM = -1;
@@ -111,6 +130,7 @@ template <int VM> __device__ __forceinline__ void wait_then_barrier() {
 // What a producer reads
 struct HaloEmuSource {
     const float* x; unsigned x_pix_stride; int H, W, bfr, y0, x0, pad_y, pad_x;      // NHWC input, the tile, the padding
+                                                                                     // (XBF16: a bf16 buffer, stride in bf16 elements)
     const float* pre_scale; const float* pre_shift; bool has_pre; int pre_relu;      // AFFINE: scale / shift per input channel
                                                                                      // (any readable address without has_pre)
     const unsigned short* w; int w_rows, w_ld;     // bf16 weights [NP planes][w_rows][w_ld], k = tap * tap_stride + channel
@@ -119,8 +139,10 @@ struct HaloEmuSource {
 };
 
 // PRODUCER waves 4..7 (one per SIMD), from the start of the kernel to the end of the K loop.  `before_first_barrier` runs
-// once the patch of chunk 0 is stored.
-template <int BN, int KS, int NP, bool AFFINE, typename Extra>
+// once the patch of chunk 0 is stored.  XBF16 (NP 1, no AFFINE): the patch source holds bf16 -- load_a is one 8-byte load,
+// store_a zeroes the pixels outside the image and writes the 8 bytes to the slot plane_store<1> would have rounded them into.
+// Nothing else differs: the same addresses (in elements), the same clamps, one operation per pass, the same waits.
+template <int BN, int KS, int NP, bool AFFINE, bool XBF16 = false, typename Extra>
 __device__ __forceinline__ void halo_emu_produce(const HaloEmuSource& in, char* const As, char* const Bs, int tid, int wv,
                                                  Extra&& before_first_barrier) {
     using G = HaloEmuGeom<BN, KS, NP>;
@@ -132,7 +154,8 @@ __device__ __forceinline__ void halo_emu_produce(const HaloEmuSource& in, char* 
     constexpr int NI = NP * BN / 16;                     // DMA wave-instructions per weight stage (16 rows x 64 B each)
     constexpr int NIW = NI / 4;                          // ... per producer wave: 6 / 3 (BN 128 / 64, NP 3), 2 / 1 (NP 1)
     static_assert(NI % 4 == 0 && PPS * (T - 1) >= PA && PPS <= 2, "producer work divides evenly");
-    typedef PatchRegs<AFFINE> regs_t;
+    static_assert(!XBF16 || (NP == 1 && !AFFINE), "a bf16 patch is the one-plane tile's, without a prologue");
+    typedef std::conditional_t<XBF16, PatchRegsBf16, PatchRegs<AFFINE>> regs_t;
     const int ptid = tid - 256, lane = tid & 63;
     const int lrow = ptid >> 3, lk = (ptid & 7) * 4;
     const int nsteps = in.nchunks * T;
@@ -155,7 +178,8 @@ __device__ __forceinline__ void halo_emu_produce(const HaloEmuSource& in, char* 
     }
     auto load_a = [&](int p, int chunk, regs_t& r) {
         const unsigned cs = (unsigned)(chunk * BK);
-        load_untracked(r.v, in.x + (abase[p] + cs));
+        if constexpr (XBF16) load_untracked(r.v, reinterpret_cast<const unsigned short*>(in.x) + (abase[p] + cs));
+        else load_untracked(r.v, in.x + (abase[p] + cs));
         if constexpr (AFFINE) {
             load_untracked(r.ps, in.pre_scale + (cs + lk));
             load_untracked(r.pb, in.pre_shift + (cs + lk));
@@ -163,6 +187,11 @@ __device__ __forceinline__ void halo_emu_produce(const HaloEmuSource& in, char* 
     };
     auto store_a = [&](int p, char* dstbuf, regs_t r) {
         if (!((inpatch >> p) & 1u)) return;
+        if constexpr (XBF16) {
+            const bool ok = (inimg >> p) & 1u;                           // zero padding: bf16 +0 is fp32 +0 rounded
+            *reinterpret_cast<u32x2*>(dstbuf + awr[p]) = u32x2{ok ? r.v.x : 0u, ok ? r.v.y : 0u};
+            return;
+        } else {
         f32x4 v = r.v;
         if constexpr (AFFINE) {
             if (in.has_pre) v = v * r.ps + r.pb;
@@ -171,6 +200,7 @@ __device__ __forceinline__ void halo_emu_produce(const HaloEmuSource& in, char* 
         const bool ok = (inimg >> p) & 1u;                               // zero padding AFTER the prologue
         v.x = ok ? v.x : 0.f; v.y = ok ? v.y : 0.f; v.z = ok ? v.z : 0.f; v.w = ok ? v.w : 0.f;
         plane_store<NP>(dstbuf, G::A_PLANE, awr[p], v);
+        }
     };
     // weight DMA: producer wave pw sends wave-instructions q = pw + 4u: rows [16 rb, 16 rb + 16) of plane q / (BN/16)
     const int pw = wv - 4;

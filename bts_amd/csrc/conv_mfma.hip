@@ -851,6 +851,7 @@ int conv_launch(const ConvRun& r, const ConvChoice& choice, int too_many, long t
 #include "conv_grouped.inc"
 #include "conv_grouped_wgrad.inc"
 #include "conv_tail_bf16.inc"
+#include "conv_3x3_bf16in.inc"
 #include "conv_1x1_bf16.inc"
 #include "conv_1x1.inc"
 #include "conv_stem.inc"
@@ -1307,7 +1308,8 @@ extern "C" int bts_conv1x1_bf16_plan(int h, int w, int c_in, int c_out, int fill
 static int conv1x1_bf16_run(const float* x, long x_pix_stride, long npix, int c_in, const void* w_bf16, int k_pad, int c_out,
                             int c_out_pad, const float* pre_scale, const float* pre_shift, int pre_relu, const float* e1_scale,
                             const float* e1_shift, const float* res, long res_pix_stride, int act, float* y, long y_pix_stride,
-                            float* y2, long y2_pix_stride, int bn, bool any_width, bts_stream_t stream) {
+                            float* y2, long y2_pix_stride, int bn, bool any_width, bts_stream_t stream, bool y_bf16 = false) {
+    if (y_bf16 && ((uintptr_t)y & 7)) return BTS_ERR_INVALID;      // a bf16 destination: 8-byte aligned base
     if (!x || !w_bf16 || !y || npix <= 0 || c_in <= 0 || c_out <= 0 || k_pad <= 0 || c_out_pad < c_out) return BTS_ERR_INVALID;
     if ((pre_scale == nullptr) != (pre_shift == nullptr) || !act_e2_ok(act, e1_scale, e1_shift)) return BTS_ERR_INVALID;
     if (!nhwc_view_ok(x, x_pix_stride, c_in) || (y_pix_stride & 3) || y_pix_stride < c_out || ((uintptr_t)y & 3) ||
@@ -1333,6 +1335,7 @@ static int conv1x1_bf16_run(const float* x, long x_pix_stride, long npix, int c_
     a.e1_scale = e1_scale; a.e1_shift = e1_shift; a.act = act; a.y = y; a.y_pix_stride = y_pix_stride; a.n_ntiles = 0;
     a.res = res; a.res_pix_stride = res_pix_stride; a.y2 = y2; a.y2_pix_stride = y2_pix_stride;
     const ConvRun run = launch_on(stream);
+    if (y_bf16) return launch_conv1x1_bf16<192>(a, run, true);      // bn == 192: the only caller passes it
     return bn == 128 ? launch_conv1x1_bf16<128>(a, run) : bn == 192 ? launch_conv1x1_bf16<192>(a, run) : launch_conv1x1_bf16<256>(a, run);
 }
 
@@ -1342,6 +1345,78 @@ extern "C" int bts_conv1x1_bf16_fwd_f32(const float* x, long x_pix_stride, long 
                                         bts_stream_t stream) {
     return conv1x1_bf16_run(x, x_pix_stride, npix, c_in, w_bf16, k_pad, c_out, c_out_pad, pre_scale, pre_shift, pre_relu, e1_scale,
                             e1_shift, nullptr, 0, act, y, y_pix_stride, nullptr, 0, 192, false, stream);
+}
+
+// ---- the same launch to a bf16 destination (BtsModel.bf16_mid_storage: the bottleneck intermediate of a dense layer): the
+//      checks of the fp32 entry point on every operand, y's stride counted in bf16 elements
+extern "C" int bts_conv1x1_bf16_fwd_bf16(const float* x, long x_pix_stride, long npix, int c_in, const void* w_bf16, int k_pad,
+                                         int c_out, int c_out_pad, const float* pre_scale, const float* pre_shift, int pre_relu,
+                                         const float* e1_scale, const float* e1_shift, int act, void* y, long y_pix_stride,
+                                         bts_stream_t stream) {
+    return conv1x1_bf16_run(x, x_pix_stride, npix, c_in, w_bf16, k_pad, c_out, c_out_pad, pre_scale, pre_shift, pre_relu, e1_scale,
+                            e1_shift, nullptr, 0, act, static_cast<float*>(y), y_pix_stride, nullptr, 0, 192, false, stream, true);
+}
+
+// ---- 3x3 convolution reading a bf16 NHWC tensor on the bf16 halo tile (conv_3x3_bf16in.inc): its own opt-in entry point and
+//      plan query, so that bts_conv_fwd_f32 / bts_conv_plan_f32 answer for every descriptor exactly as they did without it
+//
+// The query accepts a layer iff bts_conv_plan_f32 answers BTS_CONV_KIND_HALO_BF16 for it at precision 2 (no prologue, no
+// residual, no y2, stride 1, dilation 1, NHWC), asked of conv_plan itself on a descriptor of that layer with a split-K
+// workspace lent, as the encoder lends one: without a workspace the dispatch never splits K and takes the halo tile for a
+// superset of these layers.
+//
+// Measured (profiles/bf16_mid_bench.txt: the layer's pair, bottleneck 1x1 on the wide tile + this convolution, intermediate in
+// fp32 against bf16, DenseNet161 at 352x1216, fill_frames 16, both forms alternating in one process, 5 rounds x 200 pairs; a
+// class wins if the gain of the medians exceeds the larger spread) -- every class the dispatch answer admits, gain at B = 16 /
+// at the B = 4 sub-batch launch:
+//   block 1, 88x304: K  96 +50.4 / +34.8 %,  K 240 +31.8 / +32.7 %,  K 336 +26.6 / +31.0 %      (spreads <= 2.3 %)
+//   block 2, 44x152: K 192 +30.3 / +27.9 %,  K 480 +21.9 / +17.7 %,  K 720 +13.8 / +14.3 %      (spreads <= 0.6 %)
+// No class loses at B = 4, so the query leaves none and needs no threshold of its own.  Blocks 3 and 4 (22x76, 11x38: under
+// 0.80 real pixels of their tile grid, not BTS_CONV_KIND_HALO_BF16) stay out: forced through the entry point they ran +9 ...
+// +62 % faster than the row-tiled / split-K kernels they take today, but with another sum order, hence other bits.  Whole
+// model, configs[1], bf16 + bf16_tail_convs + bf16_wide_1x1, two hipGraphs alternating: 17.80 -> 16.80 ms, 899 -> 952 frames/s,
+// +5.9 % (spreads 1.0 / 0.9 %), outputs bit-identical.
+extern "C" int bts_conv3x3_bf16in_plan(int h, int w, int c_in, int c_out, int fill_frames, int* bn, long* workgroups) {
+    int ff, prec;                                           // the arithmetic is this entry point's own: no precision argument
+    if (!bn || !workgroups || !resolve_declaration(fill_frames, 2, &ff, &prec)) return BTS_ERR_INVALID;
+    *bn = 0; *workgroups = 0;
+    if (h <= 0 || w <= 0 || c_in <= 0 || c_out <= 0 || (c_in % BK) || prec != 2) return 0;
+    // a plan query checks pointers and never follows them
+    float* const dummy = reinterpret_cast<float*>((uintptr_t)1 << 20);
+    bts_conv_desc d{};
+    d.x = dummy; d.w = dummy; d.y = dummy; d.w_split = dummy;
+    d.B = 1; d.h_in = h; d.w_in = w; d.up = 1; d.ksize = 3; d.dil = 1; d.stride = 1; d.pad = 1;
+    d.c_in_ld = c_in; d.k_pad = 9 * c_in; d.x_pix_stride = c_in;
+    d.c_out = c_out; d.c_out_pad = (c_out + 31) / 32 * 32; d.y_pix_stride = (c_out + 3) & ~3;
+    d.precision = 2; d.fill_frames = ff;
+    d.splitk_ws = dummy; d.splitk_ws_floats = (long)1 << 40;
+    ConvChoice c;
+    if (conv_plan(&d, false, c) != 0 || c.kind != BTS_CONV_KIND_HALO_BF16) return 0;
+    *bn = c.bn; *workgroups = (long)ff * tiles_4x32(h, w) * ((c_out + c.bn - 1) / c.bn);
+    return 0;
+}
+
+extern "C" int bts_conv3x3_bf16in_fwd_f32(const void* x, long x_pix_stride, int B, int h, int w, int c_in, const void* w_bf16,
+                                          int k_pad, int c_out, int c_out_pad, const float* e1_scale, const float* e1_shift, int act,
+                                          float* y, long y_pix_stride, bts_stream_t stream) {
+    if (!x || !w_bf16 || !y) return BTS_ERR_INVALID;
+    if (B <= 0 || h <= 0 || w <= 0 || c_in <= 0 || c_out <= 0 || k_pad <= 0) return BTS_ERR_INVALID;
+    if ((c_out_pad & 31) || c_out_pad < c_out) return BTS_ERR_INVALID;
+    if (((uintptr_t)x & 7) || (x_pix_stride & 3) || x_pix_stride < c_in || y_pix_stride < c_out || ((uintptr_t)w_bf16 & 15) ||
+        ((uintptr_t)y & 3) || ((uintptr_t)e1_scale & 3) || ((uintptr_t)e1_shift & 3)) return BTS_ERR_INVALID;
+    if (!act_e2_ok(act, e1_scale, e1_shift)) return BTS_ERR_INVALID;
+    if ((c_in % BK) || (k_pad & 7) || k_pad < 9 * (long)c_in) return BTS_ERR_UNSUPPORTED;
+    // the kernel addresses both operands with 32-bit element offsets, decodes tiles with 32-bit arithmetic and addresses the
+    // pixels of an output tile row with a 32-bit per-lane offset (bts_conv_tail_bf16_fwd_f32's limits)
+    if (!fits_u32((double)B * h * w * (double)x_pix_stride) || (double)B * h * w >= 2147483648.0 ||
+        !fits_u32((double)c_out_pad * (double)k_pad) || !fits_u32(64.0 * (double)y_pix_stride)) return BTS_ERR_UNSUPPORTED;
+    Conv3x3Bf16InArgs a;
+    a.x = static_cast<const unsigned short*>(x); a.x_pix_stride = x_pix_stride; a.B = B; a.H = h; a.W = w; a.c_in = c_in;
+    a.w = static_cast<const unsigned short*>(w_bf16); a.k_pad = k_pad; a.c_out = c_out; a.c_out_pad = c_out_pad;
+    a.e1_scale = e1_scale; a.e1_shift = e1_shift; a.act = act; a.y = y; a.y_pix_stride = y_pix_stride; a.n_ntiles = 0;
+    int bm, bn;
+    choose_tile((long)B * h * w, c_out, &bm, &bn);          // bts_conv_fwd_f32's column tile: 128, else 64 (48 and 32 pad to 64)
+    return bn == 128 ? launch_conv3x3_bf16in<128>(a, launch_on(stream)) : launch_conv3x3_bf16in<64>(a, launch_on(stream));
 }
 
 // ---- the same tile at 128 / 192 / 256 output channels per workgroup with the bottleneck epilogue (res, y2): ResNe(X)t's

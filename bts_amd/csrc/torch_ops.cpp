@@ -434,6 +434,102 @@ void conv1x1_bf16(const Tensor& x, const Tensor& w_plane, OptTensor pre_scale, O
                                       ps, pb, (int)(pre_relu != 0), es, eb, (int)act, y.data_ptr<float>(), ys, current_stream()), op);
 }
 
+// ------------------------------------------------------------------------------- the bf16-resident bottleneck intermediate
+// [rows, C] view of a BFLOAT16 NHWC buffer: unit channel stride, a row stride that is a multiple of 4 elements, 8-byte aligned
+long rows2d_stride_bf16(const Tensor& t, const char* op, const char* what) {
+    TORCH_CHECK(t.is_cuda(), op, ": ", what, " must be a CUDA(ROCm) tensor (no CPU fallback)");
+    TORCH_CHECK(t.scalar_type() == at::kBFloat16, op, ": ", what, " must be bfloat16, got ", t.scalar_type());
+    TORCH_CHECK(t.dim() == 2 && t.stride(1) == 1, op, ": ", what, " must be a 2-D view with unit channel stride");
+    const long s = t.size(0) > 1 ? t.stride(0) : t.size(1);
+    TORCH_CHECK(s % 4 == 0 && (reinterpret_cast<uintptr_t>(t.data_ptr()) & 7) == 0, op, ": ", what,
+                " must have a pixel stride that is a multiple of 4 elements and an 8-byte aligned base");
+    return s;
+}
+
+// conv1x1_bf16 above with a bfloat16 destination (bts_conv1x1_bf16_fwd_bf16): y is a [npix, c_out] view of a bf16 NHWC buffer.
+// The other operands and geom = {npix, c_in, c_out, pre_relu, act} as conv1x1_bf16.
+void conv1x1_bf16_ybf16(const Tensor& x, const Tensor& w_plane, OptTensor pre_scale, OptTensor pre_shift, OptTensor e1_scale,
+                        OptTensor e1_shift, Tensor y, std::vector<int64_t> geom) {
+    const char* op = "bts_hip::conv1x1_bf16_ybf16";
+    TORCH_CHECK(geom.size() == 5, op, ": geom must hold 5 integers, got ", geom.size());
+    const int64_t npix = geom[0], c_in = geom[1], c_out = geom[2], pre_relu = geom[3], act = geom[4];
+    TORCH_CHECK(npix > 0 && c_in > 0 && c_out > 0, op, ": non-positive dimension");
+    TORCH_CHECK(c_in % 16 == 0 && c_out % 192 == 0, op, ": needs c_in % 16 == 0 and c_out % 192 == 0, got ", c_in, " -> ", c_out);
+    const long xs = rows2d_stride(x, op, "x"), ys = rows2d_stride_bf16(y, op, "y");
+    TORCH_CHECK(w_plane.is_cuda(), op, ": w_plane must be a CUDA(ROCm) tensor (no CPU fallback)");
+    TORCH_CHECK(w_plane.scalar_type() == at::kShort || w_plane.scalar_type() == at::kBFloat16, op,
+                ": w_plane must hold bf16 bits (int16 from ops.round_bf16, or bfloat16), got ", w_plane.scalar_type());
+    same_device(x, w_plane, op, "w_plane");
+    same_device(x, y, op, "y");
+    TORCH_CHECK(x.size(0) == npix && x.size(1) >= c_in, op, ": x (", x.sizes(), ") is not a [npix, >= c_in] view");
+    TORCH_CHECK(y.size(0) == npix && y.size(1) == c_out, op, ": y (", y.sizes(), ") is not a [npix, c_out] view");
+    const int64_t wd = w_plane.dim();
+    TORCH_CHECK(w_plane.is_contiguous() && (wd == 2 || (wd == 3 && w_plane.size(0) == 1)), op,
+                ": w_plane must be contiguous [c_out_pad, k_pad] or [1, c_out_pad, k_pad] (ops.round_bf16), got ", w_plane.sizes());
+    const int64_t c_out_pad = w_plane.size(wd - 2), k_pad = w_plane.size(wd - 1);
+    TORCH_CHECK(c_out_pad >= c_out && k_pad >= c_in && k_pad % 32 == 0, op, ": w_plane ", w_plane.sizes(), " does not hold ", c_out, " rows of ",
+                c_in, " channels padded to a multiple of 32");
+    TORCH_CHECK(act >= 0 && act <= 2, op, ": act must be 0 (none), 1 (ReLU) or 2 (ELU), got ", act);
+    auto vec = [&](const OptTensor& t, const char* what, int64_t n) -> const float* {
+        if (!(t.has_value() && t->defined())) return nullptr;
+        need_f32_cuda(*t, op, what);
+        same_device(x, *t, op, what);
+        TORCH_CHECK(t->is_contiguous() && t->numel() >= n, op, ": ", what, " must be a contiguous vector of at least ", n, " floats");
+        return t->data_ptr<float>();
+    };
+    const float* ps = vec(pre_scale, "pre_scale", c_in);
+    const float* pb = vec(pre_shift, "pre_shift", c_in);
+    const float* es = vec(e1_scale, "e1_scale", c_out);
+    const float* eb = vec(e1_shift, "e1_shift", c_out);
+    TORCH_CHECK((ps == nullptr) == (pb == nullptr) && (es == nullptr) == (eb == nullptr), op, ": give both vectors of an affine or neither");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+    check_rc(bts_conv1x1_bf16_fwd_bf16(x.data_ptr<float>(), xs, (long)npix, (int)c_in, w_plane.data_ptr(), (int)k_pad, (int)c_out, (int)c_out_pad,
+                                       ps, pb, (int)(pre_relu != 0), es, eb, (int)act, y.data_ptr(), ys, current_stream()), op);
+}
+
+// act(e1(conv3x3(x))) from a bfloat16 NHWC input as one launch of the bf16 halo tile (bts_conv3x3_bf16in_fwd_f32).  x: [B*h*w,
+// >= c_in] view of a bf16 buffer; w_plane: the one-plane bf16 form of the packed 3x3 weight, [c_out_pad, k_pad] or
+// [1, c_out_pad, k_pad], int16 bits (ops.round_bf16) or bfloat16; y: [B*h*w, c_out] fp32 NHWC view.
+// geom = {B, h, w, c_in, c_out, act}.
+void conv3x3_bf16in(const Tensor& x, const Tensor& w_plane, OptTensor e1_scale, OptTensor e1_shift, Tensor y, std::vector<int64_t> geom) {
+    const char* op = "bts_hip::conv3x3_bf16in";
+    TORCH_CHECK(geom.size() == 6, op, ": geom must hold 6 integers, got ", geom.size());
+    const int64_t B = geom[0], h = geom[1], w = geom[2], c_in = geom[3], c_out = geom[4], act = geom[5];
+    TORCH_CHECK(B > 0 && h > 0 && w > 0 && c_in > 0 && c_out > 0, op, ": non-positive dimension");
+    TORCH_CHECK(c_in % 32 == 0, op, ": c_in (", c_in, ") must be a multiple of 32");
+    const long xs = rows2d_stride_bf16(x, op, "x");
+    need_f32_cuda(y, op, "y");
+    TORCH_CHECK(y.dim() == 2 && y.stride(1) == 1, op, ": y must be a 2-D view with unit channel stride");
+    const long ys = y.size(0) > 1 ? y.stride(0) : y.size(1);
+    TORCH_CHECK(w_plane.is_cuda(), op, ": w_plane must be a CUDA(ROCm) tensor (no CPU fallback)");
+    TORCH_CHECK(w_plane.scalar_type() == at::kShort || w_plane.scalar_type() == at::kBFloat16, op,
+                ": w_plane must hold bf16 bits (int16 from ops.round_bf16, or bfloat16), got ", w_plane.scalar_type());
+    same_device(x, w_plane, op, "w_plane");
+    same_device(x, y, op, "y");
+    TORCH_CHECK(x.size(0) == B * h * w && x.size(1) >= c_in, op, ": x (", x.sizes(), ") is not a [B*h*w, >= c_in] view");
+    TORCH_CHECK(y.size(0) == B * h * w && y.size(1) == c_out, op, ": y (", y.sizes(), ") is not a [B*h*w, c_out] view");
+    const int64_t wd = w_plane.dim();
+    TORCH_CHECK(w_plane.is_contiguous() && (wd == 2 || (wd == 3 && w_plane.size(0) == 1)), op,
+                ": w_plane must be contiguous [c_out_pad, k_pad] or [1, c_out_pad, k_pad] (ops.round_bf16), got ", w_plane.sizes());
+    const int64_t c_out_pad = w_plane.size(wd - 2), k_pad = w_plane.size(wd - 1);
+    TORCH_CHECK(c_out_pad >= c_out && c_out_pad % 32 == 0 && k_pad >= 9 * c_in && k_pad % 8 == 0, op, ": w_plane ", w_plane.sizes(),
+                " does not hold ", c_out, " rows (padded to a multiple of 32) of 9 x ", c_in, " channels");
+    TORCH_CHECK(act >= 0 && act <= 2, op, ": act must be 0 (none), 1 (ReLU) or 2 (ELU), got ", act);
+    auto vec = [&](const OptTensor& t, const char* what) -> const float* {
+        if (!(t.has_value() && t->defined())) return nullptr;
+        need_f32_cuda(*t, op, what);
+        same_device(x, *t, op, what);
+        TORCH_CHECK(t->is_contiguous() && t->numel() >= c_out_pad, op, ": ", what, " must be a contiguous vector of at least ", c_out_pad, " floats");
+        return t->data_ptr<float>();
+    };
+    const float* es = vec(e1_scale, "e1_scale");
+    const float* eb = vec(e1_shift, "e1_shift");
+    TORCH_CHECK((es == nullptr) == (eb == nullptr), op, ": give both e1 vectors or neither");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+    check_rc(bts_conv3x3_bf16in_fwd_f32(x.data_ptr(), xs, (int)B, (int)h, (int)w, (int)c_in, w_plane.data_ptr(), (int)k_pad, (int)c_out,
+                                        (int)c_out_pad, es, eb, (int)act, y.data_ptr<float>(), ys, current_stream()), op);
+}
+
 // ---------------------------------------------------------- wide 1x1, bf16 operands, 128 / 192 / 256 wide, bottleneck epilogue
 // act(e1(conv1x1(bf16(pre(x)))) + res), also written to y2, as one launch of bts_conv1x1_bf16_wide_fwd_f32.  The operands of
 // conv1x1_bf16 above, plus res / y2: optional [npix, c_out] NHWC views.  geom = {npix, c_in, c_out, pre_relu, act, bn}.
@@ -564,6 +660,9 @@ TORCH_LIBRARY(bts_hip, m) {
     m.def("conv_tail_bf16(Tensor x, Tensor w_main, Tensor w_tail, Tensor tail, Tensor? e2_scale, Tensor? e2_shift, Tensor(a!) y, int[] geom) -> ()");
     m.def("conv1x1_bf16(Tensor x, Tensor w_plane, Tensor? pre_scale, Tensor? pre_shift, Tensor? e1_scale, Tensor? e1_shift, Tensor(a!) y, "
           "int[] geom) -> ()");
+    m.def("conv1x1_bf16_ybf16(Tensor x, Tensor w_plane, Tensor? pre_scale, Tensor? pre_shift, Tensor? e1_scale, Tensor? e1_shift, "
+          "Tensor(a!) y, int[] geom) -> ()");
+    m.def("conv3x3_bf16in(Tensor x, Tensor w_plane, Tensor? e1_scale, Tensor? e1_shift, Tensor(a!) y, int[] geom) -> ()");
     m.def("conv1x1_bf16_wide(Tensor x, Tensor w_plane, Tensor? pre_scale, Tensor? pre_shift, Tensor? e1_scale, Tensor? e1_shift, Tensor? res, "
           "Tensor(a!) y, Tensor(b!)? y2, int[] geom) -> ()");
     m.def("depth_loss(Tensor est, Tensor gt, Tensor? mask, float gt_min, int kind, float param) -> (Tensor loss, Tensor stats)");
@@ -582,6 +681,8 @@ TORCH_LIBRARY_IMPL(bts_hip, CUDA, m) {
     m.impl("upconv_up9", &upconv_up9);
     m.impl("conv_tail_bf16", &conv_tail_bf16);
     m.impl("conv1x1_bf16", &conv1x1_bf16);
+    m.impl("conv1x1_bf16_ybf16", &conv1x1_bf16_ybf16);
+    m.impl("conv3x3_bf16in", &conv3x3_bf16in);
     m.impl("conv1x1_bf16_wide", &conv1x1_bf16_wide);
     m.impl("depth_loss", &depth_loss);
     m.impl("depth_loss_backward", &depth_loss_backward);

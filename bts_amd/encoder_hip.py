@@ -45,11 +45,19 @@ class DenseNetHip:
     ops.conv1x1_bf16_plan accepts on the wide bf16 tile (ops.conv1x1_bf16_forward: 192 output channels per workgroup, the
     pre-rounded weight plane) -- under the bf16 launch precision only; fp32 / bf16x3 forwards, transitions and bottlenecks of
     another width (DenseNet121: 128) stay on ops.conv_forward.  "all": also every bottleneck ops.conv1x1_bf16_wide_plan accepts
-    (ops.conv1x1_bf16_wide_forward: DenseNet121's 128-wide ones); transitions stay."""
+    (ops.conv1x1_bf16_wide_forward: DenseNet121's 128-wide ones); transitions stay.
+
+    ``bf16_mid_storage`` (BtsModel.bf16_mid_storage sets it): True keeps the bottleneck intermediate of a dense layer in
+    bfloat16 -- written by ops.conv1x1_bf16_forward into a bf16 workspace, read by ops.conv3x3_bf16in_forward -- where BOTH the
+    bottleneck takes the wide bf16 tile (``bf16_wide_1x1`` set and ops.conv1x1_bf16_plan eligible) and
+    ops.conv3x3_bf16in_plan accepts the growth convolution (the layers conv_forward runs on the bf16 halo tile, which rounds
+    every value it reads to bf16: the outputs are bit-identical).  Every other layer, and every forward that is not under
+    the bf16 launch precision, runs exactly as without it."""
 
     def __init__(self, features: nn.Sequential, key_module: Optional[nn.Module] = None):
         self.features = features
         self.bf16_wide_1x1 = False
+        self.bf16_mid_storage = False
         self.key_module = key_module if key_module is not None else features   # whose tensors fingerprint the packs
         self._pack = None
         self._pack_key = None
@@ -118,6 +126,23 @@ class DenseNetHip:
         torch.cuda.current_stream(device).synchronize()
         P["planes_made"] = True
 
+    def _round_growth_planes(self, P, device):
+        """The same for the 3x3 growth weights (the plane conv_forward's bf16 halo tile streams, and
+        ops.conv3x3_bf16in_forward): made on the first forward that keeps a bottleneck intermediate in bf16, all at once,
+        finished before this returns."""
+        for layers in P["blocks"]:
+            for L in layers:
+                ops._derived_weight(L["w2"], "_bts_round1", ops.round_bf16)
+        torch.cuda.current_stream(device).synchronize()
+        P["growth_planes_made"] = True
+
+    def _mid_bf16(self, ws, device):
+        """The bf16 twin of the workspace's ``mid``: allocated when a forward with ``bf16_mid_storage`` first needs it, kept in
+        the workspace from then on."""
+        if "mid_bf16" not in ws:
+            ws["mid_bf16"] = torch.zeros(ws["mid"].shape, dtype=torch.bfloat16, device=device)
+        return ws["mid_bf16"]
+
     # ----------------------------------------------------------------------- workspace
     def _workspace(self, B, H, W, device, slot=0):
         return self._ws.get((B, H, W, str(device), slot), lambda: self._alloc_workspace(B, H, W, device))
@@ -171,12 +196,24 @@ class DenseNetHip:
             h, w = hs[bi + 1], wss[bi + 1]
             buf = ws["blk%d" % bi]
             mid = ws["mid"][: B * h * w]
+            # the bottleneck intermediate in bf16: where the growth convolution runs on the bf16 halo tile (per block: the
+            # query reads the map and the two widths) and, per layer below, the bottleneck on the wide bf16 tile
+            mid_bf16 = bool(self.bf16_mid_storage) and bool(wide_bf16) and ops.conv3x3_bf16in_plan(h, w, self.c_mid, self.growth).eligible
             for li, L in enumerate(layers):
                 cin = L["cin"]
                 if wide_bf16 and ops.conv1x1_bf16_plan(h, w, cin, self.c_mid).eligible:
                     if not P.get("planes_made"):
                         self._round_bottleneck_planes(P, dev)
                     wb = ops._derived_weight(L["w1"], "_bts_round1", ops.round_bf16)      # cached on the packed weight
+                    if mid_bf16:
+                        if not P.get("growth_planes_made"):
+                            self._round_growth_planes(P, dev)
+                        midb = self._mid_bf16(ws, dev)[: B * h * w]
+                        ops.conv1x1_bf16_forward(buf[:, :cin], B * h * w, cin, wb, self.c_mid, midb, pre=L["pre"], pre_relu=True,
+                                                 e1=L["e1"], act=RELU, tag="enc_b%d_1x1_mid16" % (bi + 1))
+                        ops.conv3x3_bf16in_forward(midb, B, h, w, self.c_mid, ops._derived_weight(L["w2"], "_bts_round1", ops.round_bf16),
+                                                   self.growth, buf[:, cin:cin + self.growth], tag="enc_b%d_3x3_mid16" % (bi + 1))
+                        continue
                     ops.conv1x1_bf16_forward(buf[:, :cin], B * h * w, cin, wb, self.c_mid, mid, pre=L["pre"], pre_relu=True,
                                              e1=L["e1"], act=RELU, tag="enc_b%d_1x1" % (bi + 1))
                 elif wide_bf16 == "all" and ops.conv1x1_bf16_wide_plan(h, w, cin, self.c_mid).eligible:

@@ -91,6 +91,20 @@ def _rows2d(t: torch.Tensor, name: str) -> Tuple[int, int]:
     return t.stride(0), t.shape[1]
 
 
+def _rows2d_bf16(t: torch.Tensor, name: str) -> Tuple[int, int]:
+    """A [npix, C] view of a BFLOAT16 NHWC buffer (a bf16-resident activation): unit channel stride, a pixel stride that is
+    a multiple of 4 elements, an 8-byte aligned base -- what the kernels that move four channels per lane need."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise BtsHipError("bts_amd.%s: expected a CUDA/ROCm tensor (the hot path has no CPU fallback)" % name)
+    if t.dtype != torch.bfloat16:
+        raise BtsHipError("bts_amd.%s: expected bfloat16, got %s" % (name, t.dtype))
+    if t.dim() != 2 or t.stride(1) != 1 or t.stride(0) < t.shape[1]:
+        raise BtsHipError("bts_amd.%s: expected a [npix, C] view with unit channel stride" % name)
+    if t.stride(0) % 4 or t.data_ptr() % 8:
+        raise BtsHipError("bts_amd.%s: bf16 rows must be 8-byte aligned (pixel stride %d, a multiple of 4 elements)" % (name, t.stride(0)))
+    return t.stride(0), t.shape[1]
+
+
 def _rows2d_c(t: torch.Tensor, C: int, npix: int, name: str) -> int:
     """The pixel stride of a _rows2d view that a kernel walks as ``npix`` rows of ``C`` channels, 16 bytes per lane:
     C a positive multiple of 4 within the view's width, exactly npix rows, 16-byte aligned rows."""
@@ -1208,10 +1222,14 @@ def conv1x1_bf16_forward(x2d: torch.Tensor, npix: int, c_in: int, w_plane: torch
     view (c_in channels read), w_plane the one-plane bf16 form of the layer's packed weight (``round_bf16(w_packed)``:
     int16 [1, c_out_pad, k_pad], or the same bits as [c_out_pad, k_pad] / bfloat16), pre / e1 (scale, shift) pairs of >= c_in /
     >= c_out floats, y2d [npix, c_out] NHWC view (a channel slice is fine).  Runs whatever the plan query says: callers ask
-    conv1x1_bf16_plan first."""
+    conv1x1_bf16_plan first.
+
+    A ``torch.bfloat16`` y2d is a bf16-resident destination (bts_conv1x1_bf16_fwd_bf16): the same value, rounded once more to
+    the nearest bf16 (ties to even) and stored in two bytes -- for a consumer that reads bf16 (conv3x3_bf16in_forward)."""
     name = "conv1x1_bf16_forward"
     xs, xc = _rows2d(x2d, name)
-    ys, yc = _rows2d(y2d, name)
+    y_bf16 = isinstance(y2d, torch.Tensor) and y2d.dtype == torch.bfloat16
+    ys, yc = _rows2d_bf16(y2d, name) if y_bf16 else _rows2d(y2d, name)
     if not isinstance(w_plane, torch.Tensor) or not w_plane.is_cuda or w_plane.dtype not in (torch.int16, torch.bfloat16):
         raise BtsHipError("conv1x1_bf16_forward: w_plane must be an int16 / bfloat16 CUDA/ROCm tensor (round_bf16 of the packed weight)")
     if c_in <= 0 or c_in % 16 or c_out <= 0 or c_out % 192:
@@ -1219,7 +1237,7 @@ def conv1x1_bf16_forward(x2d: torch.Tensor, npix: int, c_in: int, w_plane: torch
     if npix <= 0 or xc < c_in or yc != c_out or x2d.shape[0] != npix or y2d.shape[0] != npix:
         raise BtsHipError("conv1x1_bf16_forward: views %s / %s do not fit %d pixels, %d -> %d channels"
                           % (tuple(x2d.shape), tuple(y2d.shape), npix, c_in, c_out))
-    if xs % 4 or ys % 4 or x2d.data_ptr() % 16 or y2d.data_ptr() % 16:
+    if xs % 4 or ys % 4 or x2d.data_ptr() % 16 or y2d.data_ptr() % (8 if y_bf16 else 16):
         raise BtsHipError("conv1x1_bf16_forward: rows must be 16-byte aligned (pixel strides %d / %d, multiples of 4 floats)" % (xs, ys))
     if (w_plane.dim() not in (2, 3) or (w_plane.dim() == 3 and w_plane.shape[0] != 1) or not w_plane.is_contiguous()
             or w_plane.shape[-2] < c_out or w_plane.shape[-1] < c_in or w_plane.shape[-1] % 32):
@@ -1231,17 +1249,75 @@ def conv1x1_bf16_forward(x2d: torch.Tensor, npix: int, c_in: int, w_plane: torch
     es, eb = _e2_vectors(e1, c_out, name, "e1")
     kern, flops, nbytes, xflops = "conv", 0.0, 0.0, None
     if _trace is not None:
-        kern = conv_plan.wide_1x1_bf16_kernel_name(192)
+        kern = conv_plan.wide_1x1_bf16_kernel_name(192, y_bf16)
         flops = 2.0 * npix * c_out * c_in
-        nbytes = 4.0 * npix * (c_in + c_out) + 2.0 * c_out * c_in
+        nbytes = 4.0 * npix * c_in + (2.0 if y_bf16 else 4.0) * npix * c_out + 2.0 * c_out * c_in
         xflops = 2.0 * (round_up(npix, 128)) * c_out * c_in                    # ragged last tile included
     tops = torch_ops()
     run = None
     if tops is not None:
-        run = lambda: _op(lambda: tops.conv1x1_bf16(x2d, w_plane, ps, pb, es, eb, y2d, [npix, c_in, c_out, int(bool(pre_relu)), int(act)]))
-    _enqueue("bts_conv1x1_bf16_fwd_f32", x2d,
+        top = tops.conv1x1_bf16_ybf16 if y_bf16 else tops.conv1x1_bf16
+        run = lambda: _op(lambda: top(x2d, w_plane, ps, pb, es, eb, y2d, [npix, c_in, c_out, int(bool(pre_relu)), int(act)]))
+    _enqueue("bts_conv1x1_bf16_fwd_bf16" if y_bf16 else "bts_conv1x1_bf16_fwd_f32", x2d,
              (_ptr(x2d), xs, npix, c_in, _ptr(w_plane), k_pad, c_out, cout_pad, _ptr(ps), _ptr(pb), int(bool(pre_relu)), _ptr(es), _ptr(eb),
               int(act), _ptr(y2d), ys), trace=(kern, tag, flops, nbytes, xflops), run=run)
+    return y2d
+
+
+# ---- 3x3 convolution reading a bf16-resident NHWC tensor on the bf16 halo tile (csrc/conv_3x3_bf16in.inc): the growth
+#      convolution of a dense layer whose bottleneck intermediate conv1x1_bf16_forward stored as bf16
+def conv3x3_bf16in_plan(h: int, w: int, c_in: int, c_out: int, fill_frames: Optional[int] = None) -> TailBf16Plan:
+    """Should this 3x3 layer (stride 1, padding 1, no prologue) read its input from a bf16 tensor with conv3x3_bf16in_forward?
+    Host-only query (bts_conv3x3_bf16in_plan): the layers conv_forward runs on the bf16 halo tile under precision "bf16",
+    less the classes measured to lose; (bn, workgroups of the declared launch), all 0 = stay on conv_forward.  ``fill_frames``
+    defaults to the launch_config in force."""
+    ff, _ = _resolve_launch(None, fill_frames, "conv3x3_bf16in_plan")
+    bn, wgs = C.c_int(0), C.c_long(0)
+    _lib.check(_lib.load_real().bts_conv3x3_bf16in_plan(int(h), int(w), int(c_in), int(c_out), int(ff), C.byref(bn), C.byref(wgs)),
+               "bts_conv3x3_bf16in_plan")
+    return TailBf16Plan((bn.value, wgs.value))
+
+
+def conv3x3_bf16in_forward(x2d: torch.Tensor, B: int, h: int, w: int, c_in: int, w_plane: torch.Tensor, c_out: int, y2d: torch.Tensor,
+                           e1: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, act: int = ACT_NONE, tag: str = "conv3x3_bf16in"):
+    """act(e1(conv3x3(x))) in one launch of the bf16 halo tile fed from a BFLOAT16 tensor (bts_conv3x3_bf16in_fwd_f32): x2d
+    [B*h*w, >= c_in] view of a bf16 NHWC buffer (c_in % 32 == 0 channels read), w_plane the one-plane bf16 form of the layer's
+    packed 3x3 weight (``round_bf16(w_packed)``: int16 [1, c_out_pad, k_pad], or the same bits as [c_out_pad, k_pad] /
+    bfloat16), e1 a (scale, shift) pair of >= c_out_pad floats, y2d [B*h*w, c_out] fp32 NHWC view (a channel slice is fine).
+    Bit for bit conv_forward under precision "bf16" on ``x2d.float()`` where that takes the bf16 halo tile.  Runs whatever
+    the plan query says: callers ask conv3x3_bf16in_plan first."""
+    name = "conv3x3_bf16in_forward"
+    xs, xc = _rows2d_bf16(x2d, name)
+    ys, yc = _rows2d(y2d, name)
+    if not isinstance(w_plane, torch.Tensor) or not w_plane.is_cuda or w_plane.dtype not in (torch.int16, torch.bfloat16):
+        raise BtsHipError("conv3x3_bf16in_forward: w_plane must be an int16 / bfloat16 CUDA/ROCm tensor (round_bf16 of the packed weight)")
+    if B <= 0 or h <= 0 or w <= 0 or c_in <= 0 or c_in % 32 or c_out <= 0:
+        raise BtsHipError("conv3x3_bf16in_forward: B=%d %dx%d, %d -> %d channels; needs c_in %% 32 == 0" % (B, h, w, c_in, c_out))
+    if xc < c_in or yc != c_out or x2d.shape[0] != B * h * w or y2d.shape[0] != B * h * w:
+        raise BtsHipError("conv3x3_bf16in_forward: views %s / %s do not fit B=%d %dx%d, %d -> %d channels"
+                          % (tuple(x2d.shape), tuple(y2d.shape), B, h, w, c_in, c_out))
+    if (w_plane.dim() not in (2, 3) or (w_plane.dim() == 3 and w_plane.shape[0] != 1) or not w_plane.is_contiguous()
+            or w_plane.shape[-2] < c_out or w_plane.shape[-2] % 32 or w_plane.shape[-1] < 9 * c_in or w_plane.shape[-1] % 8):
+        raise BtsHipError("conv3x3_bf16in_forward: w_plane %s must be contiguous [1, c_out_pad >= %d (a multiple of 32), k_pad >= %d]"
+                          % (tuple(w_plane.shape), c_out, 9 * c_in))
+    cout_pad, k_pad = int(w_plane.shape[-2]), int(w_plane.shape[-1])
+    _check_act3(act, name)
+    es, eb = _e2_vectors(e1, cout_pad, name, "e1")
+    kern, flops, nbytes, xflops = "conv", 0.0, 0.0, None
+    if _trace is not None:
+        bn = conv_plan.bf16in_3x3_tile(c_out)
+        kern = conv_plan.bf16in_3x3_kernel_name(bn)
+        flops = 2.0 * 9 * B * h * w * c_out * c_in
+        nbytes = 2.0 * B * h * w * c_in + 4.0 * B * h * w * c_out + 2.0 * 9 * c_out * c_in
+        tiles = B * ((h + 3) // 4) * ((w + 31) // 32)
+        xflops = 2.0 * 9 * (tiles * 128) * round_up(c_out, bn) * c_in             # ragged tiles included
+    tops = torch_ops()
+    run = None
+    if tops is not None:
+        run = lambda: _op(lambda: tops.conv3x3_bf16in(x2d, w_plane, es, eb, y2d, [B, h, w, c_in, c_out, int(act)]))
+    _enqueue("bts_conv3x3_bf16in_fwd_f32", x2d,
+             (_ptr(x2d), xs, B, h, w, c_in, _ptr(w_plane), k_pad, c_out, cout_pad, _ptr(es), _ptr(eb), int(act), _ptr(y2d), ys),
+             trace=(kern, tag, flops, nbytes, xflops), run=run)
     return y2d
 
 

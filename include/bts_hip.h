@@ -348,6 +348,55 @@ int bts_conv1x1_bf16_fwd_f32(const float* x, long x_pix_stride, long npix, int c
  *   all three 0 when the layer should stay on bts_conv_fwd_f32. */
 int bts_conv1x1_bf16_plan(int h, int w, int c_in, int c_out, int fill_frames, int* bm, int* bn, long* workgroups);
 
+/* bts_conv1x1_bf16_fwd_f32 with a BF16 destination: the first bf16-RESIDENT activation of the library (the bottleneck
+ * intermediate of a dense layer under BtsModel.bf16_mid_storage, read back by bts_conv3x3_bf16in_fwd_f32).  Everything the fp32
+ * entry point says about x, w_bf16, pre_*, e1_*, act, rounding of the operands, sum order and non-finite values holds; the
+ * value it would have stored, act(e1(sum)), is rounded ONCE more, to the nearest bf16 (ties to even; v_cvt_pk_bf16_f32, the
+ * conversion every precision-2 kernel applies to its input on the way to LDS: NaN stays NaN, infinity infinity), and stored
+ * in two bytes.  A consumer that rounds its input to bf16 anyway therefore sees the bits it would have seen.
+ *   y       : bf16 [npix] NHWC pixels, y_pix_stride >= c_out counted in BF16 ELEMENTS (a multiple of 4), base 8-byte aligned; a
+ *             channel slice of a wider buffer is fine: nothing is written outside [p][0 .. c_out)
+ * Every host check of bts_conv1x1_bf16_fwd_f32 applies, with the same two error codes (a pixel stride >= 2^26 elements
+ * included).  Any supported shape runs, whatever a plan query says. */
+int bts_conv1x1_bf16_fwd_bf16(const float* x, long x_pix_stride, long npix, int c_in, const void* w_bf16, int k_pad,
+                              int c_out, int c_out_pad, const float* pre_scale, const float* pre_shift, int pre_relu,
+                              const float* e1_scale, const float* e1_shift, int act, void* y, long y_pix_stride,
+                              bts_stream_t stream);
+
+/* A 3x3 convolution (stride 1, padding 1, dilation 1) whose input is a BF16 NHWC tensor, in one launch of the one-plane bf16
+ * halo tile (csrc/conv_3x3_bf16in.inc):
+ *   y[b][Y][X][n] = act( e1( sum_{tap, c < c_in} x[b][Y+dy][X+dx][c] * w_bf16[n][tap * c_in + c] ) ),   tap = 3 (dy+1) + (dx+1)
+ * Products of bf16 pairs are exact in fp32 and accumulate in fp32 (v_mfma_f32_32x32x16_bf16); pixels outside the map
+ * contribute 0; e1(a) = fma(a, e1_scale[n], e1_shift[n]).  NOTHING is rounded here: x and w_bf16 are supplied in bf16.  Where
+ * x holds the nearest-even rounding of an fp32 tensor, the result is bit for bit bts_conv_fwd_f32's at precision 2 on that
+ * tensor wherever that runs BTS_CONV_KIND_HALO_BF16 (same tile, sum order and epilogue).  Opt-in: bts_conv_fwd_f32 never takes
+ * this path on its own.
+ *   x       : bf16 NHWC [B,h,w], x_pix_stride >= c_in counted in bf16 elements (a multiple of 4), base 8-byte aligned;
+ *             c_in % 32 == 0.  A channel-prefix view is fine: channels >= c_in are never loaded.
+ *   w_bf16  : bf16 [c_out_pad][k_pad], k = tap * c_in + c, 16-byte aligned: the one-plane precision-2 form of the packed 3x3
+ *             weight (bts_amd/ops.py:round_bf16 of pack_conv_weight's matrix); k_pad % 8 == 0, k_pad >= 9 c_in
+ *   y       : fp32 NHWC [B,h,w], y_pix_stride >= c_out floats, 4-byte aligned (a channel slice is fine: nothing is written
+ *             outside it)
+ *   c_out_pad % 32 == 0, >= c_out (rows past c_out are read, never stored); act 0 none / 1 ReLU / 2 ELU; e1_* [c_out_pad] or
+ *   both NULL.  Output channels per workgroup: 128 where bts_conv_fwd_f32 would pick 128 for c_out, else 64.
+ * BTS_ERR_INVALID: null or misaligned operands, strides that are no multiple of 4 or too short, act == 3.
+ * BTS_ERR_UNSUPPORTED: c_in % 32 != 0, k_pad % 8 != 0 or < 9 c_in, B h w x_pix_stride >= 2^32, B h w >= 2^31,
+ * c_out_pad k_pad >= 2^32, 64 y_pix_stride >= 2^32 (the 32-bit offsets of bts_conv_tail_bf16_fwd_f32).  Any supported shape
+ * runs, whatever the plan query says.  Sum order fixed: bits do not depend on B. */
+int bts_conv3x3_bf16in_fwd_f32(const void* x, long x_pix_stride, int B, int h, int w, int c_in, const void* w_bf16, int k_pad,
+                               int c_out, int c_out_pad, const float* e1_scale, const float* e1_shift, int act, float* y,
+                               long y_pix_stride, bts_stream_t stream);
+
+/* Should a 3x3 layer whose input a caller could keep in bf16 take bts_conv3x3_bf16in_fwd_f32 (host-side query, no GPU work, no
+ * pointers)?  Accepted: exactly the layers for which bts_conv_plan_f32 answers BTS_CONV_KIND_HALO_BF16 at precision 2 with no
+ * prologue, no residual, no y2, stride 1, dilation 1 and NHWC output -- asked with a split-K workspace lent, as the encoder
+ * lends one (without one that answer covers a superset) -- less the classes the per-layer bench has lose
+ * (csrc/conv_mfma.hip: the constant and its source).  Per-frame geometry and the declared fill_frames (as in bts_conv_desc,
+ * 0 = the library default) only, never B.
+ *   *bn = output channels per workgroup (128 or 64), *workgroups = workgroups of the DECLARED launch (fill_frames frames);
+ *   both 0 when the layer should stay on bts_conv_fwd_f32 (and its input in fp32). */
+int bts_conv3x3_bf16in_plan(int h, int w, int c_in, int c_out, int fill_frames, int* bn, long* workgroups);
+
 /* The same wide bf16 tile at 128, 192 or 256 output channels per workgroup, with the bottleneck epilogue: ResNe(X)t's conv1 /
  * conv3 / stride-1 downsample 1x1 layers and DenseNet121's bottlenecks (c_out 128) in the precision-2 arithmetic.  Everything
  * bts_conv1x1_bf16_fwd_f32 says about x, w_bf16, pre_*, e1_*, y, act, rounding, sum order and non-finite values holds; added:
