@@ -124,6 +124,8 @@ ABI: Dict[str, Entry] = {
     # opt-in and not replayable by bts_plan_run: no plan kind (a recording reports it as a foreign launch)
     "bts_conv_grouped_fwd_f32": _launch(_vp, _l64, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _l64, _vp),
     "bts_conv_grouped_plan": _query(_i, _i, _i, _i, _i, _i, _i, _pi, _pi, _pl),
+    "bts_conv_grouped_bf16_fwd_f32": _launch(_vp, _l64, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _l64, _vp),
+    "bts_conv_grouped_bf16_plan": _query(_i, _i, _i, _i, _i, _i, _i, _pi, _pi, _pl),
     "bts_conv_grouped_wgrad_f32": _launch(_vp, _l64, _vp, _l64, _i, _i, _i, _i, _i, _vp, _vp, _l64, _vp),
     "bts_conv_grouped_wgrad_plan": _query(_i, _i, _i, _i, _i, _i, _l64, _pi, _pl),
     "bts_conv1x1_bf16_fwd_f32": _launch(_vp, _l64, _l64, _i, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _l64, _vp),

@@ -737,6 +737,13 @@ class BtsModel(nn.Module):
                                             # "bf16" / "bf16x3" stay on bundles in every mode; the training graph has its own
                                             # switch (grouped_conv_train).  A plan
                                             # cannot replay the native launch: with use_plans the forward raises BtsHipError
+        self.grouped_conv_bf16 = "bundles"  # ResNeXt's grouped 3x3 (eval forward, conv_precision "bf16" only): "bundles" = the bundle
+                                            # launch of that precision; "auto" = the bf16 grouped kernel
+                                            # (ops.conv_grouped_bf16_forward) where ops.conv_grouped_bf16_plan accepts
+                                            # the layer; "native" = on every stride-1 block with <= 16 channels per group and
+                                            # width % 64 == 0; any other value raises BtsHipError.  Nothing changes under "fp32" /
+                                            # "bf16x3", in training, or for grouped_conv, which keeps its meaning.  A plan
+                                            # cannot replay the launch: with use_plans the bf16 forward raises BtsHipError
         self.bf16_wide_1x1 = False          # DenseNet161's bottleneck 1x1 layers (eval forward, conv_precision "bf16" only): True runs
                                             # the ones ops.conv1x1_bf16_plan accepts on the wide bf16 tile
                                             # (ops.conv1x1_bf16_forward); nothing changes under "fp32" / "bf16x3", for
@@ -794,6 +801,20 @@ class BtsModel(nn.Module):
         if not (isinstance(value, (bool, int)) and value in (0, 1)) and value != "all":
             raise BtsHipError("BtsModel.bf16_wide_1x1 must be False, True or \"all\", got %r" % (value,))
         self.__dict__["_bf16_wide_1x1"] = value if value == "all" else bool(value)
+
+    GROUPED_BF16_MODES = ("bundles", "auto", "native")
+
+    @property
+    def grouped_conv_bf16(self) -> str:
+        """"bundles" (default), "auto" or "native": which of ResNeXt's grouped 3x3 layers an eval forward under conv_precision
+        "bf16" runs on the bf16 grouped kernel (see __init__); any other value raises BtsHipError."""
+        return self.__dict__.get("_grouped_conv_bf16", "bundles")
+
+    @grouped_conv_bf16.setter
+    def grouped_conv_bf16(self, value):
+        if not isinstance(value, str) or value not in self.GROUPED_BF16_MODES:
+            raise BtsHipError("BtsModel.grouped_conv_bf16 must be one of %s, got %r" % (self.GROUPED_BF16_MODES, value))
+        self.__dict__["_grouped_conv_bf16"] = value
 
     @property
     def bf16_mid_storage(self) -> bool:
@@ -865,6 +886,10 @@ class BtsModel(nn.Module):
                     and (self.bf16_wide_1x1 == "all" or not isinstance(self.encoder.base_model, encoders.ResNet))):
                 raise BtsHipError("BtsModel: bf16_wide_1x1 launches bts_conv1x1_bf16_fwd_f32 / bts_conv1x1_bf16_wide_fwd_f32, which a "
                                   "plan cannot replay; set use_plans = False or bf16_wide_1x1 = False")
+            if (self.grouped_conv_bf16 != "bundles" and ops.current_launch_config()[1] == 2
+                    and isinstance(self.encoder.base_model, encoders.ResNet)):
+                raise BtsHipError("BtsModel: grouped_conv_bf16 launches bts_conv_grouped_bf16_fwd_f32, which a plan cannot replay; "
+                                  "set use_plans = False or grouped_conv_bf16 = \"bundles\"")
             r = self._plans.forward(self, x, focal, slot, outs)
             if abs_mins is not None:
                 dec = self.decoder
@@ -885,6 +910,7 @@ class BtsModel(nn.Module):
         plan.bind(base, key_module=src_base)
         if cls is ResNetHip:
             plan.grouped_conv = self.grouped_conv
+            plan.grouped_conv_bf16 = self.grouped_conv_bf16
             plan.bf16_wide_1x1 = self.bf16_wide_1x1 == "all"
         else:
             plan.bf16_wide_1x1 = self.bf16_wide_1x1

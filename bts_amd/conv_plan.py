@@ -100,6 +100,12 @@ def grouped_kernel_name(cg: int) -> str:
     return "conv_grouped_kernel<%d>" % cg
 
 
+def grouped_bf16_kernel_name(cg: int) -> str:
+    """The kernel bts_conv_grouped_bf16_fwd_f32 launches for ``cg`` channels per group, as KernelTrace records it (does not
+    begin with grouped_kernel_name's prefix: launch counts tell the two kernels apart by it)."""
+    return "conv_grouped_bf16_kernel<%d>" % cg
+
+
 def grouped_wgrad_kernel_name(cg: int) -> str:
     """The kernel bts_conv_grouped_wgrad_f32 launches for ``cg`` channels per group, as KernelTrace records it (its reduce
     launch rides in the same record)."""

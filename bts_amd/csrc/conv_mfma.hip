@@ -849,6 +849,7 @@ int conv_launch(const ConvRun& r, const ConvChoice& choice, int too_many, long t
 #include "conv_up9.inc"
 #include "conv_wino_tail.inc"
 #include "conv_grouped.inc"
+#include "conv_grouped_bf16.inc"
 #include "conv_grouped_wgrad.inc"
 #include "conv_tail_bf16.inc"
 #include "conv_3x3_bf16in.inc"
@@ -1515,6 +1516,48 @@ extern "C" int bts_conv_grouped_fwd_f32(const float* x, long x_pix_stride, int B
     const int rc = cg == 16 ? bts_launch<conv_grouped_kernel<16>>(grid, dim3(256), 0, s, a)
                  : cg == 8  ? bts_launch<conv_grouped_kernel<8>>(grid, dim3(256), 0, s, a)
                             : bts_launch<conv_grouped_kernel<4>>(grid, dim3(256), 0, s, a);
+    return rc != 0 ? rc : (int)hipGetLastError();
+}
+
+// ---- the same layers with bf16 operands on v_mfma_f32_16x16x16_bf16 (conv_grouped_bf16.inc): opt-in beside the bundle
+//      launch of precision 2, as bts_conv_grouped_fwd_f32 is beside that of precision 0
+extern "C" int bts_conv_grouped_bf16_plan(int h, int w, int c, int groups, int precision, int fill_frames, int* bm, int* bn,
+                                          long* workgroups) {
+    int ff, prec;
+    if (!bm || !bn || !workgroups || !resolve_declaration(fill_frames, precision, &ff, &prec)) return BTS_ERR_INVALID;
+    long wgs = 0;
+    const bool ok = grouped_bf16_eligible(h, w, c, groups, prec, ff, &wgs);
+    *bm = ok ? GR_TH * GR_TW : 0; *bn = ok ? 64 : 0; *workgroups = ok ? wgs : 0;
+    return 0;
+}
+
+extern "C" int bts_conv_grouped_bf16_fwd_f32(const float* x, long x_pix_stride, int B, int h, int w, int c, int groups,
+                                             const void* w_packed_bf16, const float* e1_scale, const float* e1_shift, int act,
+                                             float* y, long y_pix_stride, bts_stream_t stream) {
+    if (!x || !w_packed_bf16 || !y || B <= 0 || h <= 0 || w <= 0 || c <= 0 || groups <= 0 || (c % groups)) return BTS_ERR_INVALID;
+    if (!act_e2_ok(act, e1_scale, e1_shift)) return BTS_ERR_INVALID;
+    if (!grouped_supported(c, groups)) return BTS_ERR_UNSUPPORTED;
+    if (!nhwc_view_ok(x, x_pix_stride, c) || !nhwc_view_ok(y, y_pix_stride, c) || ((uintptr_t)w_packed_bf16 & 15) ||
+        ((uintptr_t)e1_scale & 15) || ((uintptr_t)e1_shift & 15)) return BTS_ERR_INVALID;
+    // the kernel counts pixels and tiles in 32 bits (addresses are 64-bit)
+    if ((double)B * h * w >= 2147483648.0) return BTS_ERR_UNSUPPORTED;
+    GroupedBf16Args a;
+    a.x = x; a.x_pix_stride = x_pix_stride; a.B = B; a.H = h; a.W = w; a.w = static_cast<const unsigned short*>(w_packed_bf16);
+    a.e1_scale = e1_scale; a.e1_shift = e1_shift; a.act = act; a.y = y; a.y_pix_stride = y_pix_stride;
+    double fill;
+    grouped_grid(h, w, &a.n_ty, &a.n_tx, &fill);
+    const long tiles = (long)B * a.n_ty * a.n_tx;
+    const int slabs = c / 64;
+    if (tiles > 0x7fffffffL || slabs > 65535) return BTS_ERR_UNSUPPORTED;
+    a.tiles = (int)tiles;
+    // persistent workgroups: what the chip holds at two per CU, shared among the slabs
+    const long chunks = tiles < (GR_RESIDENT + slabs - 1) / slabs ? tiles : (GR_RESIDENT + slabs - 1) / slabs;
+    const dim3 grid((unsigned)chunks, (unsigned)slabs);
+    const int cg = c / groups;
+    hipStream_t s = (hipStream_t)stream;
+    const int rc = cg == 16 ? bts_launch<conv_grouped_bf16_kernel<16>>(grid, dim3(256), 0, s, a)
+                 : cg == 8  ? bts_launch<conv_grouped_bf16_kernel<8>>(grid, dim3(256), 0, s, a)
+                            : bts_launch<conv_grouped_bf16_kernel<4>>(grid, dim3(256), 0, s, a);
     return rc != 0 ? rc : (int)hipGetLastError();
 }
 

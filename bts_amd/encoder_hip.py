@@ -268,6 +268,12 @@ class ResNetHip:
     Stride-2 blocks, groups of 32 / 64 channels (nothing redundant to remove) and the bf16 / bf16x3 precisions stay on
     bundles in every mode; the training graph (bts_amd/train.py) never reads the attribute.
 
+    ``grouped_conv_bf16`` (BtsModel.grouped_conv_bf16 sets it): the same three values for forwards whose launch precision is
+    bf16, the only ones that read it: "bundles" (default); "auto" = the bf16 grouped kernel (ops.conv_grouped_bf16_forward,
+    one 16-channel block x one tap per v_mfma_f32_16x16x16_bf16) on the layers ops.conv_grouped_bf16_plan accepts;
+    "native" = on every stride-1 block with at most 16 channels per group and width % 64 == 0.  ``grouped_conv`` keeps its
+    meaning: under bf16 it still issues no native launch, and under fp32 / bf16x3 this switch changes nothing.
+
     ``bf16_wide_1x1`` (BtsModel sets it, True for its "all"): under the bf16 launch precision conv1, conv3 (identity, final ReLU
     and skip tap in the epilogue) and a stride-1 downsample 1x1 run on the wide bf16 tile (ops.conv1x1_bf16_wide_forward)
     wherever ops.conv1x1_bf16_wide_plan accepts the layer; stride-2 downsamples, the 3x3 / grouped layers, the stem and widths
@@ -278,6 +284,7 @@ class ResNetHip:
     def __init__(self, model: nn.Module, key_module: Optional[nn.Module] = None):
         self.model = model
         self.grouped_conv = "bundles"
+        self.grouped_conv_bf16 = "bundles"
         self.bf16_wide_1x1 = False
         self.key_module = key_module if key_module is not None else model
         self._pack = None
@@ -321,7 +328,8 @@ class ResNetHip:
                 b = dict(w1=w1, e1=_bn_vecs(blk.bn1, co1), w2=w2, nb=nb, cb=cb, cg=blk.conv2.in_channels // g,
                          e2=_bn_vecs(blk.bn2, ops.round_up(width, 32)), w3=w3, e3=_bn_vecs(blk.bn3, co3),
                          stride=blk.conv2.stride[0], width=width, c_out=blk.conv3.out_channels, down=None,
-                         groups=g, conv2=blk.conv2, w2n=None)        # w2n: ops.pack_grouped_native, made on first use
+                         groups=g, conv2=blk.conv2, w2n=None,        # w2n: ops.pack_grouped_native, made on first use
+                         w2nb=None)                                  # w2nb: ops.pack_grouped_native_bf16, likewise
                 if blk.downsample is not None:
                     wd, cod, _ = ops.pack_conv_weight(blk.downsample[0].weight.detach())
                     b["down"] = dict(w=wd, e1=_bn_vecs(blk.downsample[1], cod), stride=blk.downsample[0].stride[0])
@@ -339,6 +347,15 @@ class ResNetHip:
             for b in blocks:
                 if b["nb"] > 1 and b["w2n"] is None and b["stride"] == 1 and b["cg"] <= 16 and b["width"] % 64 == 0:
                     b["w2n"] = ops.pack_grouped_native(b["conv2"].weight.detach(), b["groups"])
+        torch.cuda.current_stream(device).synchronize()
+
+    def _pack_grouped_native_bf16(self, P, device):
+        """The bf16 native-form weights (ops.pack_grouped_native_bf16) of every block the bf16 entry point supports: all at
+        once on the first forward that needs one and finished before this returns, as _pack_grouped_native."""
+        for blocks in P["layers"]:
+            for b in blocks:
+                if b["nb"] > 1 and b["w2nb"] is None and b["stride"] == 1 and b["cg"] <= 16 and b["width"] % 64 == 0:
+                    b["w2nb"] = ops.pack_grouped_native_bf16(b["conv2"].weight.detach(), b["groups"])
         torch.cuda.current_stream(device).synchronize()
 
     def _round_1x1_planes(self, P, device):
@@ -371,6 +388,15 @@ class ResNetHip:
         if mode == "bundles" or b["stride"] != 1 or b["cg"] > 16 or b["width"] % 64 or ops.current_launch_config()[1] != 0:
             return False
         return mode == "native" or ops.conv_grouped_plan(h, w, b["width"], b["groups"]).eligible
+
+    def _grouped_native_bf16(self, b, h, w) -> bool:
+        """Does this block's grouped 3x3 (input map h x w) take the bf16 grouped kernel under ``self.grouped_conv_bf16``?"""
+        mode = self.grouped_conv_bf16
+        if mode not in self.GROUPED_MODES:
+            raise ops.BtsHipError("ResNetHip.grouped_conv_bf16 must be one of %s, got %r" % (self.GROUPED_MODES, mode))
+        if mode == "bundles" or b["stride"] != 1 or b["cg"] > 16 or b["width"] % 64 or ops.current_launch_config()[1] != 2:
+            return False
+        return mode == "native" or ops.conv_grouped_bf16_plan(h, w, b["width"], b["groups"]).eligible
 
     def _workspace(self, B, H, W, device, slot=0):
         return self._ws.get((B, H, W, str(device), slot), lambda: self._alloc_workspace(B, H, W, device))
@@ -435,6 +461,11 @@ class ResNetHip:
                         self._pack_grouped_native(P, dev)
                     ops.conv_grouped_forward(t1, B, h, w, b["w2n"], b["width"], b["groups"], e1=b["e2"], act=RELU, y2d=t2,
                                              tag=tag + "_g3x3")
+                elif b["nb"] > 1 and self._grouped_native_bf16(b, h, w):
+                    if b["w2nb"] is None:
+                        self._pack_grouped_native_bf16(P, dev)
+                    ops.conv_grouped_bf16_forward(t1, B, h, w, b["w2nb"], b["width"], b["groups"], e1=b["e2"], act=RELU, y2d=t2,
+                                                  tag=tag + "_g3x3")
                 elif b["nb"] > 1:
                     ops.conv_forward(t1, B, h, w, b["w2"], b["cb"], 3, stride=s, pad=1, c_in_ld=b["cb"], e1=b["e2"], act=RELU,
                                      y2d=t2, n_bundles=b["nb"], tag=tag + "_g3x3", c_in_real=b["cg"])

@@ -82,12 +82,12 @@ class GraphedModel(torch.nn.Module):
             return self.model(image, focal)
         fshape = tuple(focal.shape) if isinstance(focal, torch.Tensor) else None
         # a capture bakes in the model's launch declaration (fill_frames by the batch unless pinned, precision, bf16_tail_convs,
-        # bf16_wide_1x1 -- False, True and "all" are three different captures --, bf16_mid_storage)
+        # bf16_wide_1x1 -- False, True and "all" are three different captures --, bf16_mid_storage, grouped_conv_bf16)
         wide = getattr(self.model, "bf16_wide_1x1", False)
         key = (tuple(image.shape), str(image.device), str(image.dtype), fshape,
                getattr(self.model, "fill_frames", None), getattr(self.model, "conv_precision", 0),
                bool(getattr(self.model, "bf16_tail_convs", False)), "all" if wide == "all" else bool(wide),
-               bool(getattr(self.model, "bf16_mid_storage", False)))
+               bool(getattr(self.model, "bf16_mid_storage", False)), getattr(self.model, "grouped_conv_bf16", "bundles"))
         entry = self._graphs.get(key)
         if entry is not None and entry.fingerprint != self._fingerprint():
             self._drop(key)                         # weights changed since capture: the graph points at stale packs

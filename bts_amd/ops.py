@@ -1599,6 +1599,76 @@ def conv_grouped_forward(x2d: torch.Tensor, B: int, h: int, w: int, w_packed: to
     return y2d
 
 
+# ---- the same layers with bf16 operands (csrc/conv_grouped_bf16.inc), opt-in beside the bundle launch of precision "bf16"
+def pack_grouped_native_bf16(w: torch.Tensor, groups: int) -> torch.Tensor:
+    """Grouped [c, c/groups, 3, 3] weight -> the 144 * c bfloat16 bts_conv_grouped_bf16_fwd_f32 reads (include/bts_hip.h; no
+    padding tap): index (((s*9 + tap)*4 + b)*64 + lane)*4 + j = the weight from input channel 64 s + 16 b + 4 (lane >> 4) + j
+    to output channel 64 s + 16 b + (lane & 15), rounded by Tensor.to(torch.bfloat16) (nearest, ties to even), exact zeros
+    where the two lie in different groups.  Once per weight (ResNetHip.packed caches it)."""
+    c, cg = _grouped_native_shape(w, groups)
+    wv = w.detach().float().to(torch.bfloat16).reshape(c // 64, 4, 16, cg, 9)   # [slab, block, row, k in group, tap]
+    k = torch.arange(16, device=w.device)
+    full = wv[:, :, :, k % cg, :]                                           # [slab, block, row, k in block, tap]
+    same = (k[:, None] // cg) == (k[None, :] // cg)                         # [row, k]: one group
+    full = torch.where(same[None, None, :, :, None], full, torch.zeros((), dtype=torch.bfloat16, device=w.device))
+    full = full.reshape(c // 64, 4, 16, 4, 4, 9)                            # [slab, block, row, k-quad, j, tap]
+    return full.permute(0, 5, 1, 3, 2, 4).contiguous().view(-1)             # (slab, tap, block, k-quad, row, j): lane = 16 k-quad + row
+
+
+def pack_grouped_native_bf16_reference(w: torch.Tensor, groups: int) -> torch.Tensor:
+    """Index-by-index statement of pack_grouped_native_bf16, kept as its test oracle: every flat index decoded as the header
+    writes it."""
+    c, cg = _grouped_native_shape(w, groups)
+    wc = w.detach().float().cpu().to(torch.bfloat16)
+    idx = torch.arange(144 * c)
+    j, lane, b, tap, s = idx % 4, (idx // 4) % 64, (idx // 256) % 4, (idx // 1024) % 9, idx // 9216
+    n, ci = 64 * s + 16 * b + lane % 16, 64 * s + 16 * b + 4 * (lane // 16) + j       # output channel, input channel
+    val = wc[n, ci % cg, tap // 3, tap % 3]
+    return torch.where(ci // cg == n // cg, val, torch.zeros((), dtype=torch.bfloat16)).to(w.device)
+
+
+def conv_grouped_bf16_plan(h: int, w: int, c: int, groups: int, precision=None, fill_frames: Optional[int] = None) -> GroupedPlan:
+    """Should this grouped 3x3 layer take conv_grouped_bf16_forward?  Host-only query (bts_conv_grouped_bf16_plan);
+    ``precision`` / ``fill_frames`` default to the launch_config in force; only precision "bf16" is ever eligible."""
+    ff, pr = _resolve_launch(precision, fill_frames, "conv_grouped_bf16_plan")
+    bm, bn, wgs = C.c_int(0), C.c_int(0), C.c_long(0)
+    _lib.check(_lib.load_real().bts_conv_grouped_bf16_plan(int(h), int(w), int(c), int(groups), int(pr), int(ff), C.byref(bm),
+                                                            C.byref(bn), C.byref(wgs)), "bts_conv_grouped_bf16_plan")
+    return GroupedPlan((bm.value, bn.value, wgs.value))
+
+
+def conv_grouped_bf16_forward(x2d: torch.Tensor, B: int, h: int, w: int, w_packed: torch.Tensor, c: int, groups: int,
+                              e1: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, act: int = ACT_NONE,
+                              y2d: Optional[torch.Tensor] = None, tag: str = "grouped_conv"):
+    """act(e1(grouped conv3x3(bf16(x), bf16(w)))) in one launch of the bf16 grouped kernel (bts_conv_grouped_bf16_fwd_f32):
+    the views, e1 and y2d of conv_grouped_forward (fp32 in and out), w_packed the 144 * c bfloat16 of
+    pack_grouped_native_bf16.  Runs whatever the plan query says: callers ask conv_grouped_bf16_plan first."""
+    name = "conv_grouped_bf16_forward"
+    xs, xc = _rows2d(x2d, name)
+    if y2d is None:
+        y2d = torch.empty((B * h * w, c), dtype=torch.float32, device=x2d.device)
+    ys, yc = _rows2d(y2d, name)
+    cg = _grouped_cg(c, groups, name)
+    if xc < c or yc != c or x2d.shape[0] != B * h * w or y2d.shape[0] != B * h * w:
+        raise BtsHipError("conv_grouped_bf16_forward: views %s / %s do not fit B=%d %dx%d, %d channels"
+                          % (tuple(x2d.shape), tuple(y2d.shape), B, h, w, c))
+    if (not isinstance(w_packed, torch.Tensor) or w_packed.dtype != torch.bfloat16 or w_packed.numel() != 144 * c
+            or not w_packed.is_contiguous() or w_packed.device != x2d.device):
+        raise BtsHipError("conv_grouped_bf16_forward: w_packed must come from pack_grouped_native_bf16 (144 * c bfloat16)")
+    _check_act3(act, name)
+    es, eb = _e2_vectors(e1, c, name, "e1")
+    kern, flops, nbytes, xflops = "conv", 0.0, 0.0, None
+    if _trace is not None:
+        kern = conv_plan.grouped_bf16_kernel_name(cg)
+        flops = 2.0 * B * h * w * c * cg * 9
+        nbytes = 4.0 * 2 * B * h * w * c + 2.0 * 9 * c * cg
+        xflops = 2.0 * 9 * 16 * (B * ((h + 7) // 8) * ((w + 15) // 16) * 128) * c    # 16-channel blocks, ragged tiles included
+    _enqueue("bts_conv_grouped_bf16_fwd_f32", x2d,
+             (_ptr(x2d), xs, B, h, w, c, groups, _ptr(w_packed), _ptr(es), _ptr(eb), int(act), _ptr(y2d), ys),
+             trace=(kern, tag, flops, nbytes, xflops))
+    return y2d
+
+
 def _grouped_cg(c: int, groups: int, who: str) -> int:
     if c <= 0 or groups <= 0 or c % groups:
         raise BtsHipError("%s: %d channels do not split into %d groups" % (who, c, groups))

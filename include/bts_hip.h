@@ -490,6 +490,30 @@ int bts_conv_grouped_fwd_f32(const float* x, long x_pix_stride, int B, int h, in
  *   FRAME; all three 0 when the layer should stay on bundles. */
 int bts_conv_grouped_plan(int h, int w, int c, int groups, int precision, int fill_frames, int* bm, int* bn, long* workgroups);
 
+/* The same grouped 3x3 convolution with bf16 operands (the arithmetic of bts_conv_desc.precision = 2) in one launch of the
+ * bf16 grouped kernel (csrc/conv_grouped_bf16.inc, v_mfma_f32_16x16x16_bf16: one 16-channel block x one tap per MFMA):
+ *   y[p][n] = act( e1( sum_{tap, k < cg} bf16(x[q(p, tap)][cg * (n / cg) + k]) * bf16(w[n][k][tap]) ) ),   tap = 3 (dy+1) + (dx+1)
+ * x is rounded to bf16 (nearest, ties to even) on its way to LDS, padding is an exact zero; products are exact in fp32 and
+ * accumulate in fp32; e1 and act as above, in fp32.  Opt-in: bts_conv_fwd_f32 never takes this path on its own.
+ *   x, y          : as bts_conv_grouped_fwd_f32 (fp32 NHWC, pixel strides >= c floats and multiples of 4, 16-byte aligned)
+ *   w_packed_bf16 : 144 * c bf16 (no padding tap), 16-byte aligned (bts_amd/ops.py:pack_grouped_native_bf16): bf16 index
+ *                   (((s * 9 + tap) * 4 + b) * 64 + lane) * 4 + j = the weight from input channel
+ *                   ci = 64 s + 16 b + 4 (lane >> 4) + j to output channel n = 64 s + 16 b + (lane & 15):
+ *                   bf16_rne(w[n][ci mod cg][tap]) when ci lies in n's group, else 0 (cg < 16: block-diagonal)
+ *   e1_scale, e1_shift : as bts_conv_grouped_fwd_f32
+ * Any supported shape runs, whatever bts_conv_grouped_bf16_plan says.  c % 64 != 0 or cg outside {4, 8, 16}: BTS_ERR_UNSUPPORTED.
+ * Sum order fixed (tap-major, the 16 channels of a block inside one MFMA): a frame's bits depend neither on B nor on
+ * fill_frames.  Non-finite values: as bts_conv_grouped_fwd_f32 (own 16-channel block, 3x3 neighbourhood). */
+int bts_conv_grouped_bf16_fwd_f32(const float* x, long x_pix_stride, int B, int h, int w, int c, int groups,
+                                  const void* w_packed_bf16, const float* e1_scale, const float* e1_shift, int act, float* y,
+                                  long y_pix_stride, bts_stream_t stream);
+
+/* Should a grouped layer take bts_conv_grouped_bf16_fwd_f32 (host-side query, no GPU work, no pointers)?  Eligible only for
+ * precision 2, c % 64 == 0, cg in {4, 8, 16}, and the tile-grid fill and declared-launch thresholds written next to the
+ * constants in csrc/conv_grouped_bf16.inc (fill_frames as in bts_conv_desc, 0 = the library default; never B).
+ *   *bm = 128, *bn = 64, *workgroups = (tile, slab) pairs PER FRAME; all three 0 when the layer should stay on bundles. */
+int bts_conv_grouped_bf16_plan(int h, int w, int c, int groups, int precision, int fill_frames, int* bm, int* bn, long* workgroups);
+
 /* Weight gradient of the same grouped 3x3 convolution (csrc/conv_grouped_wgrad.inc, v_mfma_f32_16x16x1_4b_f32: one
  * instruction accumulates four 16 x 16 (output channel x input channel) blocks from one dy and one x float per lane):
  *   dw[n][k][tap] = sum_{b, p} dy[b, p][n] * x[b, q(p, tap)][cg * (n / cg) + k],   tap = 3 (dy+1) + (dx+1)
